@@ -20,7 +20,11 @@ per frame as the reference runs 2D models, lib/core/test.py:212-214).  `--mode t
 per step instead: forward + losses + backward + gradient all-reduce (RCCL when N > 1) + momentum SGD on a resident clip with
 resident labels (`training.Trainer.step`).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline`, `cpu_baseline` and (bf16) `accuracy_vs_fp32`.
+Prints ONE JSON line (rank 0) with the driver's contract fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`).
+A plain run does only what that line needs: set up, warm up, time `--steps` steps, print.  `--full` adds everything else the
+benchmark measures, as further fields of the same line: `roofline` / `roofline_hbm` (per-launch profilers, back-to-back passes, the
+rocprofv3 child run), `host_frames`, (bf16) `accuracy_vs_fp32`, `cpu_baseline`, the other arithmetic modes and `other_configs`.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -646,7 +650,15 @@ def main():
     ap.add_argument('--keyframe-dce', action='store_true',
                     help='opt-in cfg.HIP.KEYFRAME_DCE: compute only the centre frame of the FPN outputs that slice-center keeps '
                          '(identical detections; NOT the default, the default materialises every frame like the reference)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every measurement beyond the headline (roofline and per-kernel passes, host-frame leg, accuracy vs fp32, '
+                         'CPU baselines, other precisions and configs; each still subject to its --no-* switch). Off: set up, warm up, '
+                         'time --steps steps, print the headline line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64)')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be >= 1')
     if a.dtype == 'fp16' and os.environ.get('DAT_H16', 'bf16') != 'fp16':
         # the 16-bit format is a property of the library build, chosen when it is loaded: the same command line again with the fp16 build
         # (under a launcher every rank does this for itself)
@@ -725,10 +737,11 @@ def main():
         slots = [(ws, torch.cuda.current_stream())]
 
         xstats = []
+        last = {}       # the last step's executor (its loss blobs): what --dump-outputs writes
 
         def run_steps(n, timing=False):
             for _ in range(n):
-                trainer.step(1e-4, timing=timing)
+                last['ex'] = trainer.step(1e-4, timing=timing)
                 if timing and trainer.last_exchange_stats:
                     xstats.append(dict(trainer.last_exchange_stats))
             torch.cuda.synchronize()
@@ -742,18 +755,20 @@ def main():
                       for g in range(fwd_per_step)] for i in range(2)]
         else:
             clips = [[torch.cat([synthetic_clip(T, H, W, 1000 * rank + 10 * i + f) for f in range(B)]).contiguous().cuda()] for i in range(2)]
-        pipe = ClipPipeline(model, ws, a.pipeline, graph=a.graph, fifo=a.fifo, keep_results=False)
+        # (results are kept on the host only for --dump-outputs)
+        pipe = ClipPipeline(model, ws, a.pipeline, graph=a.graph, fifo=a.fifo, keep_results=bool(a.dump_outputs))
         slots = [(sl.ws, sl.stream) for sl in pipe.slots]
 
         # the input blobs are resident in HBM (the contract of `value`); in the benched bf16 mode the graphs read them where they
         # lie -- one captured graph per (slot, input buffer) -- instead of copying 99 MB per clip into a private graph input first
         resident_in = a.dtype in ('bf16', 'fp16') and bool(a.graph) and os.environ.get('DAT_BENCH_RESIDENT', '1') != '0'   # (env: A/B switch)
+        last = {}       # (tag = (step, forward of the step), per-image results) of the last run_steps call: what --dump-outputs writes
 
         def run_steps(n):
             for i in range(n):
-                for unit in clips[i % 2]:
-                    pipe.submit(unit, im_info, im_shape, resident=resident_in)
-            pipe.drain()
+                for u, unit in enumerate(clips[i % 2]):
+                    pipe.submit(unit, im_info, im_shape, tag=(i, u), resident=resident_in)
+            last['results'], last['steps'] = pipe.drain(), n
 
     torch.cuda.synchronize()
     _dbg('built')
@@ -783,29 +798,37 @@ def main():
                 pr = ops.ConvProfiler(capacity=cap)
                 pr.start()
                 profs.append(pr)
-    if not train and not a.no_roofline:
+    if not train and not a.no_roofline and a.full:
         start_profilers()
     _dbg('profilers started')
     barrier()
     torch.cuda.synchronize()
     if not train:
         pipe.host_enqueue_s = 0.0
-    power = PowerSampler(find_hwmon(device_identity(rank, local_rank).get('pci')) if rank == 0 else None).start()
+    power = PowerSampler(find_hwmon(device_identity(rank, local_rank).get('pci')) if rank == 0 else None).start() if a.full else None
     t0 = time.perf_counter()
     run_steps(a.steps)
     barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    power = power.stop()
+    power = power.stop() if power is not None else None
     _dbg('timed region done')
-    if a.no_roofline:       # (the rocprofv3 child: its kernel_stats.csv must hold whole graph-replayed forwards and nothing else)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last, trainer if train else None)
+        _dbg('outputs written')
+    if a.no_roofline or not a.full:
+        # (plain run, and the rocprofv3 child of --full: its kernel_stats.csv must hold whole graph-replayed forwards and nothing else)
         elapsed = max_over_ranks(elapsed)
         if dist is not None:
             dist.destroy_process_group()
         if rank == 0:
-            print(json.dumps({'metric': 'clips/sec (8-frame 800px)', 'value': round(a.gpus * a.steps * (1 if train else clips_per_step) / elapsed, 4),
-                              'unit': 'clips/s', 'n_gpus': a.gpus, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': round(1e3 * elapsed / a.steps, 3),
-                              'dtype': a.dtype, 'roofline': None, 'note': '--no-roofline: timed region only'}), flush=True)
+            out = headline(a, elapsed, train, None if train else pipe, 512 if train else pipe.n_det, None if train else resident_in, world,
+                           ranks_seen, share_gpu, B, clips_per_step, fwd_per_step)
+            if not train:
+                out['host_enqueue_ms_per_step'] = round(1e3 * pipe.host_enqueue_s / a.steps, 3)
+            if a.no_roofline:
+                out.update(roofline=None, note='--no-roofline: timed region only')
+            print(json.dumps(out), flush=True)
         return
     records, conv_log, mhz = [], [], []
 
@@ -1119,49 +1142,9 @@ def main():
     if all_tflop_per_step > 0 and step_s > 0:
         roofline['whole_step_tflops'] = round(all_tflop_per_step / step_s, 2)
         roofline['whole_step_frac'] = round(all_tflop_per_step / step_s / peak, 4)
-    if train:
-        workload = ('3D R-%s FPN3D keypoint R-CNN TRAINING iteration, 1x3x%dx%dx%d clip per step per GPU (forward + 13 losses + backward + '
-                    '%s + momentum SGD; 2000 proposals, 512 sampled rois; labels resident)'
-                    % (a.arch, T, H, W, 'bucketed gradient all-reduce over %d ranks' % world if world > 1 else 'no gradient exchange at 1 rank'))
-    elif two_d:
-        workload = ('2D R-%s-FPN keypoint R-CNN inference, a step = %d frames of 1x3x%dx%d run as %d forward(s) of %d frame(s) '
-                    '(per frame: 1000 proposals, %d detections in the last frame -> kps_score -> decoded keypoints)'
-                    % (a.arch, T, H, W, fwd_per_step, B, n_det))
-    elif best2d:
-        workload = ('configs/video/2d_best/01_R101_best_hungarian.yaml model (R-101 FPN3D body with NUM_FRAMES 1 / TIME_KERNEL_DIM 1, slice-center, 2-MLP box head, '
-                    '2D keypoint head): %d frames of 1x3x1x%dx%d per step (= per forward) per GPU; `value` counts FRAMES/s (per frame: 1000 proposals, %d '
-                    'detections -> kps_score -> decoded keypoints)' % (B, H, W, n_det))
-    elif tube:
-        workload = ('3D R-%s FPN3D keypoint R-CNN with TUBE heads (declared extension of the reference\'s dead FPN3D RPN design), %d clip(s) of '
-                    '1x3x%dx%dx%d per step per GPU (kT=3 body+FPN kept 3D to the heads, tube RPN per level, tube rois on the 2-MLP head, 3D keypoint '
-                    'head; per clip: 1000 tube proposals, %d tube detections -> kps_score [R, 17*T, 56, 56] -> decoded keypoints)'
-                    % (a.arch, B, T, H, W, n_det))
-    else:
-        workload = ('3D R-%s FPN3D keypoint R-CNN inference, %d clip(s) of 1x3x%dx%dx%d per step (= per forward) per GPU '
-                    '(kT=3 body+FPN, slice-center 2D heads, per clip: 1000 proposals, %d detections -> kps_score -> decoded keypoints)'
-                    % (a.arch, B, T, H, W, n_det))
-    out = {
-        'metric': 'clips/sec (8-frame 800px)', 'value': round(value, 4), 'unit': 'clips/s',
-        'n_gpus': a.gpus, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': round(1e3 * elapsed / a.steps, 3),
-        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': a.dtype, 'data': 'synthetic',
-        'config': {'workload': workload, 'mode': a.mode, 'name': a.workload,
-                   'weights': 'random-init (synthetic_params, seed 3)', 'clips_per_step_per_gpu': 1 if train else clips_per_step,
-                   'images_per_forward': 1 if train else B,
-                   'forwards_in_flight': 1 if train else a.pipeline, 'clips_in_flight': 1 if train else a.pipeline * clips_per_step,
-                   'keyframe_dce': bool(a.keyframe_dce),
-                   'hip_graph': bool(graph_on),
-                   # share of the CUs the persistent HBM-bound conv kernels take while several forwards are in flight (cfg.HIP.PERSISTENT_CU_SHARE)
-                   'persistent_kernel_cu_share_percent': 100 if train else int(getattr(pipe, 'persistent_share', 100)),
-                   # since round 4 the benched graphs read the caller's resident input buffers IN PLACE (rounds 1-3 copied the 99 MB
-                   # per clip device-to-device into a private graph input first): `value` is not comparable with rounds 1-3 by that copy
-                   'resident_input': bool(resident_in) if not train else True,
-                   'parallelism': ('data-parallel x%d, one bucketed RCCL gradient all-reduce per iteration' if train else
-                                   'clip-sharded x%d (no data-path collective)') % a.gpus},
-        'ranks_seen': ranks_seen,
-        **({'shared_gpu_test': 'DAT_BENCH_SHARE_GPU=1: %d ranks on ONE device over gloo -- a control-flow test, NOT a measurement' % world} if share_gpu else {}),
-        'roofline': roofline,
-        'roofline_hbm': roofline_hbm,
-    }
+    out = headline(a, elapsed, train, None if train else pipe, n_det, None if train else resident_in, world, ranks_seen, share_gpu, B,
+                   clips_per_step, fwd_per_step)
+    out.update(roofline=roofline, roofline_hbm=roofline_hbm)
     if train:
         # the one exchange step of the path: per-bucket sum all-reduce of the flat gradient buffer, started as the backward pass completes
         # each bucket (training.GradExchange).  allreduce_ms = time the collectives ran on the communication stream, exposed = time the
@@ -1218,6 +1201,97 @@ def main():
         dist.destroy_process_group()
 
 
+def headline(a, elapsed, train, pipe, n_det, resident_in, world, ranks_seen, share_gpu, B, clips_per_step, fwd_per_step):
+    """The contract fields of the result line -- the rate of the timed steps and what they ran -- as a plain run prints them; --full
+    appends its measurements to this dict."""
+    T, H, W = a.frames, a.height, a.width
+    two_d, tube, best2d = a.workload == '2d_r50_fpn', a.workload.endswith('_tube'), a.workload == '2d_best_r101'
+    graph_on = (not train) and pipe.use_graph and len(pipe.slots[0].graphs) > 0
+    value = a.gpus * a.steps * (1 if train else clips_per_step) / elapsed
+    if train:
+        workload = ('3D R-%s FPN3D keypoint R-CNN TRAINING iteration, 1x3x%dx%dx%d clip per step per GPU (forward + 13 losses + backward + '
+                    '%s + momentum SGD; 2000 proposals, 512 sampled rois; labels resident)'
+                    % (a.arch, T, H, W, 'bucketed gradient all-reduce over %d ranks' % world if world > 1 else 'no gradient exchange at 1 rank'))
+    elif two_d:
+        workload = ('2D R-%s-FPN keypoint R-CNN inference, a step = %d frames of 1x3x%dx%d run as %d forward(s) of %d frame(s) '
+                    '(per frame: 1000 proposals, %d detections in the last frame -> kps_score -> decoded keypoints)'
+                    % (a.arch, T, H, W, fwd_per_step, B, n_det))
+    elif best2d:
+        workload = ('configs/video/2d_best/01_R101_best_hungarian.yaml model (R-101 FPN3D body with NUM_FRAMES 1 / TIME_KERNEL_DIM 1, slice-center, 2-MLP box head, '
+                    '2D keypoint head): %d frames of 1x3x1x%dx%d per step (= per forward) per GPU; `value` counts FRAMES/s (per frame: 1000 proposals, %d '
+                    'detections -> kps_score -> decoded keypoints)' % (B, H, W, n_det))
+    elif tube:
+        workload = ('3D R-%s FPN3D keypoint R-CNN with TUBE heads (declared extension of the reference\'s dead FPN3D RPN design), %d clip(s) of '
+                    '1x3x%dx%dx%d per step per GPU (kT=3 body+FPN kept 3D to the heads, tube RPN per level, tube rois on the 2-MLP head, 3D keypoint '
+                    'head; per clip: 1000 tube proposals, %d tube detections -> kps_score [R, 17*T, 56, 56] -> decoded keypoints)'
+                    % (a.arch, B, T, H, W, n_det))
+    else:
+        workload = ('3D R-%s FPN3D keypoint R-CNN inference, %d clip(s) of 1x3x%dx%dx%d per step (= per forward) per GPU '
+                    '(kT=3 body+FPN, slice-center 2D heads, per clip: 1000 proposals, %d detections -> kps_score -> decoded keypoints)'
+                    % (a.arch, B, T, H, W, n_det))
+    return {
+        'metric': 'clips/sec (8-frame 800px)', 'value': round(value, 4), 'unit': 'clips/s',
+        'n_gpus': a.gpus, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': round(1e3 * elapsed / a.steps, 3),
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': a.dtype, 'data': 'synthetic',
+        'config': {'workload': workload, 'mode': a.mode, 'name': a.workload,
+                   'weights': 'random-init (synthetic_params, seed 3)', 'clips_per_step_per_gpu': 1 if train else clips_per_step,
+                   'images_per_forward': 1 if train else B,
+                   'forwards_in_flight': 1 if train else a.pipeline, 'clips_in_flight': 1 if train else a.pipeline * clips_per_step,
+                   'keyframe_dce': bool(a.keyframe_dce),
+                   'hip_graph': bool(graph_on),
+                   # share of the CUs the persistent HBM-bound conv kernels take while several forwards are in flight (cfg.HIP.PERSISTENT_CU_SHARE)
+                   'persistent_kernel_cu_share_percent': 100 if train else int(getattr(pipe, 'persistent_share', 100)),
+                   # ADVICE r4: since round 4 the benched graphs read the caller's resident input buffers IN PLACE (rounds 1-3 copied the 99 MB
+                   # per clip device-to-device into a private graph input first): `value` is not comparable with rounds 1-3 by that copy
+                   'resident_input': bool(resident_in) if not train else True,
+                   'parallelism': ('data-parallel x%d, one bucketed RCCL gradient all-reduce per iteration' if train else
+                                   'clip-sharded x%d (no data-path collective)') % a.gpus},
+        'ranks_seen': ranks_seen,
+        **({'shared_gpu_test': 'DAT_BENCH_SHARE_GPU=1: %d ranks on ONE device over gloo -- a control-flow test, NOT a measurement' % world} if share_gpu else {}),
+    }
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+WEIGHT_SAMPLE = 1 << 22     # elements of the updated flat weight buffer written by a training run (a fixed, seeded sample when larger)
+
+
+def dump_outputs(out_dir, last, trainer=None):
+    """--dump-outputs: what the LAST timed step handed its caller, as out_dir/<name>.npy (float32, or float64 where the result is).
+    Inference: per image of the step (forwards of the step in order, images of a forward in order) `imNN_boxes` [n, 5]
+    (x1, y1, x2, y2, score of every detection of the foreground classes) and `imNN_keypoints` [n, 4, K] (the decoded keypoint rows of
+    the person detections).  Training: `loss_<blob>` (one value per loss blob) and `weights` (the updated trainable weights after the
+    step's SGD update, flat; a seeded sample of WEIGHT_SAMPLE elements when the buffer is larger)."""
+    def f(x):
+        x = np.asarray(x)
+        return x.astype(np.float64 if x.dtype == np.float64 else np.float32)
+    arrays = {}
+    if trainer is not None:
+        for name, v in sorted(last['ex'].loss_values().items()):
+            arrays['loss_' + ''.join(c if c.isalnum() or c in '_-' else '_' for c in name)] = np.array([v], np.float32)
+        w = trainer.flat_w
+        n = int(w.numel())
+        if n > WEIGHT_SAMPLE:
+            idx = np.sort(np.random.RandomState(0).randint(0, n, size=WEIGHT_SAMPLE))
+            w = w[torch.from_numpy(idx).to(w.device)]
+        arrays['weights'] = f(w.detach().float().cpu().numpy())
+    else:
+        step = last['steps'] - 1
+        k = 0
+        for (_, u), per_image in sorted(((tag, res) for tag, res in last['results'] if tag[0] == step), key=lambda tr: tr[0][1]):
+            for cls_boxes, _, cls_keyps in per_image:
+                boxes = [np.asarray(b, np.float32).reshape(-1, 5) for b in cls_boxes[1:]]
+                arrays['im%02d_boxes' % k] = f(np.concatenate(boxes) if boxes else np.zeros((0, 5), np.float32))
+                kps = [kp for per_cls in (cls_keyps or [])[1:] for kp in per_cls]
+                arrays['im%02d_keypoints' % k] = f(np.stack(kps) if kps else np.zeros((0,), np.float32))
+                k += 1
+        assert k > 0, 'no results of the last timed step'
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, 'outputs of %d bytes exceed the %d-byte limit' % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), v)
+
+
 def _child_env():
     return {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT',
                                                               'GROUP_RANK', 'ROLE_RANK', 'LOCAL_WORLD_SIZE', 'TORCHELASTIC_RUN_ID')}
@@ -1229,7 +1303,7 @@ def precision_mode_run(dtype, steps=5, warmup=2):
     (tests/test_gpu_parity_full.py), printed next to the bf16 `value`."""
     import subprocess
     cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', str(warmup), '--dtype', dtype,
-           '--no-cpu-baseline', '--no-accuracy', '--no-other-configs', '--no-rocprof-check', '--h2d', '0']
+           '--full', '--no-cpu-baseline', '--no-accuracy', '--no-other-configs', '--no-rocprof-check', '--h2d', '0']
     try:
         p = subprocess.run(cmd, env=_child_env(), stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=240)
         d = json.loads(p.stdout.decode().strip().splitlines()[-1])
@@ -1246,7 +1320,7 @@ def fp16_mode_run(steps=20, warmup=5):
     the arithmetic costs against the fp32 parity mode of the same model on the benched clip -- the figures `accuracy_vs_fp32` gives for bf16."""
     import subprocess
     cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', str(warmup), '--dtype', 'fp16',
-           '--no-cpu-baseline', '--no-other-configs', '--no-rocprof-check', '--h2d', '0']
+           '--full', '--no-cpu-baseline', '--no-other-configs', '--no-rocprof-check', '--h2d', '0']
     try:
         p = subprocess.run(cmd, env=_child_env(), stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=300)
         d = json.loads(p.stdout.decode().strip().splitlines()[-1])
@@ -1287,7 +1361,7 @@ def other_configs():
     except Exception as e:   # noqa: BLE001
         res['config5_end_to_end'] = {'error': '%s: %s' % (type(e).__name__, e)}
     for name, extra in runs:
-        cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '10', '--warmup', '3', '--no-cpu-baseline',
+        cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '10', '--warmup', '3', '--full', '--no-cpu-baseline',
                '--no-accuracy', '--no-other-configs', '--no-rocprof-check'] + extra
         try:
             p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=120)

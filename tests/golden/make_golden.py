@@ -4,13 +4,13 @@
 Cython NMS/IoU compiled into oracle/_ref (oracle/build_ref.py).
 
 Run in the build container only (needs /root/reference):
-    python tests/golden/make_golden.py            (everything; or one generator: --only-cfg | --only-roi-data | --only-lr | --only-blob |
+    python tests/golden/make_golden.py            (everything; or one generator: --only-cython | --only-affine-gpu (on the GPU) | --only-cfg | --only-roi-data | --only-lr | --only-blob |
                                                    --only-decode | --only-tracker | --only-builders | --only-weights | --only-clips | --only-postproc | --only-dataset)
 Writes tests/golden/: reference_host.npz (anchors, transforms, IoU / NMS, GenerateProposals, RoIToBatchFormat, level mapping, collect /
 distribute, inflation), reference_roi_data.npz (training labels, boxes and tubes), reference_lr_policy.npz (schedules + the momentum
 correction rule), reference_postproc.npz, reference_posetrack_annorect.json, reference_blob.npz, reference_decode.npz,
-reference_tracker.json, reference_cfg_defaults.json / reference_cfg_files.json, reference_builder_nets.json.gz (the graphs the
-reference's builder functions emit) + reference_heatmap_outputs.json (the keypoint output function on a 3D head, both deconv variants), reference_weights_load.npz (checkpoint loading), reference_clips.json (clip assembly), synthetic_posetrack.json + reference_json_dataset.npz / .json (the dataset layer: JsonDataset.get_roidb and get_clip's tube ground truth on a synthetic COCO-format file).  The shims do not change any arithmetic:
+reference_tracker.json, reference_cfg_defaults.json / reference_cfg_files.json (+ reference_configs/: the shipped yaml files), reference_builder_nets.json.gz (the graphs the
+reference's builder functions emit) + reference_heatmap_outputs.json (the keypoint output function on a 3D head, both deconv variants), reference_weights_load.npz (checkpoint loading), reference_clips.json (clip assembly), synthetic_posetrack.json + reference_json_dataset.npz / .json (the dataset layer: JsonDataset.get_roidb and get_clip's tube ground truth on a synthetic COCO-format file).  reference_cython.npz: the compiled Cython's answers on the fuzz cases of the tests that compare against it live.  reference_affine_gpu.json: digests of the reference AffineChannelNd op's outputs (--only-affine-gpu, on the GPU).  The shims do not change any arithmetic:
   * removed NumPy aliases (np.float/np.int), py2 builtins (basestring, unicode),
     cPickle -> pickle, bytes config defaults decoded to str;
   * caffe2 / cv2 / pycocotools are replaced by inert stub modules so that pure
@@ -19,6 +19,7 @@ reference's builder functions emit) + reference_heatmap_outputs.json (the keypoi
 import builtins
 import os
 import pickle
+import shutil
 import sys
 import types
 
@@ -653,6 +654,10 @@ def golden_cfg_files(cfg):
         rc.assert_and_infer_cfg()
         now = flat(rc.cfg)
         res[os.path.relpath(f, '/root/reference/configs')] = {k: v for k, v in now.items() if k not in base or base[k] != v}
+        # the file itself, verbatim: the fixture the cfg tests of tests/test_host_cpu.py load (reference_configs/video/<dir>/<file>)
+        dst = os.path.join(HERE, 'reference_configs', *f.split(os.sep)[-3:])
+        os.makedirs(os.path.dirname(dst), exist_ok=True)
+        shutil.copyfile(f, dst)
     for k in list(rc.cfg.keys()):
         rc.cfg[k] = copy.deepcopy(default[k])
     _yaml.load = _load
@@ -1155,8 +1160,100 @@ def golden_postproc(cfg):
     print('wrote reference_postproc.npz', len(out), 'arrays')
 
 
+def fuzz_cases():
+    """The inputs of tests/test_oracle_golden.py test_oracle_vs_compiled_reference_live: (n, dets [n, 5], query boxes [17, 4]) drawn in order
+    from RandomState(11)."""
+    rs = np.random.RandomState(11)
+    out = []
+    for n in (1, 5, 64, 257, 700):
+        b = rs.uniform(0, 100, (n, 4)).astype(np.float32)
+        b[:, 2:] = b[:, :2] + rs.uniform(1, 60, (n, 2)).astype(np.float32)
+        d = np.hstack((b, rs.uniform(0, 1, (n, 1)).astype(np.float32)))
+        q = rs.uniform(0, 100, (17, 4)).astype(np.float32)
+        q[:, 2:] = q[:, :2] + rs.uniform(1, 60, (17, 2)).astype(np.float32)
+        out.append((n, d, q))
+    return out
+
+
+def large_nms_dets(n):
+    """The input of tests/test_gpu_kernels.py test_nms_beyond_4096_boxes_bit_exact_vs_reference_cython (its _random_dets, span 2000)."""
+    rs = np.random.RandomState(n)
+    b = rs.uniform(0, 2000.0, (n, 4)).astype(np.float32)
+    b[:, 2:] = b[:, :2] + rs.uniform(1, 80, (n, 2)).astype(np.float32)
+    return np.hstack((b, rs.uniform(0, 1, (n, 1)).astype(np.float32)))
+
+
+LARGE_NMS_SIZES = (4097, 8191, 12000, 16384)
+
+
+def golden_cython():
+    """reference_cython.npz: what the reference's compiled Cython (oracle/_ref) returns on the fuzz cases of the tests that compare
+    against it, so that they run where oracle/_ref was never built: cython_nms.nms keep indices (fuzz cases at 0.3 / 0.5 / 0.7, large
+    cases at 0.5 / 0.7) and cython_bbox.bbox_overlaps; the fuzz inputs themselves, and the float64 sum of every large input (its
+    boxes are drawn again from the seed)."""
+    from oracle import build_ref
+    build_ref.build()
+    nms_mod, bbox_mod = build_ref.load()
+    res = {}
+    for n, d, q in fuzz_cases():
+        res['fuzz_%d_dets' % n], res['fuzz_%d_query' % n] = d, q
+        for thr in (0.3, 0.5, 0.7):
+            res['fuzz_%d_keep_%g' % (n, thr)] = np.asarray(nms_mod.nms(d, np.float32(thr)), np.int64)
+        res['fuzz_%d_overlaps' % n] = np.asarray(bbox_mod.bbox_overlaps(d[:, :4], q))
+    for n in LARGE_NMS_SIZES:
+        d = large_nms_dets(n)
+        res['large_%d_dets_sum' % n] = np.array(d.astype(np.float64).sum())
+        for thr in (0.5, 0.7):
+            res['large_%d_keep_%g' % (n, thr)] = np.asarray(nms_mod.nms(d, np.float32(thr)), np.int64)
+    np.savez_compressed(os.path.join(HERE, 'reference_cython.npz'), **res)
+    print('wrote reference_cython.npz', len(res), 'arrays')
+
+
+AFFINE_SHAPES = ((2, 5, 7), (1, 64, 8, 48, 84), (3, 16, 4, 4), (1, 3, 2, 5, 5), (4, 256, 1), (1, 64, 3, 191, 333), (8, 2048, 1, 24, 42))
+
+
+def golden_affine_gpu():
+    """reference_affine_gpu.json (needs the GPU and oracle/_ref/libref_affine.so): SHA-256 of the bytes the reference's own
+    AffineChannelNd op writes -- forward out of place, forward in place, gradient -- on the inputs of tests/test_gpu_kernels.py
+    test_affine_channel_nd_matches_the_reference_cuda_op_compiled_for_gfx950 (RandomState(5) per shape), which checks against them
+    where oracle/_ref was never built."""
+    import ctypes as C
+    import hashlib
+    import json
+    import torch
+    from oracle import build_ref
+    lib = build_ref.load_affine()
+    assert lib is not None and torch.cuda.is_available(), 'needs oracle/_ref/libref_affine.so and a GPU'
+
+    def digest(t):
+        torch.cuda.synchronize()
+        return hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
+    res = {}
+    err = C.create_string_buffer(256)
+    for shape in AFFINE_SHAPES:
+        rs = np.random.RandomState(5)
+        n, c = shape[0], shape[1]
+        inner = int(np.prod(shape[2:]))
+        x = (rs.randn(*shape) * 3).astype(np.float32)
+        s = rs.uniform(0.5, 1.5, c).astype(np.float32)
+        b = rs.randn(c).astype(np.float32)
+        xd, sd, bd = [torch.from_numpy(v).cuda() for v in (x, s, b)]
+        y, x2, g = torch.empty_like(xd), xd.clone(), torch.empty_like(xd)
+        assert lib.ref_affine_channel_nd_fwd(xd.data_ptr(), sd.data_ptr(), bd.data_ptr(), y.data_ptr(), n, c, inner, c, err, 256) == 0, err.value
+        assert lib.ref_affine_channel_nd_fwd(x2.data_ptr(), sd.data_ptr(), bd.data_ptr(), x2.data_ptr(), n, c, inner, c, err, 256) == 0, err.value
+        assert lib.ref_affine_channel_nd_bwd(sd.data_ptr(), xd.data_ptr(), g.data_ptr(), n, c, inner, c, err, 256) == 0, err.value
+        res['x'.join(str(v) for v in shape)] = {'fwd': digest(y), 'fwd_in_place': digest(x2), 'bwd': digest(g)}
+    with open(os.path.join(HERE, 'reference_affine_gpu.json'), 'w') as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+    print('wrote reference_affine_gpu.json', len(res), 'shapes')
+
+
 if __name__ == '__main__':
-    if '--only-postproc' in sys.argv:
+    if '--only-cython' in sys.argv:
+        golden_cython()
+    elif '--only-affine-gpu' in sys.argv:
+        golden_affine_gpu()
+    elif '--only-postproc' in sys.argv:
         golden_postproc(_install_shims())
     elif '--only-tracker' in sys.argv:
         golden_tracker(_install_shims())
@@ -1190,3 +1287,4 @@ if __name__ == '__main__':
         golden_weights(sys.modules['core.config'].cfg)
         golden_clips(sys.modules['core.config'].cfg)
         golden_dataset(sys.modules['core.config'].cfg)
+        golden_cython()

@@ -1222,7 +1222,7 @@ def test_bench_two_gpus_smoke(mode):
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     env['HSA_ENABLE_IPC_MODE_LEGACY'] = '0'
-    cmd = [sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '2', '--no-cpu-baseline',
+    cmd = [sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '2', '--full', '--no-cpu-baseline',
            '--no-accuracy', '--no-other-configs', '--h2d', '0'] + (['--mode', 'train'] if mode == 'train' else [])
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
@@ -1249,7 +1249,7 @@ def test_bench_two_ranks_control_flow_on_one_gpu(mode):
     env.update(DAT_BENCH_SHARE_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     port = 29500 + ((os.getpid() + 211 + (mode == 'train')) % 1000)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1', '--master-port', str(port),
-           os.path.join(repo, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--no-accuracy'] + (['--mode', 'train'] if mode == 'train' else [])
+           os.path.join(repo, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full', '--no-accuracy'] + (['--mode', 'train'] if mode == 'train' else [])
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith('{')]
@@ -1262,6 +1262,41 @@ def test_bench_two_ranks_control_flow_on_one_gpu(mode):
         assert line['allreduce']['buckets'] >= 2 and line['allreduce']['backend'] == 'gloo'
     else:
         assert line['roofline']['frac'] > 0 and line['host_frames']['value_including_upload'] > 0
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: one line with the contract fields and exactly K
+    timed steps, none of the --full measurements, and the last step's per-clip boxes / keypoint rows as float32 .npy files -- the same
+    arrays from a second run with the same arguments."""
+    import json
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / ('run%d' % run))
+        cmd = [sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '2', '--pipeline', '2',
+               '--dump-outputs', d]
+        p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith('{')]
+        assert len(lines) == 1, lines
+        line = json.loads(lines[0])
+        assert line['steps'] == 3 and line['value'] > 0 and line['ms_per_step'] > 0 and line['higher_is_better'] is True
+        assert line['unit'] == 'clips/s' and line['dtype'] == 'bf16' and line['metric'].startswith('clips/sec')
+        assert abs(line['value'] - 2 * 1e3 / line['ms_per_step']) <= 1e-3 * line['value']
+        for k in ('roofline', 'host_frames', 'accuracy_vs_fp32', 'cpu_baseline', 'other_configs'):
+            assert k not in line, k
+        names = sorted(os.listdir(d))
+        assert names == ['im00_boxes.npy', 'im00_keypoints.npy', 'im01_boxes.npy', 'im01_keypoints.npy'], names
+        arrs = {n: np.load(os.path.join(d, n)) for n in names}
+        assert all(a.dtype == np.float32 for a in arrs.values())
+        assert arrs['im00_boxes.npy'].shape[1] == 5 and arrs['im00_boxes.npy'].shape[0] > 0
+        assert arrs['im00_keypoints.npy'].shape[0] == arrs['im00_boxes.npy'].shape[0]
+        dumps.append(arrs)
+    for n in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][n], dumps[1][n])
 
 
 @pytest.mark.parametrize('mode', ['infer', 'train'])
@@ -1279,7 +1314,7 @@ def test_bench_eight_ranks_control_flow_on_one_gpu(mode):
     env.update(DAT_BENCH_SHARE_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     port = 29500 + ((os.getpid() + 617 + (mode == 'train')) % 1000)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '8', '--master-addr', '127.0.0.1', '--master-port', str(port),
-           os.path.join(repo, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--no-accuracy', '--no-other-configs', '--h2d', '0'] + (['--mode', 'train'] if mode == 'train' else ['--batch', '1', '--pipeline', '1'])
+           os.path.join(repo, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--full', '--no-accuracy', '--no-other-configs', '--h2d', '0'] + (['--mode', 'train'] if mode == 'train' else ['--batch', '1', '--pipeline', '1'])
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith('{')]

@@ -87,10 +87,12 @@ def test_cfg_defaults_and_merge(tmp_path):
     reset_cfg()
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/configs'), reason='reference configs not mounted')
+REF_CONFIGS = os.path.join(REPO, 'tests', 'golden', 'reference_configs')     # the reference's shipped yaml files (make_golden.py golden_cfg_files)
+
+
 def test_every_shipped_reference_yaml_loads():
     from detectandtrack_amd.core.config import cfg, cfg_from_file, assert_and_infer_cfg, reset_cfg
-    files = sorted(glob.glob('/root/reference/configs/video/*/*.yaml'))
+    files = sorted(glob.glob(os.path.join(REF_CONFIGS, 'video', '*', '*.yaml')))
     assert len(files) == 12
     for f in files:
         reset_cfg()
@@ -1077,6 +1079,34 @@ def test_reference_affine_op_library_is_built_from_the_reference_source_and_expo
     assert '#include REF_AFFINE_CU' in drv and 'CUDA_1D_KERNEL_LOOP' not in drv and '__global__' not in drv
 
 
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """bench.py --dump-outputs: the results of the LAST step only (forwards of the step in order, images in order), boxes of every
+    foreground class [n, 5] and the person keypoint rows [n, 4, K] as float32 .npy files; --full and --dump-outputs are options."""
+    import bench
+    rs = np.random.RandomState(0)
+
+    def image(n):
+        kps = [rs.rand(4, 17).astype(np.float32) for _ in range(n)]
+        return ([[], rs.rand(n, 5).astype(np.float32)], None, [[], kps] if n else None)
+    step0 = [((0, 0), [image(3)]), ((0, 1), [image(1)])]
+    step1 = [((1, 1), [image(0), image(2)]), ((1, 0), [image(4)])]      # (completion order differs from submission order)
+    bench.dump_outputs(str(tmp_path / 'out'), {'results': step0 + step1, 'steps': 2})
+    names = sorted(os.listdir(str(tmp_path / 'out')))
+    assert names == ['im%02d_%s.npy' % (k, w) for k in range(3) for w in ('boxes', 'keypoints')]
+    want = [step1[1][1][0], step1[0][1][0], step1[0][1][1]]
+    for k, (cls_boxes, _, cls_keyps) in enumerate(want):
+        b = np.load(str(tmp_path / 'out' / ('im%02d_boxes.npy' % k)))
+        kp = np.load(str(tmp_path / 'out' / ('im%02d_keypoints.npy' % k)))
+        assert b.dtype == np.float32 and kp.dtype == np.float32
+        np.testing.assert_array_equal(b, cls_boxes[1])
+        if cls_keyps:
+            np.testing.assert_array_equal(kp, np.stack(cls_keyps[1]))
+        else:
+            assert kp.size == 0 and b.shape == (0, 5)
+    src = open(os.path.join(REPO, 'bench.py')).read()
+    assert "'--full', action='store_true'" in src and "'--dump-outputs'" in src
+
+
 def test_bench_power_sampler_reads_an_amdgpu_hwmon_tree(tmp_path):
     """bench.py's `roofline.power_over_timed_region`: the hwmon directory is found by PCI address (or as the only one), power is read from
     power1_average | power1_input in microwatts, the clock from freq1_input in Hz; a box without the files reports None."""
@@ -1286,7 +1316,6 @@ def test_cfg_has_every_key_and_default_of_the_real_reference_config():
     assert cfg.RPN.ON is False
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/configs'), reason='reference configs not mounted')
 def test_every_shipped_yaml_gives_the_effective_config_the_real_reference_computes():
     """cfg_from_file + assert_and_infer_cfg against lib/core/config.py ITSELF on all 12 shipped configs (tests/golden/make_golden.py
     golden_cfg_files): yaml load, the type rules of _merge_a_into_b, the TIME_KERNEL_DIM int-to-dict mapping (:826-858) and the inferred
@@ -1311,7 +1340,7 @@ def test_every_shipped_yaml_gives_the_effective_config_the_real_reference_comput
     try:
         for rel, want in sorted(ref.items()):
             reset_cfg()
-            cfg_from_file(os.path.join('/root/reference/configs', rel))
+            cfg_from_file(os.path.join(REF_CONFIGS, rel))
             assert_and_infer_cfg()
             now = flat(cfg)
             got = {k: v for k, v in now.items() if not k.startswith('HIP.') and (k not in base or base[k] != v)}

@@ -1,5 +1,7 @@
 """Oracle (CPU restatement) vs golden vectors produced by the REAL reference code
 (tests/golden/make_golden.py) and vs the reference's compiled Cython (oracle/_ref)."""
+import os
+
 import numpy as np
 import pytest
 
@@ -101,24 +103,23 @@ def test_fpn_level_map_and_distribute(golden):
 
 
 def test_oracle_vs_compiled_reference_live():
-    """When oracle/_ref holds the compiled reference Cython, fuzz the oracle against it."""
+    """Fuzz the oracle against the reference's compiled Cython: against its answers stored in tests/golden/reference_cython.npz
+    (make_golden.py golden_cython: the RandomState(11) cases) everywhere, and live as well when oracle/_ref holds the compiled modules."""
     from oracle import build_ref
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_cython.npz'))
     mods = build_ref.load()
-    if mods is None:
-        pytest.skip('oracle/_ref not built')
-    ref_nms, ref_bbox = mods
-    rs = np.random.RandomState(11)
-    for n in (0, 1, 5, 64, 257, 700):
-        if n == 0:
-            continue
-        b = rs.uniform(0, 100, (n, 4)).astype(np.float32)
-        b[:, 2:] = b[:, :2] + rs.uniform(1, 60, (n, 2)).astype(np.float32)
-        d = np.hstack((b, rs.uniform(0, 1, (n, 1)).astype(np.float32)))
+    for n in (1, 5, 64, 257, 700):
+        d, q = g['fuzz_%d_dets' % n], g['fuzz_%d_query' % n]
+        b = np.ascontiguousarray(d[:, :4])
         for thr in (0.3, 0.5, 0.7):
-            np.testing.assert_array_equal(on.nms_boxes(d, thr), ref_nms.nms(d, np.float32(thr)))
-        q = rs.uniform(0, 100, (17, 4)).astype(np.float32)
-        q[:, 2:] = q[:, :2] + rs.uniform(1, 60, (17, 2)).astype(np.float32)
-        np.testing.assert_array_equal(ob.bbox_overlaps_2d(b, q), ref_bbox.bbox_overlaps(b, q))
+            keep = on.nms_boxes(d, thr)
+            np.testing.assert_array_equal(keep, g['fuzz_%d_keep_%g' % (n, thr)])
+            if mods is not None:
+                np.testing.assert_array_equal(keep, mods[0].nms(d, np.float32(thr)))
+        ov = ob.bbox_overlaps_2d(b, q)
+        np.testing.assert_array_equal(ov, g['fuzz_%d_overlaps' % n])
+        if mods is not None:
+            np.testing.assert_array_equal(ov, mods[1].bbox_overlaps(b, q))
 
 
 def test_gpu_nms_restatement_known_answers():
