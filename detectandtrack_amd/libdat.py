@@ -163,6 +163,10 @@ for _name, (_res, _args) in _PROTOS.items():
     _fn = getattr(_lib, _name)  # AttributeError here == header/library mismatch
     _fn.restype = _res
     _fn.argtypes = _args
+# a library of the other 16-bit flavour than DAT_H16 would read every 16-bit tensor in the wrong format, silently
+_fmt = _lib.dat_h16_format()
+assert _fmt == (1 if H16 == 'fp16' else 0), ('DAT_LIB=%s holds the %s build of the library but DAT_H16=%s: set DAT_H16 to the format '
+                                            'of the library DAT_LIB names' % (LIB_PATH, 'fp16' if _fmt == 1 else 'bf16', H16))
 
 
 class Ctx(object):

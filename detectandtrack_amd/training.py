@@ -908,8 +908,11 @@ class Trainer(object):
 
     def __init__(self, model, ws, dist=None):
         self.model, self.ws, self.dist = model, ws, dist
-        from detectandtrack_amd.workspace import _x3
-        assert not _x3(ws), "cfg.HIP.DTYPE 'bf16x3' is an inference mode (train in 'bf16' or 'fp32')"
+        from detectandtrack_amd.workspace import _mode
+        # 'bf16x3' and 'fp16' are inference modes: no fp16 training path is tested or benched, and there is no loss scaling
+        mode = getattr(ws, 'dtype', None) or cfg.HIP.DTYPE
+        assert mode in ('bf16', 'fp32'), "cfg.HIP.DTYPE %r is an inference mode (train in 'bf16' or 'fp32')" % (mode,)
+        _mode(ws)       # (the 16-bit mode must match the loaded build)
         self.trainable = list(model.TrainableParams())
         self.biases = set(model.biases)
         self.iter = 0

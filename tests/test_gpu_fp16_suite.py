@@ -1,0 +1,95 @@
+"""The fp16 library build (libdat_hip_f16.so: the same sources with -DDAT_H16_IS_FP16, cfg.HIP.DTYPE 'fp16'), kernel by kernel.
+
+The 16-bit format belongs to the loaded library, so the format-generic kernel tests run again in ONE child process started with
+DAT_H16=fp16: tests/test_gpu_kernels.py, tests/test_gpu_fp16_edges.py and the persistent-kernel test of tests/test_gpu_model.py.
+The parent reads the child's JUnit report: no failure or error, every skip is a bf16-only test, and one test per kernel family (plus
+the NMS and proposal goldens) is among the passed -- so that a collection mistake cannot pass for a green run.  The child is never
+retried."""
+import os
+import subprocess
+import sys
+import time
+import xml.etree.ElementTree as ET
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CHILD_FILES = ['tests/test_gpu_kernels.py', 'tests/test_gpu_fp16_edges.py',
+               'tests/test_gpu_model.py::test_persistent_kernel_cu_share_does_not_change_results']
+
+K = 'tests.test_gpu_kernels::'
+E = 'tests.test_gpu_fp16_edges::'
+MUST_PASS = [
+    K + 'test_layout_roundtrip[1]',
+    K + 'test_conv3d[3x3x3-bf16]',                                   # generic kernel + the split-K finish
+    K + 'test_conv3d[heads_100x14x14_c512-bf16]',
+    K + 'test_conv3x3_c64_weights_stationary[res2_like]',           # ws64
+    K + 'test_conv1x1_k64_c256_weights_stationary[many_tiles]',     # 256-channel pointwise
+    K + 'test_conv3x3_linear_320_position_tiles',
+    K + 'test_conv3x3x3_linear_strips_per_frame[2x4x24x42_128_256-bp128_ks3]',
+    K + 'test_conv3x3x3_linear_strips_with_key_frame_outputs',
+    K + 'test_conv3x3_big_tile[3x3x3_ragged_16x16]',
+    K + 'test_conv_block_order_switch_is_bit_identical[split_k_4_cout_blocks]',
+    K + 'test_conv3d_large_pointwise_layers[group4_k256_sum-bf16]',
+    K + 'test_conv1x1_weights_in_lds_kernel[k128_c512_sum]',        # lw
+    K + 'test_conv1x1_k_streaming_kernel[k1024_c256_mask]',         # ks
+    K + 'test_stem_conv1[1]',
+    K + 'test_fused_stem_conv_matches_torch[bf16]',
+    K + 'test_fused_stem_and_maxpool_at_bench_size',
+    K + 'test_stem_conv_pool_fused_equals_two_kernels[False-shape1-bf16]',
+    K + 'test_stem_from_uint8_frames_is_bit_identical_to_the_blob_path[720-1280-800-1333-2-32-bf16]',
+    K + 'test_maxpool[1]',
+    K + 'test_roi_align_single_level[1]',
+    K + 'test_kps_tail[1]',
+    K + 'test_conv_one_pixel_wide_tiles[bf16]',
+    K + 'test_full_size_layers_spot_checked[4]',
+    K + 'test_batched_proposals_collect_and_box_results_equal_the_one_image_calls[1]',
+    K + 'test_device_preprocessing_is_bit_identical_to_the_host_path[720-1280-800-1333-1-32]',
+    K + 'test_nms_boxes_bit_exact_vs_reference[nms_n1000_t7]',
+    K + 'test_nms_beyond_4096_boxes_bit_exact_vs_reference_cython[12000]',
+    K + 'test_rpn_proposals_vs_reference_golden[gp_fpn3]',
+    K + 'test_box_results_on_device_match_the_real_reference[pp_boxes_k5]',
+    K + 'test_heatmaps_to_keypoints_matches_the_oracle[1-0-56-9]',
+    E + 'test_sums_beyond_the_half_range_brought_back_by_the_affine_scale[splitk_3x3x3]',
+    E + 'test_outputs_beyond_the_range_saturate_with_round_to_nearest_even[ks_1x1]',
+    E + 'test_subnormal_operands_and_outputs[big_tile_3x3]',
+    E + 'test_layout_conversion_is_torch_rounding_bit_for_bit',
+    'tests.test_gpu_model::test_persistent_kernel_cu_share_does_not_change_results',
+]
+
+
+def test_fp16_build_passes_the_kernel_suite(tmp_path):
+    xml = str(tmp_path / 'fp16_suite.xml')
+    env = dict(os.environ, DAT_H16='fp16', PYTHONPATH=REPO)
+    env.pop('DAT_LIB', None)
+    cmd = [sys.executable, '-m', 'pytest', '-m', 'gpu', '-q', '-p', 'no:cacheprovider', '--junitxml=' + xml] + CHILD_FILES
+    t0 = time.time()
+    try:
+        p = subprocess.run(cmd, cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1200)
+    except subprocess.TimeoutExpired as e:
+        out = (e.output or b'').decode(errors='replace')
+        pytest.fail('the fp16 child run did not finish in 1200 s:\n' + out[-4000:])
+    secs = time.time() - t0
+    out = p.stdout.decode(errors='replace')
+    assert os.path.exists(xml), 'the fp16 child wrote no report (exit %d):\n%s' % (p.returncode, out[-4000:])
+    passed, skipped, failed = [], [], []
+    for case in ET.parse(xml).getroot().iter('testcase'):
+        tid = case.get('classname') + '::' + case.get('name')
+        bad = [c for c in case if c.tag in ('failure', 'error')]
+        skip = [c for c in case if c.tag == 'skipped']
+        if bad:
+            failed.append('%s: %s' % (tid, (bad[0].get('message') or '')[:300]))
+        elif skip:
+            skipped.append((tid, skip[0].get('message') or ''))
+        else:
+            passed.append(tid)
+    print('fp16 child: %d passed, %d skipped, %d failed in %.0f s (exit %d)' % (len(passed), len(skipped), len(failed), secs, p.returncode))
+    assert not failed, 'fp16 build failures:\n' + '\n'.join(failed) + '\n' + out[-3000:]
+    assert p.returncode == 0, out[-4000:]
+    # (besides the bf16-only tests, only the one skip that does not depend on the build: the compiled reference op is absent in
+    # both processes alike when oracle/_ref was never built)
+    wrong_skips = [(t, m) for t, m in skipped if 'bf16 build only' not in m and 'oracle/_ref/libref_affine.so was never built' not in m]
+    assert not wrong_skips, 'skips in the fp16 build that are not bf16-only tests: %r' % wrong_skips[:10]
+    missing = [t for t in MUST_PASS if t not in set(passed)]
+    assert not missing, 'must-pass tests that did not pass in the fp16 build: %r' % missing

@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import numerics as nm
+
 pytestmark = pytest.mark.gpu
 
 
@@ -18,6 +20,18 @@ def ops():
 
 def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _bf16_only(ops):
+    """Tests of the bf16-only modes (bf16x3, split_bf16x2): the fp16 build refuses them."""
+    if ops.L.H16 == 'fp16':
+        pytest.skip('bf16 build only')
+
+
+def _bound(got, ref_args, cin, k, what, extra=0.0):
+    """The per-element bound (tests/numerics.py) of a conv output in the build's 16-bit format: ref_args = the conv_ref64 arguments."""
+    ref64, abs64 = nm.conv_ref64(*ref_args)
+    nm.assert_elementwise(got, ref64, abs64, nm.conv_k(cin, k), nm.h16(), what, extra)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -154,6 +168,10 @@ def test_layout_roundtrip(ops, dtype):
     assert np.all(got[..., 5:] == 0)
     back = ops.to_ncdhw(nd, dtype, 2, 5, 3).cpu().numpy()
     np.testing.assert_allclose(back, x, rtol=tol, atol=tol)
+    if dtype == 1:      # the conversion is torch's round to nearest even, bit for bit, and the way back is exact
+        assert nd.dtype == nm.h16()
+        np.testing.assert_array_equal(got[..., :5], nm.q16(ref))
+        np.testing.assert_array_equal(back, nm.q16(x))
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -203,6 +221,8 @@ def test_conv3d(ops, case, dtype):
     k-slice, fp32 accumulate) -- held to 5e-4 against the fp32 reference (fp32 MFMA mode: 2e-4; plain bf16: 3e-2)."""
     name, N, T, H, W, Cin, Cout, k, s, relu, res_mode, affine = case
     x3, dtype = dtype == 2, (0 if dtype == 2 else dtype)
+    if x3:
+        _bf16_only(ops)
     rs = np.random.RandomState(abs(hash(name)) % 1000)
     x = rs.randn(N, Cin, T, H, W).astype(np.float32)
     w = (rs.randn(Cout, Cin, *k) * np.sqrt(2.0 / (Cin * k[0] * k[1] * k[2]))).astype(np.float32)
@@ -218,8 +238,8 @@ def test_conv3d(ops, case, dtype):
     elif res_mode == 2:
         res_small = rs.randn(N, Cout, T, Ho // 2, Wo // 2).astype(np.float32)
         res = np.repeat(np.repeat(res_small, 2, axis=3), 2, axis=4)
-    if dtype == 1:  # bf16: quantise the operands the kernel will see, so only accumulation order differs
-        q = lambda a: torch.from_numpy(a).bfloat16().float().numpy()
+    if dtype == 1:  # 16-bit: quantise the operands the kernel will see, so only accumulation order differs
+        q = nm.q16
         x, w = q(x), q(w)
         if res is not None:
             res = q(res)
@@ -252,6 +272,15 @@ def test_conv3d(ops, case, dtype):
     tol = (5e-4 if x3 else 2e-4) if dtype == 0 else 3e-2 * max(1.0, np.abs(ref).max() / 4)
     print('conv %s dtype=%s max-abs err %.3e (ref max %.2f)' % (name, 'bf16x3' if x3 else dtype, err, np.abs(ref).max()))
     assert err < tol
+    if dtype == 1:
+        _bound(got, (x, w, scale, bias, res, s, pads, relu), Cin, k, 'conv ' + name)
+        try:                    # the same layer under a forced split-K plan (the split-K finish kernel writes the output)
+            assert ops.tune_plan(128, 2) == 0
+            y_sk = layer(xd, T=T, residual=rd, res_mode=res_mode)
+        finally:
+            ops.tune_plan(0, 0)
+        _bound(ops.to_ncdhw(y_sk, dtype, N, Cout, T).cpu().numpy(), (x, w, scale, bias, res, s, pads, relu), Cin, k,
+               'conv split-K ' + name)
 
 
 WS64_CASES = [
@@ -269,7 +298,7 @@ def test_conv3x3_c64_weights_stationary(ops, case):
     same bf16 operands, and bit for bit against the generic kernel (forced plan: same tap / k-slice accumulation order)."""
     name, frames, H, W, relu, with_res, affine = case
     rs = np.random.RandomState(len(name) * 7 + H)
-    q = lambda a: torch.from_numpy(a).bfloat16().float().numpy()
+    q = nm.q16
     x = q(rs.randn(1, 64, frames, H, W).astype(np.float32))
     w = q((rs.randn(64, 64, 1, 3, 3) * np.sqrt(2.0 / (64 * 9))).astype(np.float32))
     scale = rs.uniform(0.5, 1.5, 64).astype(np.float32) if affine else None
@@ -289,6 +318,7 @@ def test_conv3x3_c64_weights_stationary(ops, case):
     got = ops.to_ncdhw(y, 1, 1, 64, frames).cpu().numpy()
     err = np.abs(got - ref).max()
     assert err < 3e-2 * max(1.0, np.abs(ref).max() / 4), err
+    _bound(got, (x, w, scale, bias, res, (1, 1), (0, 1, 1), relu), 64, (1, 3, 3), 'ws64 ' + name)
 
 
 @pytest.mark.parametrize('dtype', [0, 1])
@@ -337,7 +367,7 @@ def test_conv1x1_k64_c256_weights_stationary(ops, case):
     """conv1x1_k64_c256_ws_kernel against torch on the same bf16 operands and bit for bit against the generic kernel (forced plan)."""
     name, T, H, W, relu, res_mode, affine = case
     rs = np.random.RandomState(len(name) * 5 + W)
-    q = lambda a: torch.from_numpy(a).bfloat16().float().numpy()
+    q = nm.q16
     x = q(rs.randn(1, 64, T, H, W).astype(np.float32))
     w = q((rs.randn(256, 64, 1, 1, 1) * np.sqrt(2.0 / 64)).astype(np.float32))
     scale = rs.uniform(0.5, 1.5, 256).astype(np.float32) if affine else None
@@ -361,6 +391,7 @@ def test_conv1x1_k64_c256_weights_stationary(ops, case):
     assert torch.equal(y, y_gen)
     got = ops.to_ncdhw(y, 1, 1, 256, T).cpu().numpy()
     assert np.abs(got - ref).max() < 3e-2 * max(1.0, np.abs(ref).max() / 4)
+    _bound(got, (x, w, scale, bias, res, (1, 1), (0, 0, 0), relu), 64, (1, 1, 1), 'pw256 ' + name)
 
 
 def _in_fresh_context(env, fn):
@@ -394,7 +425,7 @@ def test_conv3x3_linear_320_position_tiles(ops):
     """The opt-in 320-position linear tiles (DAT_CONV_LINEAR=5; a grid just above one block per CU: 100 maps of 14 x 14, 512 output
     channels = 308 blocks of 256 positions, 248 of 320) against torch and bit for bit against the 2-D tiling (DAT_CONV_LINEAR=0)."""
     rs = np.random.RandomState(5)
-    q = lambda a: torch.from_numpy(a).bfloat16().float().numpy()
+    q = nm.q16
     N, H, W, Cin, Cout = 100, 14, 14, 64, 512
     x = q(rs.randn(N, Cin, 1, H, W).astype(np.float32))
     w = q((rs.randn(Cout, Cin, 1, 3, 3) * np.sqrt(2.0 / (Cin * 9))).astype(np.float32))
@@ -409,6 +440,7 @@ def test_conv3x3_linear_320_position_tiles(ops):
     assert torch.equal(y320, y2d)
     got = ops.to_ncdhw(y320, 1, N, Cout, 1).cpu().numpy()
     assert np.abs(got - ref).max() < 3e-2 * max(1.0, np.abs(ref).max() / 4)
+    _bound(got, (x, w, None, bias, res, (1, 1), (0, 1, 1), True), Cin, (1, 3, 3), 'linear-320')
 
 
 @pytest.mark.parametrize('plan', [(256, 1), (256, 2), (128, 1), (128, 3)], ids=lambda p: 'bp%d_ks%d' % p)
@@ -420,7 +452,7 @@ def test_conv3x3x3_linear_strips_per_frame(ops, shape, plan):
     two clips (the clip / frame decode and the temporal zero padding at clip borders)."""
     N, T, H, W, Cin, Cout = shape
     rs = np.random.RandomState(H * W + Cin)
-    q = lambda a: torch.from_numpy(a).bfloat16().float().numpy()
+    q = nm.q16
     x = q(rs.randn(N, Cin, T, H, W).astype(np.float32))
     w = q((rs.randn(Cout, Cin, 3, 3, 3) * np.sqrt(2.0 / (Cin * 27))).astype(np.float32))
     scale = rs.uniform(0.5, 1.5, Cout).astype(np.float32)
@@ -441,6 +473,7 @@ def test_conv3x3x3_linear_strips_per_frame(ops, shape, plan):
     assert torch.equal(y_lin, y_2d)
     got = ops.to_ncdhw(y_lin, 1, N, Cout, T).cpu().numpy()
     assert np.abs(got - ref).max() < 3e-2 * max(1.0, np.abs(ref).max() / 4)
+    _bound(got, (x, w, scale, bias, res, (1, 1), (1, 1, 1), True), Cin, (3, 3, 3), 'strips %r %r' % (shape, plan))
 
 
 def test_conv3x3x3_linear_strips_with_key_frame_outputs(ops):
@@ -448,8 +481,8 @@ def test_conv3x3x3_linear_strips_with_key_frame_outputs(ops):
     the selected frames equal those of the full conv bit for bit, with the 2-D tiling as well."""
     N, T, H, W, Cin, Cout = 2, 4, 24, 42, 128, 256
     rs = np.random.RandomState(11)
-    x = torch.from_numpy(rs.randn(N, Cin, T, H, W).astype(np.float32))
-    w = torch.from_numpy((rs.randn(Cout, Cin, 3, 3, 3) * np.sqrt(2.0 / (Cin * 27))).astype(np.float32))
+    x = torch.from_numpy(nm.q16(rs.randn(N, Cin, T, H, W).astype(np.float32)))
+    w = torch.from_numpy(nm.q16((rs.randn(Cout, Cin, 3, 3, 3) * np.sqrt(2.0 / (Cin * 27))).astype(np.float32)))
     layer = ops.ConvLayer(_dev(w.numpy()), None, _dev(np.zeros(Cout, np.float32)), stride=(1, 1), pads=(1, 1, 1), relu=True, dtype=1)
     xd = ops.to_ndhwc(_dev(x.numpy()), 1)
     full = layer(xd, T=T)                                     # [N*T, H, W, C]
@@ -459,6 +492,9 @@ def test_conv3x3x3_linear_strips_with_key_frame_outputs(ops):
     assert torch.equal(key, full.view(N, T, H, W, -1)[:, t0])
     key2d = _in_fresh_context({'DAT_CONV_LINEAR': '0'}, lambda: layer(xd, T=T, out_t=(t0, 1)))
     assert torch.equal(key, key2d)
+    got = key.float().cpu()[..., :Cout].permute(0, 3, 1, 2).numpy()           # [N, Cout, H, W] of frame t0
+    ref64, abs64 = nm.conv_ref64(x, w, None, None, None, (1, 1), (1, 1, 1), True)
+    nm.assert_elementwise(got, ref64[:, :, t0], abs64[:, :, t0], nm.conv_k(Cin, (3, 3, 3)), nm.h16(), 'key-frame strips')
 
 
 BT_CASES = [
@@ -475,7 +511,7 @@ def test_conv3x3_big_tile(ops, case):
     and bit for bit against the generic kernel (forced plan; same patch / tap / k-slice accumulation order)."""
     name, T, H, W, Cin, Cout, kt, relu, res_mode, affine = case
     rs = np.random.RandomState(len(name) * 3 + W)
-    q = lambda a: torch.from_numpy(a).bfloat16().float().numpy()
+    q = nm.q16
     x = q(rs.randn(1, Cin, T, H, W).astype(np.float32))
     w = q((rs.randn(Cout, Cin, kt, 3, 3) * np.sqrt(2.0 / (Cin * 9 * kt))).astype(np.float32))
     scale = rs.uniform(0.5, 1.5, Cout).astype(np.float32) if affine else None
@@ -508,6 +544,7 @@ def test_conv3x3_big_tile(ops, case):
     assert err < 3e-2 * max(1.0, np.abs(ref).max() / 4), err
     # (the generic kernel and torch agree as well: the comparison above is not vacuous)
     assert np.abs(ops.to_ncdhw(y_gen, 1, 1, Cout, T).cpu().numpy() - ref).max() < 3e-2 * max(1.0, np.abs(ref).max() / 4)
+    _bound(got, (x, w, scale, bias, res, (1, 1), (kt // 2, 1, 1), relu), Cin, (kt, 3, 3), 'big-tile ' + name)
 
 
 @pytest.mark.parametrize('case', [('split_k_4_cout_blocks', 4, 24, 42, 512, 512, 3), ('two_cout_blocks', 3, 60, 84, 128, 256, 3), ('2d', 2, 48, 84, 256, 384, 1)],
@@ -517,7 +554,7 @@ def test_conv_block_order_switch_is_bit_identical(ops, case):
     only permutes which block computes which (tile, cout block, split): same bits as the default order, split-K included."""
     name, T, H, W, Cin, Cout, kt = case
     rs = np.random.RandomState(len(name) + W)
-    q = lambda a: torch.from_numpy(a).bfloat16().float().numpy()
+    q = nm.q16
     x = q(rs.randn(1, Cin, T, H, W).astype(np.float32))
     w = q((rs.randn(Cout, Cin, kt, 3, 3) * np.sqrt(2.0 / (Cin * 9 * kt))).astype(np.float32))
     bias = (rs.randn(Cout) * 0.1).astype(np.float32)
@@ -529,6 +566,8 @@ def test_conv_block_order_switch_is_bit_identical(ops, case):
     assert torch.equal(y0, y1)
     ref = _conv_ref(x, w, None, bias, None, (1, 1), (kt // 2, 1, 1), True)
     assert np.abs(ops.to_ncdhw(y1, 1, 1, Cout, T).cpu().numpy() - ref).max() < 3e-2 * max(1.0, np.abs(ref).max() / 4)
+    _bound(ops.to_ncdhw(y1, 1, 1, Cout, T).cpu().numpy(), (x, w, None, bias, None, (1, 1), (kt // 2, 1, 1), True), Cin, (kt, 3, 3),
+           'block order ' + name)
 
 
 PW_CASES = [
@@ -552,6 +591,8 @@ def test_conv3d_large_pointwise_layers(ops, case, dtype):
     from detectandtrack_amd import libdat as L
     name, T, H, W, Cin, Cout, relu, res_mode, affine = case
     x3, dtype = dtype == 2, (0 if dtype == 2 else dtype)       # (bf16x3: fp32 tensors, split-operand conv)
+    if x3:
+        _bf16_only(ops)
     rs = np.random.RandomState(abs(hash(name)) % 1000)
     x = rs.randn(1, Cin, T, H, W).astype(np.float32)
     w = (rs.randn(Cout, Cin, 1, 1, 1) * np.sqrt(2.0 / Cin)).astype(np.float32)
@@ -564,7 +605,7 @@ def test_conv3d_large_pointwise_layers(ops, case, dtype):
         res_small = rs.randn(1, Cout, T, H // 2, W // 2).astype(np.float32)
         res = np.repeat(np.repeat(res_small, 2, axis=3), 2, axis=4)
     if dtype == 1:
-        q = lambda a: torch.from_numpy(a).bfloat16().float().numpy()
+        q = nm.q16
         x, w = q(x), q(w)
         if res is not None:
             res = q(res)
@@ -590,6 +631,8 @@ def test_conv3d_large_pointwise_layers(ops, case, dtype):
                                                                                             np.abs(got - gen).max()))
     assert err < tol
     np.testing.assert_array_equal(got, gen)
+    if dtype == 1:
+        _bound(got, (x, w, scale, bias, res, (1, 1), (0, 0, 0), relu), Cin, (1, 1, 1), 'pointwise ' + name)
 
 
 def test_conv3d_forced_plans_agree(ops):
@@ -627,7 +670,7 @@ def test_stem_conv1(ops, dtype):
     s = rs.uniform(0.5, 1.5, 64).astype(np.float32)
     b = (rs.randn(64) * 0.1).astype(np.float32)
     if dtype == 1:
-        q = lambda a: torch.from_numpy(a).bfloat16().float().numpy()
+        q = nm.q16
         x, w = q(x), q(w)
     ref = _conv_ref(x, w, s, b, None, (2, 2), (0, 3, 3), True)
     layer = ops.stem_layer(_dev(w), _dev(s), _dev(b), dtype)
@@ -638,6 +681,8 @@ def test_stem_conv1(ops, dtype):
     print('stem dtype=%d err %.3e ref max %.1f' % (dtype, err, np.abs(ref).max()))
     assert got.shape == ref.shape
     assert err < (2e-3 if dtype == 0 else 0.02 * np.abs(ref).max())
+    if dtype == 1:
+        _bound(got, (x, w, s, b, None, (2, 2), (0, 3, 3), True), 3, (1, 7, 7), 'stem')
 
 
 @pytest.mark.parametrize('dtype', [0, 1])
@@ -645,7 +690,7 @@ def test_maxpool(ops, dtype):
     rs = np.random.RandomState(6)
     x = rs.randn(1, 64, 2, 13, 18).astype(np.float32)
     if dtype == 1:
-        x = torch.from_numpy(x).bfloat16().float().numpy()
+        x = nm.q16(x)
     ref = F.max_pool3d(torch.from_numpy(x), (1, 3, 3), (1, 2, 2), (0, 1, 1)).numpy()
     y = ops.maxpool_hw(ops.to_ndhwc(_dev(x), dtype), dtype, 3, 2, 1)
     np.testing.assert_array_equal(ops.to_ncdhw(y, dtype, 1, 64, 2).cpu().numpy(), ref)
@@ -686,7 +731,7 @@ def test_roi_align_single_level(ops, dtype):
     rs = np.random.RandomState(8)
     feat = rs.randn(2, 64, 1, 20, 30).astype(np.float32)
     if dtype == 1:
-        feat = torch.from_numpy(feat).bfloat16().float().numpy()
+        feat = nm.q16(feat)
     rois = _rand_rois(rs, 23, 30 * 16, 20 * 16, batch=2)
     ref = roi_align_2d(feat[:, :, 0], rois, 7, 1. / 16., 2)
     fd = ops.to_ndhwc(_dev(feat), dtype)
@@ -695,6 +740,10 @@ def test_roi_align_single_level(ops, dtype):
     err = np.abs(got - ref).max()
     print('roi_align dtype=%d err %.3e' % (dtype, err))
     assert err < (1e-4 if dtype == 0 else 3e-2)
+    if dtype == 1:
+        # K = 2 x 2 samples of 4 bilinear taps; the output is stored in the feature's format
+        absref = roi_align_2d(np.abs(feat[:, :, 0]), rois, 7, 1. / 16., 2)
+        nm.assert_elementwise(got, ref, absref, 16, out.dtype, 'roi_align single level')
 
 
 def test_roi_align_tube_and_keyframe(ops):
@@ -1071,7 +1120,7 @@ def test_kps_tail(ops, dtype):
     w = (rs.randn(Cin, K, 4, 4) * 0.05).astype(np.float32)
     b = (rs.randn(K) * 0.1).astype(np.float32)
     if dtype == 1:
-        q = lambda a: torch.from_numpy(a).bfloat16().float().numpy()
+        q = nm.q16
         x, w = q(x), q(w)
     net = Net({'kps_score_lowres_w': w, 'kps_score_lowres_b': b}, opts_for('R18'))
     ref = net.kps_outputs_2d(torch.from_numpy(x)).numpy()
@@ -1083,6 +1132,18 @@ def test_kps_tail(ops, dtype):
     err = np.abs(out - ref).max()
     print('kps tail dtype=%d err %.3e' % (dtype, err))
     assert err < (1e-4 if dtype == 0 else 3e-2)
+    if dtype == 1:
+        from oracle.net3d import bilinear_kernel
+        up = torch.from_numpy(np.ascontiguousarray(bilinear_kernel(K, 2), np.float64))
+        t64 = lambda a: torch.from_numpy(a.astype(np.float64))
+        low = F.conv_transpose2d(t64(x), t64(w), t64(b), stride=2, padding=1)
+        abs_low = F.conv_transpose2d(t64(np.abs(x)), t64(np.abs(w)), t64(np.abs(b)), stride=2, padding=1)
+        ref64 = F.conv_transpose2d(low, up, None, stride=2, padding=1).numpy()
+        abs64 = F.conv_transpose2d(abs_low, up, None, stride=2, padding=1).numpy()
+        # the sub-pixel conv stores kps_score_lowres in the 16-bit format and dat_kps_finalize (elementwise.hip kps_finalize_kernel)
+        # upsamples that stored blob in fp32: a second rounding, at most u16 * |lowres| under the (non-negative) bilinear taps
+        extra = nm.unit_roundoff(nm.h16()) * F.conv_transpose2d(low.abs(), up, None, stride=2, padding=1).numpy()
+        nm.assert_elementwise(out, ref64, abs64, Cin * 16 + 4, 'fp32', 'kps tail', extra)
 
 
 def _roi_align_cases():
@@ -1170,7 +1231,7 @@ def test_fused_stem_conv_matches_torch(ops, dtype_name):
         w = torch.randn((64, 3, 1, 7, 7), generator=g) * 0.05
         scale, bias = torch.rand(64, generator=g) + 0.5, torch.randn(64, generator=g)
         if dtype_name == 'bf16':
-            data_r, w_r = data.to(torch.bfloat16).float(), w.to(torch.bfloat16).float()
+            data_r, w_r = nm.q16(data), nm.q16(w)
         else:
             data_r, w_r = data, w
         ref = F.relu(F.conv3d(data_r, w_r, None, stride=(1, 2, 2), padding=(0, 3, 3)) * scale.view(1, -1, 1, 1, 1) + bias.view(1, -1, 1, 1, 1))
@@ -1181,6 +1242,8 @@ def test_fused_stem_conv_matches_torch(ops, dtype_name):
         err = (got - ref).abs().max().item()
         tol = 2e-3 if dtype_name == 'fp32' else 0.02 * ref.abs().max().item()
         assert err < tol, (N, T, H, W, err, tol)
+        if dtype_name == 'bf16':
+            _bound(got, (data_r, w_r, scale, bias, None, (2, 2), (0, 3, 3), True), 3, (1, 7, 7), 'fused stem %r' % ((N, T, H, W),))
 
 
 @pytest.mark.parametrize('dtype_name', ['fp32', 'bf16'])
@@ -1196,7 +1259,7 @@ def test_conv_one_pixel_wide_tiles(ops, dtype_name):
         x = torch.randn((1, cin, 2, H, W), generator=g)
         w = torch.randn((cout, cin) + k, generator=g) * (1.0 / (cin * k[1])) ** 0.5
         if dtype_name == 'bf16':
-            x, w = x.to(torch.bfloat16).float(), w.to(torch.bfloat16).float()
+            x, w = nm.q16(x), nm.q16(w)
         ref = F.conv3d(x, w, None)
         lay = ops.ConvLayer(w.cuda(), None, None, stride=(1, 1), pads=(0, 0, 0), relu=False, dtype=dt)
         xd = x.permute(0, 2, 3, 4, 1).reshape(2, H, W, cin).to(tdt).cuda().contiguous()
@@ -1204,14 +1267,18 @@ def test_conv_one_pixel_wide_tiles(ops, dtype_name):
         got = y.view(1, 2, ref.shape[3], ref.shape[4], -1)[..., :cout].permute(0, 4, 1, 2, 3)
         err = (got - ref).abs().max().item()
         assert err < (1e-3 if dtype_name == 'fp32' else 0.03 * ref.abs().max().item()), (cin, cout, k, H, W, err)
+        if dtype_name == 'bf16':
+            _bound(got, (x, w, None, None, None, (1, 1), (0, 0, 0), False), cin, k, 'one-pixel tiles %r' % ((cin, cout, k, H, W),))
     # the packed-stem formulation at a height that selects 128 x 1 tiles
     data = torch.rand((1, 3, 1, 256, 96), generator=g) * 255 - 110
     w7 = torch.randn((64, 3, 1, 7, 7), generator=g) * 0.025
-    ref = F.relu(F.conv3d(data.to(torch.bfloat16).float() if dtype_name == 'bf16' else data,
-                          w7.to(torch.bfloat16).float() if dtype_name == 'bf16' else w7, None, stride=(1, 2, 2), padding=(0, 3, 3)))
+    ref = F.relu(F.conv3d(nm.q16(data) if dtype_name == 'bf16' else data,
+                          nm.q16(w7) if dtype_name == 'bf16' else w7, None, stride=(1, 2, 2), padding=(0, 3, 3)))
     old = ops.stem_layer(w7.cuda(), torch.ones(64).cuda(), torch.zeros(64).cuda(), dt)
     y = old(ops.stem_pack(data.cuda(), dt), T=1).float().cpu().view(1, 1, 128, 48, 64).permute(0, 4, 1, 2, 3)
     assert (y - ref).abs().max().item() < (1e-2 if dtype_name == 'fp32' else 0.02 * ref.abs().max().item())
+    if dtype_name == 'bf16':
+        _bound(y, (nm.q16(data), nm.q16(w7), None, None, None, (2, 2), (0, 3, 3), True), 3, (1, 7, 7), 'one-pixel tiles: packed stem')
 
 
 @pytest.mark.parametrize('clips', [1, 4])
@@ -1236,15 +1303,17 @@ def test_full_size_layers_spot_checked(ops, clips):
     for (name, cin, cout, k, st, hi, wi, F_, T) in cases:
         pads = (k[0] // 2, k[1] // 2, k[2] // 2) if name != 'stem_k4x1' else (0, 0, 0)
         w = torch.randn((cout, cin) + tuple(k), device='cuda', generator=g) * (2.0 / (cin * k[0] * k[1] * k[2])) ** 0.5
-        w = w.to(torch.bfloat16).float()
+        w = nm.q16(w)
         bias = torch.randn(cout, device='cuda', generator=g)
         layer = ops.ConvLayer(w, None, bias, stride=(st, st), pads=pads, relu=False, dtype=ops.BF16)
-        x = torch.randn((F_, hi, wi, layer.cin), device='cuda', generator=g).to(torch.bfloat16)
+        x = torch.randn((F_, hi, wi, layer.cin), device='cuda', generator=g).to(nm.h16())
         y = layer(x, T=T).float()
         ho, wo = layer.out_hw(hi, wi)
         assert y.shape[0] == F_
         xf = x.float()
+        w64, x64 = w.double(), x.double()
         worst = 0.0
+        got_s, ref_s, abs_s = [], [], []
         idx = torch.randint(0, F_ * ho * wo, (48 if clips == 1 else 24,), device='cuda', generator=g).tolist()
         for c_ in range(F_ // T if T > 1 else min(F_, 4)):     # corners + a random interior position of the first and the last frame of every clip
             for f in ((c_ * T, c_ * T + T - 1) if T > 1 else (c_, F_ - 1 - c_)):
@@ -1256,6 +1325,7 @@ def test_full_size_layers_spot_checked(ops, clips):
             oh, ow = divmod(r, wo)
             lo = (f // T) * T               # temporal taps stay inside the frame's own clip
             acc = bias.clone()
+            acc64, abs64 = bias.double(), bias.double().abs()
             for kt in range(k[0]):
                 ft = f + kt - pads[0]
                 if ft < lo or ft >= lo + T:
@@ -1269,8 +1339,15 @@ def test_full_size_layers_spot_checked(ops, clips):
                         if iw < 0 or iw >= wi:
                             continue
                         acc += w[:, :, kt, kh, kw] @ xf[ft, ih, iw, :cin]
+                        acc64 += w64[:, :, kt, kh, kw] @ x64[ft, ih, iw, :cin]
+                        abs64 += w64[:, :, kt, kh, kw].abs() @ x64[ft, ih, iw, :cin].abs()
             worst = max(worst, (y[f, oh, ow, :cout] - acc).abs().max().item() / max(1.0, acc.abs().max().item()))
+            got_s.append(y[f, oh, ow, :cout])
+            ref_s.append(acc64)
+            abs_s.append(abs64)
         assert worst < 0.02, (name, clips, worst)
+        nm.assert_elementwise(torch.stack(got_s), torch.stack(ref_s), torch.stack(abs_s), nm.conv_k(cin, k), nm.h16(),
+                              'full size %s clips=%d' % (name, clips))
 
 
 def test_rpn_proposals_at_bench_size_vs_oracle(ops):
@@ -1312,11 +1389,14 @@ def test_fused_stem_and_maxpool_at_bench_size(ops):
     data = torch.rand((1, 3, 8, 768, 1344), generator=g) * 255 - 110
     w = torch.randn((64, 3, 1, 7, 7), generator=g) * 0.025
     scale, bias = torch.rand(64, generator=g) + 0.5, torch.randn(64, generator=g)
-    ref = F.relu(F.conv3d(data.to(torch.bfloat16).float(), w.to(torch.bfloat16).float(), None, stride=(1, 2, 2), padding=(0, 3, 3)) *
+    ref = F.relu(F.conv3d(nm.q16(data), nm.q16(w), None, stride=(1, 2, 2), padding=(0, 3, 3)) *
                  scale.view(1, -1, 1, 1, 1) + bias.view(1, -1, 1, 1, 1))
     y = ops.StemConv(w.cuda(), scale.cuda(), bias.cuda(), ops.BF16, relu=True)(data.cuda())
     got = y.float().cpu().view(1, 8, 384, 672, 64).permute(0, 4, 1, 2, 3)
     assert (got - ref).abs().max().item() < 0.02 * ref.abs().max().item()
+    # (the frames as a batch of one-frame clips: the same conv, a smaller im2col for the float64 reference)
+    _bound(got.permute(2, 1, 0, 3, 4), (nm.q16(data).permute(2, 1, 0, 3, 4), nm.q16(w), scale, bias, None, (2, 2), (0, 3, 3), True), 3,
+           (1, 7, 7), 'stem at bench size')
     pool = ops.maxpool_hw(y, ops.BF16, 3, 2, 1).float().cpu().view(1, 8, 192, 336, 64).permute(0, 4, 1, 2, 3)
     ref_pool = F.max_pool3d(got, kernel_size=(1, 3, 3), stride=(1, 2, 2), padding=(0, 1, 1))
     assert (pool - ref_pool).abs().max().item() == 0.0
@@ -1482,7 +1562,7 @@ def test_conv1x1_weights_in_lds_kernel(ops, case):
     channel passes, two cout parts, stride 2, both residual modes, Cout padding, ragged tiles."""
     name, T, H, W, Cin, Cout, stride, relu, res_mode, affine = case
     rs = np.random.RandomState(abs(hash(name)) % 1000)
-    q = lambda a: torch.from_numpy(a).bfloat16().float().numpy()
+    q = nm.q16
     x = q(rs.randn(1, Cin, T, H, W).astype(np.float32))
     w = q((rs.randn(Cout, Cin, 1, 1, 1) * np.sqrt(2.0 / Cin)).astype(np.float32))
     scale = rs.uniform(0.5, 1.5, Cout).astype(np.float32) if affine else None
@@ -1518,6 +1598,7 @@ def test_conv1x1_weights_in_lds_kernel(ops, case):
     err = np.abs(got - ref).max()
     print('lw %s max-abs err %.3e (ref max %.2f)' % (name, err, np.abs(ref).max()))
     assert err < 3e-2 * max(1.0, np.abs(ref).max() / 4)
+    _bound(got, (x, w, scale, bias, res, (stride, stride), (0, 0, 0), relu), Cin, (1, 1, 1), 'lw ' + name)
     if layer.cstride > Cout:          # the padding channels of the blob stay zero
         assert not y[..., Cout:].any()
 
@@ -1542,7 +1623,7 @@ def test_conv1x1_k_streaming_kernel(ops, case):
     a ragged last tile."""
     name, T, H, W, Cin, Cout, stride, relu, res_mode, affine = case
     rs = np.random.RandomState(abs(hash(name)) % 1000)
-    q = lambda a: torch.from_numpy(a).bfloat16().float().numpy()
+    q = nm.q16
     x = q(rs.randn(1, Cin, T, H, W).astype(np.float32))
     w = q((rs.randn(Cout, Cin, 1, 1, 1) * np.sqrt(2.0 / Cin)).astype(np.float32))
     scale = rs.uniform(0.5, 1.5, Cout).astype(np.float32) if affine else None
@@ -1583,6 +1664,8 @@ def test_conv1x1_k_streaming_kernel(ops, case):
     err = np.abs(got - ref).max()
     print('ks %s max-abs err %.3e (ref max %.2f), %.1f us' % (name, err, np.abs(ref).max(), 1e3 * rec[0][2]))
     assert err < 3e-2 * max(1.0, np.abs(ref).max() / 4)
+    _bound(got, (x, w, scale, bias, None if res_mode == 3 else res, (stride, stride), (0, 0, 0), relu, res if res_mode == 3 else None),
+           Cin, (1, 1, 1), 'ks ' + name)
     if layer.cstride > Cout:          # the padding channels of the blob stay zero
         assert not y[..., Cout:].any()
 

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import numerics as nm
 from tests.model_util import fpn3d_kps_cfg, build_product, synthetic_clip, oracle_opts
 
 pytestmark = pytest.mark.gpu
@@ -743,8 +744,8 @@ def test_persistent_kernel_cu_share_does_not_change_results():
     for cin, cout, k, pads, with_res in cases:
         w = (torch.randn((cout, cin) + k, generator=g) * (2.0 / (cin * k[1] * k[2])) ** 0.5).cuda()
         layer = ops.ConvLayer(w, None, torch.zeros(cout).cuda(), stride=(1, 1), pads=pads, relu=True, dtype=ops.BF16)
-        x = torch.randn((T, H, W, cin), generator=g).bfloat16().cuda()
-        res = torch.randn((T, H, W, cout), generator=g).bfloat16().cuda() if with_res else None
+        x = torch.randn((T, H, W, cin), generator=g).to(nm.h16()).cuda()
+        res = torch.randn((T, H, W, cout), generator=g).to(nm.h16()).cuda() if with_res else None
         outs = []
         try:
             for pct in (100, 50, 13):
@@ -753,5 +754,10 @@ def test_persistent_kernel_cu_share_does_not_change_results():
         finally:
             ops.persistent_share(100)
         assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2]), (cin, cout, k)
+        # and what they all compute is the conv: per-element bound against float64 on the CPU (tests/numerics.py)
+        nc = lambda t, c: t.float().cpu()[..., :c].permute(3, 0, 1, 2).unsqueeze(0)          # [T, H, W, cs] -> (1, c, T, H, W)
+        ref64, abs64 = nm.conv_ref64(nc(x, cin), nm.q16(w.cpu()), None, torch.zeros(cout), None if res is None else nc(res, cout),
+                                     (1, 1), pads, True)
+        nm.assert_elementwise(nc(outs[0], cout), ref64, abs64, nm.conv_k(cin, k), nm.h16(), 'cu share %r' % ((cin, cout, k),))
     with pytest.raises(Exception):
         ops.persistent_share(0)

@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import numerics as nm
+
 pytestmark = pytest.mark.gpu
 
 
@@ -52,7 +54,7 @@ def test_conv_backward_matches_autograd(ops, case, dtype_name):
     w = torch.randn((cout, cin) + k, generator=g) * (2.0 / (cin * k[0] * k[1] * k[2])) ** 0.5
     scale = torch.rand(cout, generator=g) + 0.5
     if dtype_name == 'bf16':   # the reference sees the same rounded operands
-        x = x.to(torch.bfloat16).float()
+        x = nm.q16(x)
     xr = x.clone().requires_grad_(True)
     wr = w.clone().requires_grad_(True)
     sr = scale.clone().requires_grad_(True)
@@ -60,7 +62,7 @@ def test_conv_backward_matches_autograd(ops, case, dtype_name):
     y = z * sr.view(1, -1, 1, 1, 1)
     gy = torch.randn(y.shape, generator=g)
     if dtype_name == 'bf16':
-        gy = gy.to(torch.bfloat16).float()
+        gy = nm.q16(gy)
     y.backward(gy)
 
     cs_x, cs_g = ops.round_up(cin, 64), ops.round_up(cout, 64)
@@ -78,6 +80,18 @@ def test_conv_backward_matches_autograd(ops, case, dtype_name):
     got = _from_ndhwc(dx, N, cin, T)
     err = (got - xr.grad).abs().max() / max(xr.grad.abs().max(), 1e-6)
     assert err < (2e-4 if dtype_name == 'fp32' else 3e-2), 'dx rel err %.3e' % err
+    if dtype_name == 'bf16':
+        # per-element bounds against float64 (tests/numerics.py): dW is stored in fp32 after a reduction over every output position
+        x64, w64, s64, gy64 = x.double(), w.double(), scale.double().view(1, -1, 1, 1, 1), gy.double()
+        st3 = (1, st, st)
+        wgrad = lambda a, b: torch.nn.grad.conv3d_weight(a, w.shape, b, stride=st3, padding=pads)
+        nm.assert_elementwise(dW.cpu(), wgrad(x64, gy64 * s64), wgrad(x64.abs(), (gy64 * s64).abs()), gy.numel() // cout, 'fp32', 'dW')
+        # dx is stored in 16 bits, from weights that dat_conv3d_pack_weights_dgrad packs with the scale folded in (conv_pack.hip
+        # pack_tile: w * scale, then ONE rounding to 16 bits): a second rounding, at most u16 * |w * scale| per weight
+        dgrad = lambda a, b: torch.nn.grad.conv3d_input(x.shape, a, b, stride=st3, padding=pads)
+        abs_dx = dgrad(w64.abs(), (gy64 * s64).abs())
+        nm.assert_elementwise(got, dgrad(w64, gy64 * s64), abs_dx, nm.conv_k(cout, k), nm.h16(), 'dx',
+                              extra=nm.unit_roundoff(nm.h16()) * abs_dx)
     # accumulate into an existing gradient (a blob with two consumers)
     base = torch.randn(dx.shape, generator=g).to(tdt).cuda()
     base[..., cin:] = 0
@@ -728,14 +742,14 @@ def test_direct_weight_gradient_over_a_frame_window(ops, k, win):
     cin, cout, T, H, W = 128, 192, 4, 17, 22
     pads = (k[0] // 2, k[1] // 2, k[2] // 2)
     g = torch.Generator().manual_seed(11)
-    x = torch.randn((1, cin, T, H, W), generator=g).bfloat16().float()
+    x = torch.randn((1, cin, T, H, W), generator=g).to(nm.h16()).float()
     w = torch.randn((cout, cin) + k, generator=g) * 0.05
     gy = torch.zeros((1, cout, T, H, W))
     t0, n = win
-    gy[:, :, t0:t0 + n] = torch.randn((1, cout, n, H, W), generator=g).bfloat16().float()
+    gy[:, :, t0:t0 + n] = torch.randn((1, cout, n, H, W), generator=g).to(nm.h16()).float()
     wr = w.clone().requires_grad_(True)
     F.conv3d(x, wr, None, stride=1, padding=pads).backward(gy)
-    xd, gd = _ndhwc(x, cin, torch.bfloat16), _ndhwc(gy, cout, torch.bfloat16)
+    xd, gd = _ndhwc(x, cin, nm.h16()), _ndhwc(gy, cout, nm.h16())
     cg = ops.ConvGrad(w.cuda(), None, (1, 1), pads, ops.BF16, cin, cout)
     full, _ = cg.weight(xd, gd, T)
     part, _ = cg.weight(xd, gd, T, g_frames=(t0, n))
@@ -927,15 +941,15 @@ def test_nine_tap_weight_gradient_variants_agree(ops, monkeypatch, cin, cout, T,
     (odd chunk counts), channel counts that are not multiples of 64, a forced two-range split (ks = 2: plain stores, no atomics) and a
     larger forced split: the same gradient to the fp32 summation order, and torch autograd."""
     g = torch.Generator().manual_seed(cin + cout)
-    x = torch.randn((1, cin, T, H, W), generator=g).bfloat16().float()
+    x = torch.randn((1, cin, T, H, W), generator=g).to(nm.h16()).float()
     w = torch.randn((cout, cin, 3, 3, 3), generator=g) * 0.05
-    gy = torch.randn((1, cout, T, H, W), generator=g).bfloat16().float()
+    gy = torch.randn((1, cout, T, H, W), generator=g).to(nm.h16()).float()
     wr = w.clone().requires_grad_(True)
     F.conv3d(x, wr, None, stride=1, padding=1).backward(gy)
     ref = wr.grad
     mx = float(ref.abs().max())
     cs_x, cs_g = ops.round_up(cin, 64), ops.round_up(cout, 64)
-    xd, gd = _ndhwc(x, cs_x, torch.bfloat16), _ndhwc(gy, cs_g, torch.bfloat16)
+    xd, gd = _ndhwc(x, cs_x, nm.h16()), _ndhwc(gy, cs_g, nm.h16())
     outs = {}
     for name, env in (('sub2 ilv1', {}), ('sub1', {'DAT_WGRAD_SUB': '1'}), ('ilv0', {'DAT_WGRAD_ILV': '0'}), ('sub2 ks2', {'DAT_WGRAD_KS': '2'}),
                       ('sub2 ks6', {'DAT_WGRAD_KS': '6'}), ('sub1 ks5', {'DAT_WGRAD_SUB': '1', 'DAT_WGRAD_KS': '5'})):
@@ -1006,11 +1020,11 @@ def test_pointwise_weight_gradient_kernel(ops, monkeypatch, case, acc):
     summation order.  Reference semantics: the ConvGradient of every ConvNd, lib/modeling/model_builder.py:908-951."""
     cin, cout, st, N, T, H, W, win = case
     g = torch.Generator().manual_seed(cin + 3 * cout)
-    x = torch.randn((N, cin, T, H, W), generator=g).bfloat16().float()
+    x = torch.randn((N, cin, T, H, W), generator=g).to(nm.h16()).float()
     w = torch.randn((cout, cin, 1, 1, 1), generator=g) * 0.05
     scale = torch.rand(cout, generator=g) + 0.5
     Ho, Wo = (H - 1) // st + 1, (W - 1) // st + 1
-    gy = torch.randn((N, cout, T, Ho, Wo), generator=g).bfloat16().float()
+    gy = torch.randn((N, cout, T, Ho, Wo), generator=g).to(nm.h16()).float()
     if win is not None:
         t0, n = win
         keep = torch.zeros_like(gy)
@@ -1021,7 +1035,7 @@ def test_pointwise_weight_gradient_kernel(ops, monkeypatch, case, acc):
     ref = wr.grad
     mx = float(ref.abs().max())
     cs_x, cs_g = ops.round_up(cin, 64), ops.round_up(cout, 64)
-    xd, gd = _ndhwc(x, cs_x, torch.bfloat16), _ndhwc(gy, cs_g, torch.bfloat16)
+    xd, gd = _ndhwc(x, cs_x, nm.h16()), _ndhwc(gy, cs_g, nm.h16())
 
     def run():
         ops.drop_ctx()                                  # a context made under the current environment
@@ -1056,15 +1070,15 @@ def test_pointwise_weight_gradient_batch_equals_the_single_launches(ops):
         ker = (3, 3, 3) if k == len(PW_CASES) else (1, 1, 1)
         pads = tuple(v // 2 for v in ker)
         g = torch.Generator().manual_seed(100 + k)
-        x = torch.randn((N, cin, T, H, W), generator=g).bfloat16().float()
+        x = torch.randn((N, cin, T, H, W), generator=g).to(nm.h16()).float()
         Ho, Wo = (H + 2 * pads[1] - ker[1]) // st + 1, (W + 2 * pads[2] - ker[2]) // st + 1
-        gy = torch.randn((N, cout, T, Ho, Wo), generator=g).bfloat16().float()
+        gy = torch.randn((N, cout, T, Ho, Wo), generator=g).to(nm.h16()).float()
         if win is not None:
             keep_ = torch.zeros_like(gy)
             keep_[:, :, win[0]:win[0] + win[1]] = gy[:, :, win[0]:win[0] + win[1]]
             gy = keep_
         cs_x, cs_g = ops.round_up(cin, 64), ops.round_up(cout, 64)
-        xd, gd = _ndhwc(x, cs_x, torch.bfloat16), _ndhwc(gy, cs_g, torch.bfloat16)
+        xd, gd = _ndhwc(x, cs_x, nm.h16()), _ndhwc(gy, cs_g, nm.h16())
         w = torch.zeros((cout, cin) + ker, device='cuda')
         cg = ops.ConvGrad(w, None, (st, st), pads, ops.BF16, cs_x, cs_g)
         assert cg.pointwise == (ker == (1, 1, 1))

@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import numerics as nm
+
 pytestmark = pytest.mark.gpu
 
 FROZEN = ('conv1', 'res_conv1', 'res2_')
@@ -157,7 +159,7 @@ def test_r50_bottleneck_wgrad_and_dgrad_at_the_bench_map_sizes(layer, dtype_name
     Ho, Wo = (H + 2 * pads[1] - k[1]) // stride + 1, (W + 2 * pads[2] - k[2]) // stride + 1
     dy5 = torch.randn((1, cout, T, Ho, Wo), generator=g)
     if dtype_name == 'bf16':
-        x5, dy5 = x5.bfloat16().float(), dy5.bfloat16().float()
+        x5, dy5 = nm.q16(x5), nm.q16(dy5)
     cs_in, cs_out = ops.round_up(cin, 64), ops.round_up(cout, 64)
 
     def ndhwc(v, cs):
