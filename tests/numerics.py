@@ -109,3 +109,27 @@ def conv_ref64(x, w, scale=None, bias=None, res=None, stride=(1, 1), pads=(0, 0,
 def conv_k(cin, k):
     """The reduction length of a conv: input channels times taps."""
     return int(cin) * int(np.prod(k))
+
+
+def sum_bound(abssum64, n, extra=0.0):
+    """Bound on the error of a scalar that a kernel sums from `n` fp32 terms (per-thread partial sums, an LDS tree per block, then
+    float atomics across blocks), against the float64 sum of the same terms:
+
+        |got - ref| <= C * sqrt(n) * 2^-24 * sum_i |term_i|  +  extra  (+ the smallest fp32 half-ulp)
+
+    Every addition of a partial sum s rounds once, with error at most 2^-24 * |s| <= 2^-24 * sum_i |term_i|; a sum of n terms in any
+    order holds at most n - 1 such roundings, and round-to-nearest errors of independent sign grow like their square root -- the
+    C * sqrt(K) term of `bound` with K = n.  The few fp32 roundings of each term's own arithmetic (products, the final multiply by
+    the normaliser) stay below C * 2^-24 * |term_i| and are covered by the same term.  A libm call inside a term (expf, log1pf,
+    logf: a few ulps of its result, amplified by the argument's rounding) is not: the caller names it in `extra`.  A sum with one
+    term missing misses it by |term| and a sum accumulated in bf16 drifts by ~2^-9 per addition -- both far outside the bound at the
+    sizes of the suite (tests/test_train_refs_cpu.py)."""
+    return C * np.sqrt(float(max(n, 1))) * 2.0 ** -24 * float(abssum64) + float(extra) + _TINY[torch.float32]
+
+
+def assert_sum(got, ref64, abssum64, n, what, extra=0.0):
+    """`got` (a float) within `sum_bound` of the float64 sum `ref64`."""
+    b = sum_bound(abssum64, n, extra)
+    err = abs(float(got) - float(ref64))
+    assert err <= b, '%s: got %.9g, ref %.9g, |err| %.3g > bound %.3g (n=%d, sum|term| %.6g)' % (what, float(got), float(ref64), err, b,
+                                                                                               n, float(abssum64))
