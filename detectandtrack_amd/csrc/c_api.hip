@@ -51,23 +51,15 @@ int dat_ctx_create(dat_ctx** out, int device) {
         auto env_int = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
         c->force_bp = env_int("DAT_CONV_BP", 0);
         c->force_ks = env_int("DAT_CONV_KSPLIT", 0);
-        c->dbg_tw_log2 = env_int("DAT_CONV_TW_LOG2", -1);
         c->dbg_ablate = env_int("DAT_CONV_ABLATE", 0);
-        c->dbg_lds_pad = env_int("DAT_CONV_LDS_PAD", 0);
-        c->dbg_tps3 = env_int("DAT_CONV_TPS", 3) == 3;
-        c->dbg_wd = env_int("DAT_CONV_WD", 2);       // 0 off, 1 the 128-channel tiles only, 2 (default) also the 64-channel ones
         c->dbg_ntap = env_int("DAT_CONV_NTAP", 1);   // 0 off, 1 default rule; bit 1 (2/3): unrolled 1x1 variant for every 1x1 layer; bit 2 (5): no dense stride-2 patches
-        c->dbg_pack_simple = env_int("DAT_PACK_SIMPLE", 0) != 0;
         c->dbg_ws64 = env_int("DAT_CONV_WS64", 1);
         c->dbg_pwlw = env_int("DAT_CONV_PWLW", 1);
         c->dbg_pwks = env_int("DAT_CONV_PWKS", 8);
         c->dbg_wgrad_direct = env_int("DAT_WGRAD_DIRECT", 1);
         c->dbg_wgrad_ks = env_int("DAT_WGRAD_KS", 0);
-        c->dbg_wgrad_dma = env_int("DAT_WGRAD_DMA", 1);
         c->dbg_ablate_wgrad = env_int("DAT_WGRAD_ABLATE", 0);
         c->dbg_wgrad_sub = env_int("DAT_WGRAD_SUB", 2);
-        c->dbg_wgrad_ilv = env_int("DAT_WGRAD_ILV", 1);
-        c->dbg_wgrad_xcd = env_int("DAT_WGRAD_XCD", 0);
         c->dbg_pw_xcd = env_int("DAT_CONV_PW_XCD", 1);
         c->dbg_wgrad_pw = env_int("DAT_WGRAD_PW", 1);
         c->dbg_kps_sep = env_int("DAT_KPS_DECODE_SEP", 1);

@@ -13,13 +13,12 @@
 //     one 128-byte line = 64 bf16 / 32 fp32 channels of one input position;
 //   * the block stages an INPUT PATCH (output tile + halo) in LDS once per (kt, channel chunk) and reuses it
 //     for all KH*KW spatial taps — the im2col matrix never exists, and global->LDS traffic for activations
-//     drops by ~KH*KW versus a tap-by-tap implicit GEMM; only the weight tile streams per tap
-//     (double-buffered, prefetched into registers one tap ahead);
-//   * MFMA operands: A = weights (rows = output channels), B = activations (cols = output positions), both
-//     read from LDS as one ds_read_b128 per lane per k-slice with an XOR swizzle ((row>>1)&7) that makes
-//     the 16-lane read groups conflict-free for consecutive rows;
+//     drops by ~KH*KW versus a tap-by-tap implicit GEMM;
+//   * MFMA operands: A = weights (rows = output channels) straight from global memory into registers,
+//     B = activations (cols = output positions) from the LDS patch, one ds_read_b128 per lane per k-slice
+//     with an XOR swizzle ((row>>1)&7) that makes the 16-lane read groups conflict-free for consecutive rows;
 //   * bf16: v_mfma_f32_32x32x16_bf16 (fp32 accumulate); fp32 parity mode: v_mfma_f32_32x32x2_f32 (exact
-//     fp32 fma chain) consuming the same 16-byte LDS reads as 4 k-steps;
+//     fp32 fma chain) consuming the same 16-byte operands as 4 k-steps;
 //   * D layout (col = lane&31 = position, rows = 4 consecutive channels per register quad) gives 8/16-byte
 //     channel-contiguous NDHWC stores in the epilogue;
 //   * blockIdx -> tile mapping is XCD-aware: output-channel blocks of one spatial tile and neighbouring
@@ -31,27 +30,23 @@ using namespace dat_conv;
 namespace {
 
 // BN = output channels per block, BP = output positions per block, WAVES_N x WAVES_P = 4 waves.
-// TPS = spatial taps per step: a step costs ~1 us of fixed work (barrier, weight-DMA issue, table look-ups, LDS read
-// latency) whatever the tile, so thin layers (64 -> 64 channels: 8 MFMAs per wave and tap) run 3 taps per step from a
-// 3 x 8 KB weight stage; wide tiles keep 1 tap per step (their weight stages would not leave room for 2 blocks per CU).
 //
-// WD = 1 ("weights direct", the BN = 128 variants): the weight operand never touches LDS.  The packed weights are stored in
-// MFMA A-fragment order -- per (tap, 64-channel chunk, 32-row block) one 4-KiB image [k-slice][lane][16 B] -- so a wave fetches
-// the fragment of (row block, k-slice) with ONE fully coalesced 1-KiB global_load_dwordx4, straight into the registers the
-// MFMA reads.  Each fragment register is re-loaded for the NEXT tap right after the MFMAs that consumed it, so the loads have a
-// whole tap (~1000 cycles) to land.  What this removes from a tap step: the 4 LDS-DMA pieces per wave of the weight tile
-// (their ISSUE was the largest non-MFMA cost of a step), the 8 ds_read_b128 of the A fragments, the
-// 32 KB weight stage and -- because nothing a tap needs is written by another wave any more -- the per-tap barrier: the block
-// synchronises only around a patch reload (every KH*KW taps).
+// Weights: the weight operand never touches LDS.  The packed weights are stored in MFMA A-fragment order -- per (tap, 64-channel
+// chunk, 32-row block) one 4-KiB image [k-slice][lane][16 B] -- so a wave fetches the fragment of (row block, k-slice) with ONE fully
+// coalesced 1-KiB global_load_dwordx4, straight into the registers the MFMA reads.  Each fragment register is re-loaded for the NEXT
+// tap right after the MFMAs that consumed it, so the loads have a whole tap (~1000 cycles) to land.  Staging the weight tile through
+// LDS instead cost a tap step the LDS-DMA issue of the tile (the largest non-MFMA cost of a step), the
+// ds_reads of the A fragments, a 32 KB double-buffered stage and a barrier per tap.  With nothing a tap needs written by another wave,
+// the block synchronises only around a patch reload (every KH*KW taps).
 //
-// NTAP > 0 (with WD): the spatial taps of a patch are a compile-time unrolled sequence (9 = dense 3x3 stride 1, 1 = 1x1), which
+// NTAP > 0: the spatial taps of a patch are a compile-time unrolled sequence (9 = dense 3x3 stride 1, 1 = 1x1), which
 // takes everything tap-dependent out of the hot loop: the swizzled LDS address of every (tap, position sub-tile) B fragment is
 // computed ONCE per block into NTAP x PT registers (one v_xor per ds_read remains), the tap tables are never read again (the
 // s_load + s_waitcnt lgkmcnt(0) they cost per tap also drained the LDS queue), the weight pointer advances by a scalar add, and the
 // per-lane source offsets of the patch LDS-DMA are kept in registers across reloads.  NTAP = 0: the generic table-driven loop
 // (strided 3x3 convs with their stride-parity planes, other kernel shapes).
 // (the unrolled 128-position variants are held to 168 registers -- three blocks per CU -- the 256-position ones to 256)
-template <int BP, int NTAP> struct MinWaves { static constexpr int value = BP == 320 ? 1 : (NTAP > 0 && NTAP != 10 && BP == 128) ? 3 : 2; };
+template <int BP, int NTAP> struct MinWaves { static constexpr int value = (NTAP > 0 && NTAP != 10 && BP == 128) ? 3 : 2; };
 //
 // ODT = element type of the OUTPUT and of the residual (default: the operand type DT).  ODT = fp32 with DT = bf16 is the "bf16x3"
 // arithmetic mode (dat_conv_desc.dtype DAT_BF16X3): activations live in HBM as fp32, the conv reads a hi / lo bf16 SPLIT of its
@@ -60,8 +55,11 @@ template <int BP, int NTAP> struct MinWaves { static constexpr int value = BP ==
 // the MFMA loop, untouched, accumulates x_hi*W_hi + x_hi*W_lo + x_lo*W_hi in fp32: the fp32 product to ~2^-16 relative at three
 // bf16 MFMAs per k-slice instead of sixteen quarter-rate v_mfma_f32_32x32x2_f32.  Only the chunk -> source-line map (p.x3) and the
 // epilogue's element type know about it.
-template <int DT, int BN, int BP, int WAVES_N, int TPS = 1, int WD = 0, int NTAP = 0, int ODT = DT>
+//
+// ONE is always 1: it keeps the kernel names' template-argument layout, which bench.py's _short_kernel parses (fifth argument).
+template <int DT, int BN, int BP, int WAVES_N, int ONE, int NTAP, int ODT>
 __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_igemm_kernel(const ConvParams p) {
+    static_assert(ONE == 1, "see the comment above");
     constexpr int ES = ElemOf<DT>::size;
     constexpr int OES = ElemOf<ODT>::size;
     constexpr int CK = Mma<DT>::CK;
@@ -70,8 +68,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
     constexpr int WP = BP / WAVES_P;      // positions per wave
     constexpr int MT = WN / 32;
     constexpr int PT = WP / 32;
-    constexpr int W_ITEMS = BN * 8 / NTHREADS;  // 16-B items of the weight tile per thread
-    static_assert(MT >= 1 && PT >= 1 && W_ITEMS >= 1, "tile too small");
+    static_assert(MT >= 1 && PT >= 1, "tile too small");
 
 #ifdef DAT_CONV_TRACE
     const unsigned long long tr_k0 = __builtin_amdgcn_s_memtime();
@@ -80,8 +77,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
     unsigned long long clk_c0 = 0, clk_r0 = 0;
     if (p.clk) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* wbuf = smem;                                       // 2 stages x TPS taps x BN x 128 B (WD: no weight stage)
-    char* patch = smem + (WD ? 0 : 2 * TPS * BN * ROWB);     // PH*PW x 128 B
+    char* patch = smem;                                      // PH*PW x 128 B
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -123,7 +119,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
     const int n0 = nb * BN;
     const int TW = 1 << p.tw_log2;
     const int oh0 = th_i << p.th_log2;
-    const int ow0 = tw_i * p.tile_w;         // (1 << tw_log2, except for the 320-position linear tiles)
+    const int ow0 = tw_i * p.tile_w;         // (== 1 << tw_log2)
     // input coordinate of patch cell (0,0)
     const int ih0 = oh0 * p.sh - p.ph;
     const int iw0 = ow0 * p.sw - p.pw;
@@ -155,57 +151,28 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
     const int ntab = p.tab_n;          // == ntap, in plane order
     const int npatch = n_kt * p.n_cchunks;                 // (kt, channel chunk) patches of this output frame
     const int pi_lo = (npatch * split) / p.ksplit, pi_hi = (npatch * (split + 1)) / p.ksplit;
-    const int total = (pi_hi - pi_lo) * (ntab / TPS);     // steps of TPS taps (the launcher guarantees ntab % TPS == 0)
+    const int total = (pi_hi - pi_lo) * ntab;              // tap steps
 
-    const size_t w_tap_stride = (size_t)p.Cout_pad * p.Cin * ES;  // bytes between taps
     const int npatch_items = p.PH * p.PW * 8;
 
-    // ---- weight tile: global -> LDS by LDS-DMA (global_load_lds_dwordx4), no staging registers, no ds_write pass ----
-    // One wave-instruction lands 64 x 16 B = 8 tile rows, lane-linear (dest = uniform base + lane*16).  The XOR swizzle
-    // the fragment reads use is therefore applied on the SOURCE side: lane (row, phys slot) fetches the row's logical
-    // slot phys ^ ((row >> 1) & 7) -- the same involution as swz() (cdna_hip_programming.md rule 21).
-    // Item i of this thread: row (tid >> 3) + 32*i, phys slot tid & 7; (row >> 1) & 7 == (tid >> 4) & 7 for every i.
-    static_assert(W_ITEMS == 2 || W_ITEMS == 4, "weight tile = 2 or 4 16-byte items per thread");
-    const unsigned w_thr_off = (unsigned)(tid >> 3) * (unsigned)(p.Cin * ES) + (unsigned)(((tid & 7) ^ ((tid >> 4) & 7)) * 16);
-    const unsigned w_item_stride = 32u * (unsigned)(p.Cin * ES);
-    const size_t w_blk_off = (size_t)n0 * p.Cin * ES;                                             // uniform part
+    // ---- input patch: global -> LDS by LDS-DMA (global_load_lds_dwordx4), no staging registers, no ds_write pass ----
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
-#define W_DMA(SRC_, DST_) __builtin_amdgcn_global_load_lds((gptr_t)(SRC_), (lptr_t)(DST_), 16, 0, 0)
 #ifndef DAT_PATCH_AUX
 #define DAT_PATCH_AUX 0
 #endif
 #define P_DMA(SRC_, DST_) __builtin_amdgcn_global_load_lds((gptr_t)(SRC_), (lptr_t)(DST_), 16, 0, DAT_PATCH_AUX)
-#define W_PREFETCH(KT_, CC_, TI_, BUF_)                                                                         \
-    _Pragma("unroll") for (int u_ = 0; u_ < TPS; ++u_) {                                                        \
-        const char* wbase_ = p.w + ((size_t)((KT_) * ntap + p.tab_tap[(TI_) + u_]) * w_tap_stride + (size_t)(CC_) * CK * ES + w_blk_off); \
-        char* wdst_ = wbuf + ((BUF_) * TPS + u_) * BN * ROWB + wave * (8 * ROWB);                               \
-        W_DMA(wbase_ + w_thr_off, wdst_);                                                                       \
-        W_DMA(wbase_ + (w_thr_off + w_item_stride), wdst_ + 32 * ROWB);                                         \
-        if (W_ITEMS == 4) {                                                                                     \
-            W_DMA(wbase_ + (w_thr_off + 2 * w_item_stride), wdst_ + 64 * ROWB);                                 \
-            W_DMA(wbase_ + (w_thr_off + 3 * w_item_stride), wdst_ + 96 * ROWB);                                 \
-        }                                                                                                       \
-    }
-    // the tile of this step was requested one step ago: retire this wave's DMAs; the barrier that follows publishes
-    // every wave's part (a ds_read is ordered behind an LDS-DMA only by the issuer's vmcnt + a barrier)
-#define W_COMMIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+    // retire this wave's patch DMAs; the barrier that follows publishes every wave's part (a ds_read is ordered behind an LDS-DMA
+    // only by the issuer's vmcnt + a barrier)
+#define P_COMMIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
-    // per-lane LDS byte offsets of the weight fragments (lane-constant): row -> 4 k-slices, XOR-swizzled
-    int a_off[MT][4];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) a_off[i][ks] = swz(wave_n * WN + i * 32 + (lane & 31), ks * 2 + khalf);
-    // WD: this wave's A fragments in global memory: 4 KiB per (tap, channel chunk, 32-row block), this lane's 16 B inside it
-    static_assert(!WD || TPS == 1, "direct weights: one tap per step");
+    // this wave's A fragments in global memory: 4 KiB per (tap, channel chunk, 32-row block), this lane's 16 B inside it
     const size_t wd_cc_stride = (size_t)(p.Cout_pad >> 5) * 4096;
     const char* const wd_lane = p.w + (size_t)((n0 + wave_n * WN) >> 5) * 4096 + lane * 16;
 #define WD_PTR(KT_, CC_, TI_) (wd_lane + ((size_t)((KT_) * ntap + p.tab_tap[(TI_)]) * p.n_cchunks + (CC_)) * wd_cc_stride)
-    if constexpr (WD && NTAP > 0) {
+    if constexpr (NTAP > 0) {
       constexpr int NT = NTAP == 10 ? 9 : NTAP;   // NTAP = 10: the 9 taps of a 3x3 stride-2 conv on ONE dense (2*TH+1) x (2*TW+1) patch
       if (total > 0) {
-        static_assert(TPS == 1, "unrolled taps: one tap per step");
         constexpr int MAXCH = patch_pieces_per_wave(NTAP, BP);   // 1-KiB patch pieces per wave (the launcher checks nchunks <= 4 * MAXCH)
         const int kt_hi_x = kt_lo + n_kt;
         int kshift = 0;
@@ -280,7 +247,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
                         P_DMA(src, patch + (wave + 4 * u) * 1024);
                     }
                 }
-                W_COMMIT();
+                P_COMMIT();
                 __syncthreads();
             }
             // the patch after this one (its first tap's weights are fetched during this patch's last tap)
@@ -345,15 +312,13 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
         if (n_kt == p.KT && (DAT_KT_ROTATE)) kshift = (p.KT - (t + kt_lo - p.pt) % p.KT) % p.KT;
         int kt = kt_lo + pi_lo / p.n_cchunks + kshift, cc = pi_lo % p.n_cchunks, ti = 0;
         if (kt >= kt_hi_x) kt -= n_kt;
-        uint4 wa[MT][4];      // WD: the A fragments of the current tap (k-slice ks re-loaded for the next tap after its MFMAs)
-        if (WD) {
+        uint4 wa[MT][4];      // the A fragments of the current tap (k-slice ks re-loaded for the next tap after its MFMAs)
+        {
             const char* w0 = WD_PTR(kt, cc, 0);
 #pragma unroll
             for (int i = 0; i < MT; ++i)
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) wa[i][ks] = *(const uint4*)(w0 + i * 4096 + ks * 1024);
-        } else {
-            W_PREFETCH(kt, cc, 0, 0);
         }
         const int nchunks = (npatch_items + 63) >> 6;    // 1-KiB LDS-DMA pieces (8 patch rows each)
 #ifdef DAT_CONV_TRACE
@@ -392,30 +357,26 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
                 }
             }
             TR_ADD(tr_reload);
-            if (!WD || ((p.tab_new >> ti) & 1u)) {   // WD: only a patch reload needs the block to meet
-                W_COMMIT();
+            if ((p.tab_new >> ti) & 1u) {   // only a patch reload needs the block to meet
+                P_COMMIT();
                 TR_ADD(tr_wait);
                 __syncthreads();
             }
             TR_ADD(tr_bar);
-            // advance to the next (kt, cc, table entry) and prefetch its weight tile (lands during this step's MFMAs)
-            int nti = ti + TPS, ncc = cc, nkt = kt;
+            // advance to the next (kt, cc, table entry)
+            int nti = ti + 1, ncc = cc, nkt = kt;
             if (nti == ntab) {
                 nti = 0;
                 if (++ncc == p.n_cchunks) { ncc = 0; if (++nkt == kt_hi_x) nkt = kt_lo; }
             }
-            // (issuing the pieces between the k-slices' MFMAs instead measured 7 % slower: a DMA issue stalls the MFMA stream)
-            if (!WD && step + 1 < total && !((p.ablate & 2) && step > 1)) W_PREFETCH(nkt, ncc, nti, (step + 1) & 1);
             const char* const wnext = (step + 1 < total) ? WD_PTR(nkt, ncc, nti) : WD_PTR(kt, cc, ti);
 
             TR_ADD(tr_issue);
-            // ---- compute the step's taps: 4 k-slices of 16 B per row each, fragments double-buffered in registers ----
+            // ---- compute the step's tap: 4 k-slices of 16 B per row each, patch fragments double-buffered in registers ----
             // the co-resident block's wave on this SIMD is usually in its load phase: let the MFMA stream win arbitration
             __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int u = 0; u < TPS; ++u) {
-                const int tapoff = p.tab_rowoff[ti + u];
-                const char* wb = wbuf + ((step & 1) * TPS + u) * BN * ROWB;
+            {
+                const int tapoff = p.tab_rowoff[ti];
                 // patch fragment of (row, k-slice ks, k-half): 16-B slot (2*ks + khalf) ^ ((row >> 1) & 7) of the row's line
                 const char* bp[PT];
                 int bx[PT];
@@ -426,34 +387,25 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
                     bp[j] = patch + (row * PPITCH + ((khalf ^ (g & 1)) << 4));
                     bx[j] = g >> 1;
                 }
-                uint4 a[2][MT], b[2][PT];
-                if (!WD) {
-#pragma unroll
-                    for (int i = 0; i < MT; ++i) a[0][i] = *(const uint4*)(wb + a_off[i][0]);
-                }
+                uint4 b[2][PT];
 #pragma unroll
                 for (int j = 0; j < PT; ++j) b[0][j] = *(const uint4*)(bp[j] + (bx[j] << 5));
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) {
                     const int cur = ks & 1, nxt = cur ^ 1;
                     if (ks < 3) {
-                        if (!WD) {
-#pragma unroll
-                            for (int i = 0; i < MT; ++i) a[nxt][i] = *(const uint4*)(wb + a_off[i][ks + 1]);
-                        }
 #pragma unroll
                         for (int j = 0; j < PT; ++j) b[nxt][j] = *(const uint4*)(bp[j] + (((ks + 1) ^ bx[j]) << 5));
                     }
 #pragma unroll
                     for (int i = 0; i < MT; ++i)
 #pragma unroll
-                        for (int j = 0; j < PT; ++j) Mma<DT>::step(WD ? wa[i][ks] : a[cur][i], b[cur][j], acc[i][j]);
-                    if (WD) {   // this k-slice's fragments of the NEXT tap: a whole tap to land.  Unconditional (a branch around the loads made
-                                // the compiler wait with vmcnt(0) at the top of every tap) and pinned here (see the unrolled variant)
+                        for (int j = 0; j < PT; ++j) Mma<DT>::step(wa[i][ks], b[cur][j], acc[i][j]);
+                    // this k-slice's fragments of the NEXT tap: a whole tap to land.  Unconditional (a branch around the loads made
+                    // the compiler wait with vmcnt(0) at the top of every tap) and pinned here (see the unrolled variant)
 #pragma unroll
-                        for (int i = 0; i < MT; ++i) wa[i][ks] = *(const uint4*)(wnext + i * 4096 + ks * 1024);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
+                    for (int i = 0; i < MT; ++i) wa[i][ks] = *(const uint4*)(wnext + i * 4096 + ks * 1024);
+                    __builtin_amdgcn_sched_barrier(0);
                 }
             }
             __builtin_amdgcn_s_setprio(0);
@@ -471,9 +423,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
 #endif
     }
 #undef WD_PTR
-#undef W_PREFETCH
-#undef W_COMMIT
-#undef W_DMA
+#undef P_COMMIT
 #undef P_DMA
 
     // ---- epilogue: affine/bias + residual + relu, staged through LDS so that HBM sees whole 128-B+ runs ----
@@ -487,7 +437,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
     constexpr int CPL = 16 / OES;                 // channels per lane in the store phase (8 bf16 / 4 fp32)
     constexpr int LPP = WN / CPL;                // lanes per position (8 / 16)
     constexpr int PPI = 64 / LPP;                // positions per store instruction (8 / 4)
-    __syncthreads();                             // every wave is done with the weight / patch buffers
+    __syncthreads();                             // every wave is done with the patch
     char* est = smem + wave * (32 * EPITCH);
     const int sl_c = (lane % LPP) * CPL;         // this lane's first channel inside the wave's 64
     const int sl_p = lane / LPP;
@@ -743,7 +693,6 @@ static long long linear_tiles(const dat_ctx* ctx, const dat_conv_desc* d, const 
         p.H != p.Ho || p.W != p.Wo)
         return 0;
     if (d->KT == 1 && (d->pad_t != 0 || d->out_tn > 0)) return 0;
-    if (d->KT > 1 && (ctx->dbg_linear & 8)) return 0;   // (DAT_CONV_LINEAR=9: A/B switch, no per-frame strips)
     const long long per = d->KT > 1 ? (long long)p.Ho * p.Wo : (long long)p.frames * p.Ho * p.Wo;
     const long long nr = bpv + 2 * (p.Wo + 1) + 1;
     if (((nr * 8 + 63) >> 6) > 4 * patch_pieces_per_wave(9, bpv) || nr * PPITCH >= 65536 ||
@@ -757,8 +706,7 @@ struct TileChoice {
 };
 
 // pick the 2^a x 2^b tile (a+b = log2(BP)) that wastes the fewest output positions, tie -> squarer patch
-TileChoice choose_tile(int Ho, int Wo, int bp_log2, int sh, int sw, int KH, int KW, int force_tw) {
-    if (force_tw >= 0 && force_tw <= bp_log2) return TileChoice{bp_log2 - force_tw, force_tw};
+TileChoice choose_tile(int Ho, int Wo, int bp_log2, int sh, int sw, int KH, int KW) {
     TileChoice best{0, bp_log2};
     double best_cost = 1e30;
     for (int a = 0; a <= bp_log2; ++a) {
@@ -781,9 +729,9 @@ TileChoice choose_tile(int Ho, int Wo, int bp_log2, int sh, int sw, int KH, int 
     return best;
 }
 
-template <int DT, int BN, int BP, int WAVES_N, int TPS = 1, int WD = 0, int NTAP = 0, int ODT = DT>
+template <int DT, int BN, int BP, int WAVES_N, int NTAP, int ODT>
 int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ksplit, bool linear = false) {
-    TileChoice tc = choose_tile(p.Ho, p.Wo, bp_log2, p.sh, p.sw, p.KH, p.KW, ctx->dbg_tw_log2);
+    TileChoice tc = choose_tile(p.Ho, p.Wo, bp_log2, p.sh, p.sw, p.KH, p.KW);
     p.lin_h = p.lin_w = 0;
     p.lin_zero_row = -1;
     if (linear) {
@@ -808,7 +756,7 @@ int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ks
         if (!per_frame) { p.frames = 1; p.T = 1; p.ot0 = 0; p.otn = 1; p.in_lo = 0; p.in_hi = 1; }
         p.ph = 0; p.pw = wr + 1;
         p.lin_zero_row = nr - 1;
-        p.th_log2 = 0; p.tw_log2 = bp_log2;      // (bp_log2 = 9 for the 320-position tiles: pos >> tw_log2 == 0, pos & (TW - 1) == pos)
+        p.th_log2 = 0; p.tw_log2 = bp_log2;
         p.tile_w = BP;
         p.tiles_h = 1; p.tiles_w = (int)cdiv_ll(total, BP);
         p.psh = p.psw = 1; p.rsh = p.rsw = 1;
@@ -892,13 +840,11 @@ int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ks
     // the forward (res5's 512 -> 512 x 27 taps 2.09 -> 0.46 GB per launch, P2 7.8 -> 4.6 GB) and every such layer 2-4 % SLOWER -- the
     // sibling cout block no longer finds the patch in L2, and patch misses are waited for while weight misses are not.  Kept as a switch.
     p.order = ctx->dbg_order > 0;
-    DAT_ENFORCE(ctx, p.tab_n % TPS == 0 && (TPS == 1 || p.tab_new == 1u), "conv3d: %d taps per step need one stride plane of a multiple of %d taps", TPS, TPS);
-    size_t lds = (WD ? 0 : (size_t)2 * TPS * BN * ROWB) + (((size_t)p.PH * p.PW * PPITCH + 1023) & ~(size_t)1023);   // whole 1-KiB DMA pieces
-    if (lds < 4 * 32 * (64 * 4 + 16)) lds = 4 * 32 * (64 * 4 + 16);                                   // epilogue staging slices
-    lds += ctx->dbg_lds_pad;   // DEBUG: DAT_CONV_LDS_PAD=<bytes> lowers occupancy (blocks per CU) for experiments
+    size_t lds = ((size_t)p.PH * p.PW * PPITCH + 1023) & ~(size_t)1023;     // whole 1-KiB DMA pieces
+    if (lds < 4 * 32 * (64 * 4 + 16)) lds = 4 * 32 * (64 * 4 + 16);         // epilogue staging slices
     DAT_ENFORCE(ctx, lds <= 160 * 1024, "conv3d: LDS patch of %zu bytes exceeds 160 KiB (tile %dx%d, stride %dx%d)", lds,
                 th, tw, p.sh, p.sw);
-    auto kern = conv3d_igemm_kernel<DT, BN, BP, WAVES_N, TPS, WD, NTAP, ODT>;
+    auto kern = conv3d_igemm_kernel<DT, BN, BP, WAVES_N, 1, NTAP, ODT>;
     if (NTAP > 0) {   // what the unrolled variant assumes (the dispatcher only picks it for these shapes)
         DAT_ENFORCE(ctx, p.tab_n == (NTAP == 10 ? 9 : NTAP) && p.tab_new == 1u &&
                              (((size_t)p.PH * p.PW * 8 + 63) >> 6) <= (size_t)4 * patch_pieces_per_wave(NTAP, BP) && (NTAP == 10 || (size_t)p.PH * p.PW * PPITCH < 65536),
@@ -990,7 +936,6 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
     DAT_ENFORCE(ctx, d->dtype == DAT_F32 || d->dtype == DAT_BF16 || d->dtype == DAT_BF16X3, "conv3d_fwd: bad dtype %d", d->dtype);
     const bool x3 = d->dtype == DAT_BF16X3;
     DAT_ENFORCE(ctx, !x3 || DAT_H16_FORMAT == 0, "conv3d_fwd: DAT_BF16X3 needs the bf16 build of the library (this one holds IEEE half in its 16-bit tensors)");
-    DAT_ENFORCE(ctx, !x3 || weights_direct(ctx, d), "conv3d_fwd: the bf16x3 mode runs on the weights-direct kernel variants (DAT_CONV_WD)");
     DAT_ENFORCE(ctx, d->Cin % 64 == 0, "conv3d_fwd: Cin (channel stride) %d must be a multiple of 64", d->Cin);
     DAT_ENFORCE(ctx, d->Cout % 4 == 0 && d->out_cstride % 4 == 0 && d->out_cstride >= d->Cout,
                 "conv3d_fwd: Cout %d / out_cstride %d must be multiples of 4", d->Cout, d->out_cstride);
@@ -1048,9 +993,9 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
             if (cand_bp == 256 && !force_bp && ctx->dbg_ntap && !(ctx->dbg_ntap & 4) && d->KH == 3 && d->KW == 3 && d->stride_h == 2 && d->stride_w == 2) continue;
             if (force_bp && cand_bp != force_bp && !(force_bp == 256 && (small_n || ntaps == 1))) continue;
             const int lg = cand_bp == 256 ? 8 : 7;
-            const TileChoice tc = choose_tile(p.Ho, p.Wo, lg, p.sh, p.sw, p.KH, p.KW, ctx->dbg_tw_log2);
+            const TileChoice tc = choose_tile(p.Ho, p.Wo, lg, p.sh, p.sw, p.KH, p.KW);
             long long tiles = cdiv_ll(p.Ho, 1ll << tc.th_log2) * cdiv_ll(p.Wo, 1ll << tc.tw_log2) * p.frames;
-            if (weights_direct(ctx, d)) {   // (the dispatcher's rule below: linear tiles when they save >= 10 %)
+            {   // (the dispatcher's rule below: linear tiles when they save >= 10 %)
                 const long long tl = linear_tiles(ctx, d, p, cand_bp);
                 if (tl > 0 && tl * 10 <= tiles * 9) tiles = tl;
             }
@@ -1086,9 +1031,6 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
         hipEventRecord(e0, st);
     }
     int rc;
-    const int tps3 = ctx->dbg_tps3;
-    // thin layers (<= 64 output channels, dense 3x3 spatial taps): 3 taps per step
-    const bool thin3 = tps3 && small_n && !big && d->stride_h == 1 && d->stride_w == 1 && d->KH == 3 && d->KW == 3 && !weights_direct(ctx, d);
     // big-tile kernel: one block per CU at a time, so the grid has to fill the chip several times and evenly (FPN P2: 2016 blocks on
     // 256 CUs = 7.9 rounds; P3's 528 blocks would run 3 rounds for 2.06 of work: 0.45 ms against 0.34 ms with the generic kernel)
     long long bt_blocks = 0;
@@ -1102,7 +1044,7 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
     } else if (pw256_eligible(ctx, d) && !force_bp && !force_ks && !mask_mode) {
         tag = 256 * 10000 + 320 + d->dtype;     // (256 channels x 32 positions per wave: the weights-stationary 1x1 kernel)
         rc = launch_pw256(ctx, st, p);
-    } else if (pwks_eligible(ctx, d) && !force_bp && !force_ks && !x3) {       // (its epilogue knows the masking combine too)
+    } else if (pwks_eligible(ctx, d) && !force_bp && !force_ks) {       // (its epilogue knows the masking combine too)
         tag = 256 * 10000 + 340 + d->dtype;     // (the K-streaming 1x1 kernel: 256 positions x 256 channels per block)
         rc = launch_pwks(ctx, st, p);
     } else if (pwlw_eligible(ctx, d) && !force_bp && !force_ks && d->res_mode != 3) {   // (knows the sum + mask combine; plain mask layers -- K >= 512 data
@@ -1112,14 +1054,11 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
     } else if (ws64_eligible(ctx, d) && !force_bp && !force_ks && !mask_mode) {
         tag = 64 * 10000 + 9990 + d->dtype;    // ("999 positions": the persistent weights-stationary kernel)
         rc = launch_ws64(ctx, st, p);
-    } else if (thin3) {
-        tag += 3;   // (dtype digit + 3: the 3-taps-per-step variant)
-        rc = d->dtype == DAT_BF16 ? launch_conv<DAT_BF16, 64, 128, 1, 3>(ctx, st, p, 7, ksplit) : launch_conv<DAT_F32, 64, 128, 1, 3>(ctx, st, p, 7, ksplit);
-    } else if (weights_direct(ctx, d)) {   // weights straight into the MFMA registers (all 128-channel tiles; 64-channel ones at DAT_CONV_WD=2)
+    } else {   // the implicit-GEMM kernel: weights straight into the MFMA registers
         // unrolled-tap variants: dense 3x3 (stride 1) and 1x1 (any stride: one tap, one plane); the patch must fit the per-wave
         // piece registers (tile shapes with very long rows fall back to the table-driven loop).  1x1 layers with a large output
         // grid are bandwidth-bound and do better with the leaner table-driven loop (one block more per CU), measured.
-        const TileChoice tc = choose_tile(p.Ho, p.Wo, big ? 8 : 7, p.sh, p.sw, p.KH, p.KW, ctx->dbg_tw_log2);
+        const TileChoice tc = choose_tile(p.Ho, p.Wo, big ? 8 : 7, p.sh, p.sw, p.KH, p.KW);
         const long long prow = ((1ll << tc.th_log2) + (p.KH - 1) / p.sh) * ((1ll << tc.tw_log2) + (p.KW - 1) / p.sw);
         const bool fits = ((prow * 8 + 63) >> 6) <= 4 * patch_pieces_per_wave(9, big ? 256 : 128);
         const bool pw_small = (long long)p.frames * p.Ho * p.Wo <= 65536;
@@ -1131,40 +1070,19 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
         const int ntapv = dense2 ? 10 : !ctx->dbg_ntap || !fits ? 0 : (d->KH == 3 && d->KW == 3 && d->stride_h == 1 && d->stride_w == 1) ? 9 :
                           (d->KH == 1 && d->KW == 1 && (pw_small || (ctx->dbg_ntap & 2))) ? 1 : 0;
         // small maps (RoI heads): linear position tiling when it saves >= 10 % of the tiles (see launch_conv)
-        bool lin = false, lin320 = false;
+        bool lin = false;
         const long long tlin = ntapv == 9 ? linear_tiles(ctx, d, p, big ? 256 : 128) : 0;
         if (tlin > 0) {
-            const long long total = (long long)p.frames * p.Ho * p.Wo;
             const long long t2d = (long long)p.frames * cdiv_ll(p.Ho, 1ll << tc.th_log2) * cdiv_ll(p.Wo, 1ll << tc.tw_log2);
             lin = tlin * 10 <= t2d * 9;
-            // One block per CU runs a tap step in ~1.1 us, two co-resident ones in ~2.15 us each, so a grid just above the CU count
-            // costs a whole second block lifetime (keypoint head, 100 x 14 x 14 maps: 83 maps = 256 blocks 0.081 ms, 84 maps = 260
-            // blocks 0.119 ms).  320-position tiles bring such a grid back under one block per CU.
-            const long long ncu320 = ctx_num_cu(ctx), blk256 = tlin * nbn * ksplit, blk320 = cdiv_ll(total, 320) * nbn * ksplit;
-            // (opt-in, DAT_CONV_LINEAR=5: one clip at a time +2.9 % (170.6 -> 175.5 clips/s), but with four clips in flight -2 % (221.8 -> 217.5):
-            //  a 293-register block per CU on 248 CUs leaves no room for the other clips' kernels to run beside it)
-            lin320 = lin && d->KT == 1 && big && !small_n && (ctx->dbg_linear & 4) && blk256 > ncu320 && blk320 <= ncu320 &&
-                     ((((320 + 2 * (p.Wo + 1) + 1) * 8 + 63) >> 6) <= 4 * patch_pieces_per_wave(9, 320));
         }
-#define DAT_WD_LAUNCH(DT_, BN_, WN_, ODT_) (ntapv == 10 ? launch_conv<DT_, BN_, 128, WN_, 1, 1, 10, ODT_>(ctx, st, p, 7, ksplit) : ntapv == 9 ? (big ? launch_conv<DT_, BN_, 256, WN_, 1, 1, 9, ODT_>(ctx, st, p, 8, ksplit, lin) : launch_conv<DT_, BN_, 128, WN_, 1, 1, 9, ODT_>(ctx, st, p, 7, ksplit, lin)) \
-                            : ntapv == 1 ? (big ? launch_conv<DT_, BN_, 256, WN_, 1, 1, 1, ODT_>(ctx, st, p, 8, ksplit) : launch_conv<DT_, BN_, 128, WN_, 1, 1, 1, ODT_>(ctx, st, p, 7, ksplit)) \
-                            : (big ? launch_conv<DT_, BN_, 256, WN_, 1, 1, 0, ODT_>(ctx, st, p, 8, ksplit) : launch_conv<DT_, BN_, 128, WN_, 1, 1, 0, ODT_>(ctx, st, p, 7, ksplit)))
-        if (x3) rc = small_n ? DAT_WD_LAUNCH(DAT_BF16, 64, 1, DAT_F32) : DAT_WD_LAUNCH(DAT_BF16, 128, 2, DAT_F32);
-        else if (lin320) rc = d->dtype == DAT_BF16 ? launch_conv<DAT_BF16, 128, 320, 2, 1, 1, 9>(ctx, st, p, 9, ksplit, true)
-                                              : launch_conv<DAT_F32, 128, 320, 2, 1, 1, 9>(ctx, st, p, 9, ksplit, true);
-        else if (small_n) rc = d->dtype == DAT_BF16 ? DAT_WD_LAUNCH(DAT_BF16, 64, 1, DAT_BF16) : DAT_WD_LAUNCH(DAT_F32, 64, 1, DAT_F32);
-        else rc = d->dtype == DAT_BF16 ? DAT_WD_LAUNCH(DAT_BF16, 128, 2, DAT_BF16) : DAT_WD_LAUNCH(DAT_F32, 128, 2, DAT_F32);
-#undef DAT_WD_LAUNCH
-    } else if (d->dtype == DAT_BF16) {
-        if (big)
-            rc = small_n ? launch_conv<DAT_BF16, 64, 256, 1>(ctx, st, p, 8, ksplit) : launch_conv<DAT_BF16, 128, 256, 2>(ctx, st, p, 8, ksplit);
-        else
-            rc = small_n ? launch_conv<DAT_BF16, 64, 128, 1>(ctx, st, p, 7, ksplit) : launch_conv<DAT_BF16, 128, 128, 2>(ctx, st, p, 7, ksplit);
-    } else {
-        if (big)
-            rc = small_n ? launch_conv<DAT_F32, 64, 256, 1>(ctx, st, p, 8, ksplit) : launch_conv<DAT_F32, 128, 256, 2>(ctx, st, p, 8, ksplit);
-        else
-            rc = small_n ? launch_conv<DAT_F32, 64, 128, 1>(ctx, st, p, 7, ksplit) : launch_conv<DAT_F32, 128, 128, 2>(ctx, st, p, 7, ksplit);
+#define DAT_CONV_LAUNCH(DT_, BN_, WN_, ODT_) (ntapv == 10 ? launch_conv<DT_, BN_, 128, WN_, 10, ODT_>(ctx, st, p, 7, ksplit) : ntapv == 9 ? (big ? launch_conv<DT_, BN_, 256, WN_, 9, ODT_>(ctx, st, p, 8, ksplit, lin) : launch_conv<DT_, BN_, 128, WN_, 9, ODT_>(ctx, st, p, 7, ksplit, lin)) \
+                            : ntapv == 1 ? (big ? launch_conv<DT_, BN_, 256, WN_, 1, ODT_>(ctx, st, p, 8, ksplit) : launch_conv<DT_, BN_, 128, WN_, 1, ODT_>(ctx, st, p, 7, ksplit)) \
+                            : (big ? launch_conv<DT_, BN_, 256, WN_, 0, ODT_>(ctx, st, p, 8, ksplit) : launch_conv<DT_, BN_, 128, WN_, 0, ODT_>(ctx, st, p, 7, ksplit)))
+        if (x3) rc = small_n ? DAT_CONV_LAUNCH(DAT_BF16, 64, 1, DAT_F32) : DAT_CONV_LAUNCH(DAT_BF16, 128, 2, DAT_F32);
+        else if (small_n) rc = d->dtype == DAT_BF16 ? DAT_CONV_LAUNCH(DAT_BF16, 64, 1, DAT_BF16) : DAT_CONV_LAUNCH(DAT_F32, 64, 1, DAT_F32);
+        else rc = d->dtype == DAT_BF16 ? DAT_CONV_LAUNCH(DAT_BF16, 128, 2, DAT_BF16) : DAT_CONV_LAUNCH(DAT_F32, 128, 2, DAT_F32);
+#undef DAT_CONV_LAUNCH
     }
     if (e1) {
         hipEventRecord(e1, st);

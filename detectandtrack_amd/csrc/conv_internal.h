@@ -13,8 +13,7 @@
 
 namespace dat_conv __attribute__((visibility("hidden"))) {
 
-constexpr int ROWB = 128;   // bytes per weight LDS row (one 128-B line of channels), XOR-swizzled
-constexpr int PPITCH = 128; // patch row pitch: one 128-B line per pixel, lane-linear LDS-DMA image, XOR-swizzled like the weights
+constexpr int PPITCH = 128; // patch row pitch: one 128-B line per pixel, lane-linear LDS-DMA image, XOR-swizzled
 constexpr int NTHREADS = 256;
 #ifndef DAT_KT_ROTATE
 #define DAT_KT_ROTATE 1
@@ -63,7 +62,7 @@ struct ConvParams {
     int n_cchunks;            // Cin / CK
     int ksplit;               // split-K over the (kt, channel-chunk) sequence; > 1 => fp32 partials to `part`
     float* part;              // [ksplit][frames*Ho*Wo][Cout] fp32 (split-K only)
-    int ablate;               // DEBUG (DAT_CONV_ABLATE): 1 skip patch reloads, 2 skip weight streaming
+    int ablate;               // DEBUG (DAT_CONV_ABLATE): 1 skip patch reloads, 4 skip the epilogue, 8 skip patch loads (table-driven loop), 16 no XCD remap
     int nblk_n;               // Cout_pad / BN
     unsigned nblocks;
     unsigned ntiles;          // position tiles (frames x tiles_h x tiles_w)
@@ -99,8 +98,6 @@ __device__ __forceinline__ float res_combine(float v, float r, int mode) { retur
 // conv of the LAST reader of y finishes the sum and applies y's ReLU backward in one epilogue (dat_conv3d_fwd_sum_mask; training.py bwd_Conv)
 __device__ __forceinline__ float res_combine4(float v, float old, float m) { return m > 0.f ? v + old : 0.f; }
 
-__device__ __forceinline__ int swz(int row, int slot) { return (row * ROWB) + (((slot ^ (row >> 1)) & 7) << 4); }
-
 
 // compile-time index sequence for the hand-scheduled loops (`#pragma unroll` is refused for bodies of this size, and immediates /
 // register-ring slots need constant indices)
@@ -115,18 +112,15 @@ inline int cout_pad_of(const dat_conv_desc* d) {
     return (d->Cout + bn - 1) / bn * bn;
 }
 
-// packed-weight layout of a layer: the 128-channel tile variants read A fragments straight from global memory (WD)
-inline bool weights_direct(const dat_ctx* ctx, const dat_conv_desc* d) { return ctx->dbg_wd && (d->Cout > 64 || ctx->dbg_wd >= 2); }
-
 // conv_special.hip
 int ctx_num_cu(dat_ctx* ctx);
 bool ws64_eligible(const dat_ctx* ctx, const dat_conv_desc* d);
 int launch_ws64(dat_ctx* ctx, hipStream_t st, const ConvParams& cp);
 bool pw256_eligible(const dat_ctx* ctx, const dat_conv_desc* d);
 int launch_pw256(dat_ctx* ctx, hipStream_t st, const ConvParams& cp);
-bool pwlw_eligible(const dat_ctx* ctx, const dat_conv_desc* d);
+bool pwlw_eligible(dat_ctx* ctx, const dat_conv_desc* d);
 int launch_pwlw(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const dat_conv_desc* d);
-bool pwks_eligible(const dat_ctx* ctx, const dat_conv_desc* d);
+bool pwks_eligible(dat_ctx* ctx, const dat_conv_desc* d);
 int launch_pwks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp);
 bool bt_eligible(const dat_ctx* ctx, const dat_conv_desc* d);
 int bt_tile_twl(const ConvParams& p, long long* nblocks);

@@ -1,7 +1,7 @@
 // Weight packing for the conv kernels: fp32 masters in the reference's blob layout [Cout, Cin, KT, KH, KW] -> the activation dtype in
-// tap-major order, either row-major [tap][Cout_pad][Cin] (LDS-staged weight tiles) or MFMA A-fragment order (weights straight into
-// registers); the data-gradient twin (channels swapped, taps flipped, AffineChannelNd scale folded in); the
-// batched re-pack of a training step; and the first formulation of conv1 (dat_stem_pack / dat_stem_weights).
+// tap-major MFMA A-fragment order (weights straight into registers); the data-gradient twin (channels swapped,
+// taps flipped, AffineChannelNd scale folded in); the batched re-pack of a training step; and the first formulation of conv1
+// (dat_stem_pack / dat_stem_weights).
 #include "conv_internal.h"
 
 using namespace dat_conv;
@@ -9,15 +9,15 @@ using namespace dat_conv;
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// weight packing: fp32 [Cout_real, Cin_real, KT, KH, KW] -> [tap][Cout_pad][Cin] in dtype, zero padded
-// frag = 1: MFMA A-fragment order of the WD kernel variants: [tap][channel chunk of 128 B][32-row block][k-slice][lane][16 B],
-// lane = k-half * 32 + row, the 16-B slot (2 * k-slice + k-half) of the row's 128-B chunk (what swz() addresses in the LDS path)
+// weight packing: fp32 [Cout_real, Cin_real, KT, KH, KW] -> MFMA A-fragment order in dtype, zero padded to Cout_pad rows:
+// [tap][channel chunk of 128 B][32-row block][k-slice][lane][16 B], lane = k-half * 32 + row, the 16-B slot (2 * k-slice + k-half)
+// of the row's 128-B chunk
 // dgrad = 1: pack the weights of the DATA-GRADIENT conv straight from the forward master w [CoutF = Cin_real][CinF = Cout_real][taps]:
 // logical W'[co'][ci'][tap'] = w[ci'][co'][ntap - 1 - tap'] * scale[ci']  (channels swapped, every kernel axis flipped, the fused
 // AffineChannelNd scale folded in) -- what the host used to build with flip + transpose + mul + contiguous before packing.
 template <int DT>
 __global__ void pack_weights_kernel(const float* __restrict__ w, void* __restrict__ out, int Cout_real, int Cin_real,
-                                    int ntap, int Cout_pad, int Cin, int frag, int dgrad, const float* __restrict__ scale) {
+                                    int ntap, int Cout_pad, int Cin, int dgrad, const float* __restrict__ scale) {
     constexpr int CK = Mma<DT>::CK, EPS = 16 / ElemOf<DT>::size;   // channels per 128-B chunk, elements per 16-B slot
     const size_t total = (size_t)ntap * Cout_pad * Cin;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -29,12 +29,9 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, void* __restric
             if (dgrad) v = w[((size_t)ci * Cout_real + co) * ntap + (ntap - 1 - tap)] * (scale ? scale[ci] : 1.f);
             else v = w[((size_t)co * Cin_real + ci) * ntap + tap];
         }
-        size_t dst = i;
-        if (frag) {
-            const int cc = ci / CK, cl = ci % CK, slot = cl / EPS, e = cl % EPS;
-            const int lane = (slot & 1) * 32 + (co & 31);
-            dst = (((((size_t)tap * (Cin / CK) + cc) * (Cout_pad >> 5) + (co >> 5)) * 4 + (slot >> 1)) * 64 + lane) * EPS + e;
-        }
+        const int cc = ci / CK, cl = ci % CK, slot = cl / EPS, e = cl % EPS;
+        const int lane = (slot & 1) * 32 + (co & 31);
+        const size_t dst = (((((size_t)tap * (Cin / CK) + cc) * (Cout_pad >> 5) + (co >> 5)) * 4 + (slot >> 1)) * 64 + lane) * EPS + e;
         ElemOf<DT>::st(out, dst, v);
     }
 }
@@ -47,7 +44,7 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, void* __restric
 // pieces, 32 consecutive rows (= lanes of a fragment) per 512-byte run.
 template <int DT>
 __device__ __forceinline__ void pack_tile(const float* __restrict__ w, void* __restrict__ out, int Cout_real, int Cin_real, int ntap,
-                                          int Cout_pad, int Cin, int frag, int dgrad, const float* __restrict__ scale, int co0, int ci0,
+                                          int Cout_pad, int Cin, int dgrad, const float* __restrict__ scale, int co0, int ci0,
                                           int CIT) {
     // CIT: input channels of the tile (16 | 32 | 64, pack_cit): pointwise layers -- most of a bottleneck network's parameters -- get
     // 256-byte source runs and 8 KB per block instead of 64-byte runs and 2 KB
@@ -117,14 +114,9 @@ __device__ __forceinline__ void pack_tile(const float* __restrict__ w, void* __r
         float v[EPS];
 #pragma unroll
         for (int e = 0; e < EPS; ++e) v[e] = tile[co_l * pitch + (sl * EPS + e) * ntap + tap];
-        size_t dst;                                     // in elements
-        if (frag) {
-            const int cc = ci / CK, slot = (ci % CK) / EPS;
-            const int lane = (slot & 1) * 32 + (co & 31);
-            dst = (((((size_t)tap * (Cin / CK) + cc) * (Cout_pad >> 5) + (co >> 5)) * 4 + (slot >> 1)) * 64 + lane) * EPS;
-        } else {
-            dst = ((size_t)tap * Cout_pad + co) * Cin + ci;
-        }
+        const int cc = ci / CK, slot = (ci % CK) / EPS;
+        const int lane = (slot & 1) * 32 + (co & 31);
+        const size_t dst = (((((size_t)tap * (Cin / CK) + cc) * (Cout_pad >> 5) + (co >> 5)) * 4 + (slot >> 1)) * 64 + lane) * EPS;   // in elements
         uint4 o;
         if (DT == DAT_BF16) {
             o.x = f2bf2(v[0], v[1]); o.y = f2bf2(v[2], v[3]); o.z = f2bf2(v[4 % EPS], v[5 % EPS]); o.w = f2bf2(v[6 % EPS], v[7 % EPS]);
@@ -137,9 +129,9 @@ __device__ __forceinline__ void pack_tile(const float* __restrict__ w, void* __r
 
 template <int DT>
 __global__ __launch_bounds__(256) void pack_weights_tiled_kernel(const float* __restrict__ w, void* __restrict__ out, int Cout_real,
-                                                                 int Cin_real, int ntap, int Cout_pad, int Cin, int frag, int dgrad,
+                                                                 int Cin_real, int ntap, int Cout_pad, int Cin, int dgrad,
                                                                  const float* __restrict__ scale) {
-    pack_tile<DT>(w, out, Cout_real, Cin_real, ntap, Cout_pad, Cin, frag, dgrad, scale, blockIdx.x * 32, blockIdx.y * 16, 16);
+    pack_tile<DT>(w, out, Cout_real, Cin_real, ntap, Cout_pad, Cin, dgrad, scale, blockIdx.x * 32, blockIdx.y * 16, 16);
 }
 
 // Batched re-pack (training): after an SGD step every trainable layer and its data-gradient twin is re-packed from the fp32 masters --
@@ -159,7 +151,7 @@ __global__ __launch_bounds__(256) void pack_weights_batch_kernel(const dat_pack_
     const dat_pack_item it = items[cnt - 1];          // (tile0 ascending from 0: cnt >= 1)
     const int local = b - it.tile0;
     const int bx = local % it.tiles_x, by = local / it.tiles_x;
-    pack_tile<DT>(it.w, it.packed, it.rows, it.cols, it.ntap, it.cout_pad, it.cin, it.frag, it.dgrad, it.scale, bx * 32, by * it.cit, it.cit);
+    pack_tile<DT>(it.w, it.packed, it.rows, it.cols, it.ntap, it.cout_pad, it.cin, it.dgrad, it.scale, bx * 32, by * it.cit, it.cit);
 }
 
 // input channels per tile of a batched entry: as many as keep the tile (32 rows x cit x taps floats) at or below ~37 KB
@@ -227,28 +219,27 @@ int launch_pack(dat_ctx* ctx, hipStream_t st, const dat_conv_desc* d, const floa
                 void* packed) {
     const int ntap = d->KT * d->KH * d->KW;
     const int cp = cout_pad_of(d);
-    const int frag = weights_direct(ctx, d) ? 1 : 0;
     const size_t lds = (size_t)32 * (16 * ntap + 1) * sizeof(float);
-    if (lds <= 160 * 1024 && !ctx->dbg_pack_simple) {     // coalesced on both sides (see pack_weights_tiled_kernel)
+    if (lds <= 160 * 1024) {     // coalesced on both sides (see pack_weights_tiled_kernel)
         const dim3 grid(cp / 32, d->Cin / 16);
         int rc;
         if (d->dtype == DAT_BF16) {
             if ((rc = dat_ensure_lds(ctx, (const void*)pack_weights_tiled_kernel<DAT_BF16>, 160 * 1024)) != DAT_OK) return rc;
-            hipLaunchKernelGGL(pack_weights_tiled_kernel<DAT_BF16>, grid, dim3(256), lds, st, w, packed, rows, cols, ntap, cp, d->Cin, frag,
+            hipLaunchKernelGGL(pack_weights_tiled_kernel<DAT_BF16>, grid, dim3(256), lds, st, w, packed, rows, cols, ntap, cp, d->Cin,
                                dgrad, scale);
         } else {
             if ((rc = dat_ensure_lds(ctx, (const void*)pack_weights_tiled_kernel<DAT_F32>, 160 * 1024)) != DAT_OK) return rc;
-            hipLaunchKernelGGL(pack_weights_tiled_kernel<DAT_F32>, grid, dim3(256), lds, st, w, packed, rows, cols, ntap, cp, d->Cin, frag,
+            hipLaunchKernelGGL(pack_weights_tiled_kernel<DAT_F32>, grid, dim3(256), lds, st, w, packed, rows, cols, ntap, cp, d->Cin,
                                dgrad, scale);
         }
     } else {
         const size_t total = (size_t)ntap * cp * d->Cin;
         const int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
         if (d->dtype == DAT_BF16)
-            hipLaunchKernelGGL(pack_weights_kernel<DAT_BF16>, dim3(blocks), dim3(256), 0, st, w, packed, rows, cols, ntap, cp, d->Cin, frag,
+            hipLaunchKernelGGL(pack_weights_kernel<DAT_BF16>, dim3(blocks), dim3(256), 0, st, w, packed, rows, cols, ntap, cp, d->Cin,
                                dgrad, scale);
         else
-            hipLaunchKernelGGL(pack_weights_kernel<DAT_F32>, dim3(blocks), dim3(256), 0, st, w, packed, rows, cols, ntap, cp, d->Cin, frag,
+            hipLaunchKernelGGL(pack_weights_kernel<DAT_F32>, dim3(blocks), dim3(256), 0, st, w, packed, rows, cols, ntap, cp, d->Cin,
                                dgrad, scale);
     }
     DAT_CHECK_LAUNCH(ctx, "pack_weights");
@@ -287,7 +278,6 @@ int dat_conv3d_pack_item(dat_ctx* ctx, const dat_conv_desc* d, const float* w, i
     item->w = w; item->packed = packed; item->scale = scale;
     item->rows = rows_real; item->cols = cols_real; item->ntap = ntap;
     item->cout_pad = cout_pad_of(d); item->cin = d->Cin;
-    item->frag = weights_direct(ctx, d) ? 1 : 0;
     item->dgrad = dgrad ? 1 : 0; item->dtype = d->dtype;
     item->tile0 = 0; item->tiles_x = item->cout_pad / 32; item->cit = cit;
     return item->tiles_x * (d->Cin / cit);

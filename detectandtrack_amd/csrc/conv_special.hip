@@ -1068,7 +1068,7 @@ namespace dat_conv {
 bool ws64_eligible(const dat_ctx* ctx, const dat_conv_desc* d) {
     return ctx->dbg_ws64 && d->dtype == DAT_BF16 && d->Cin == 64 && d->Cout == 64 && d->KT == 1 && d->KH == 3 && d->KW == 3 &&
            d->stride_h == 1 && d->stride_w == 1 && d->pad_h == 1 && d->pad_w == 1 && d->pad_t == 0 && d->res_mode != 2 &&
-           d->out_tn <= 0 && d->out_cstride % 8 == 0 && weights_direct(ctx, d);
+           d->out_tn <= 0 && d->out_cstride % 8 == 0;
 }
 
 // CUs a persistent HBM-bound kernel (one block per CU) takes: all of them, or DAT_PERSIST_PCT percent (an experiment: does leaving CUs to the
@@ -1092,7 +1092,7 @@ int ctx_num_cu(dat_ctx* ctx) {
 // big-tile kernel (conv3x3_bt_kernel): what it assumes; the grid must fill the chip about twice (one block per CU at a time)
 bool bt_eligible(const dat_ctx* ctx, const dat_conv_desc* d) {
     return ctx->dbg_bt && d->dtype == DAT_BF16 && d->Cin % 64 == 0 && cout_pad_of(d) % 256 == 0 && d->Cout % 8 == 0 && d->KH == 3 && d->KW == 3 &&
-           d->stride_h == 1 && d->stride_w == 1 && d->pad_h == 1 && d->pad_w == 1 && d->out_cstride % 8 == 0 && weights_direct(ctx, d);
+           d->stride_h == 1 && d->stride_w == 1 && d->pad_h == 1 && d->pad_w == 1 && d->out_cstride % 8 == 0;
 }
 
 int bt_tile_twl(const ConvParams& p, long long* nblocks) {
@@ -1138,7 +1138,7 @@ int launch_bt(dat_ctx* ctx, hipStream_t st, ConvParams& p) {
 bool pw256_eligible(const dat_ctx* ctx, const dat_conv_desc* d) {
     return ctx->dbg_ws64 && d->dtype == DAT_BF16 && d->Cin == 64 && d->Cout == 256 && d->KT == 1 && d->KH == 1 && d->KW == 1 &&
            d->stride_h == 1 && d->stride_w == 1 && d->pad_h == 0 && d->pad_w == 0 && d->pad_t == 0 && d->out_tn <= 0 &&
-           d->out_cstride % 8 == 0 && weights_direct(ctx, d) &&
+           d->out_cstride % 8 == 0 &&
            // the kernel's 32-bit position / byte arithmetic and its row split by multiplication
            (long long)d->H * d->W >= 32 && (long long)d->H * d->W * d->W < (1ll << 32) &&
            (long long)d->frames * d->H * d->W * std::max(d->out_cstride, 64) * 2 < (1ll << 32);
@@ -1171,9 +1171,9 @@ static int lw_nsplit(const dat_conv_desc* d) {
     return ns;
 }
 
-bool pwlw_eligible(const dat_ctx* ctx, const dat_conv_desc* d) {
+bool pwlw_eligible(dat_ctx* ctx, const dat_conv_desc* d) {
     if (!(ctx->dbg_pwlw && d->dtype == DAT_BF16 && d->KT == 1 && d->KH == 1 && d->KW == 1 && d->pad_h == 0 && d->pad_w == 0 && d->pad_t == 0 &&
-          d->out_tn <= 0 && d->stride_h == d->stride_w && (d->stride_h == 1 || d->stride_h == 2) && weights_direct(ctx, d)))
+          d->out_tn <= 0 && d->stride_h == d->stride_w && (d->stride_h == 1 || d->stride_h == 2)))
         return false;
     const int kc = d->Cin / 64;
     if (d->Cin % 64 || !(kc == 1 || kc == 2 || kc == 4 || kc == 8)) return false;
@@ -1189,7 +1189,7 @@ bool pwlw_eligible(const dat_ctx* ctx, const dat_conv_desc* d) {
     if ((long long)Ho * Wo < 32 || (long long)Ho * Wo * Wo >= (1ll << 32)) return false;
     if (npos >= (1ll << 31) || (long long)d->frames * d->H * d->W >= (1ll << 31)) return false;
     // enough work per wave: 256 CUs x 4 waves, at least 2 tiles each per cout part
-    return npos / 32 >= 2ll * 4 * ctx->num_cu / ns;
+    return npos / 32 >= 2ll * 4 * ctx_num_cu(ctx) / ns;
 }
 
 template <int KC, int MBW, int NPASS>
@@ -1205,7 +1205,6 @@ static int launch_pwlw_t(dat_ctx* ctx, hipStream_t st, const PwLwParams& p, unsi
 }
 
 int launch_pwlw(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const dat_conv_desc* d) {
-    ctx_num_cu(ctx);
     PwLwParams p;
     p.x = cp.x; p.w = cp.w; p.scale = cp.scale; p.bias = cp.bias; p.res = cp.res; p.y = cp.y; p.res2 = cp.res2;
     p.npos = (unsigned)((long long)cp.frames * cp.Ho * cp.Wo);
@@ -1237,9 +1236,9 @@ int launch_pwlw(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const dat_co
 // K-streaming 1x1 kernel: K >= 512 (DAT_CONV_PWKS chunks of 64; same-box A/B of the R-50 forward, round 6: off 175.6, K >= 1024 179.0, K >= 512
 // 180.8 clips/s -- the K = 512 layers it takes from the weights-in-LDS kernel are the ones that needed two cout parts there), cout a multiple
 // of 256 after padding, enough 256-position tiles to give most CUs a block (one block per CU at a time: all 160 KB of LDS)
-bool pwks_eligible(const dat_ctx* ctx, const dat_conv_desc* d) {
+bool pwks_eligible(dat_ctx* ctx, const dat_conv_desc* d) {
     if (!(ctx->dbg_pwks > 0 && d->dtype == DAT_BF16 && d->KT == 1 && d->KH == 1 && d->KW == 1 && d->pad_h == 0 && d->pad_w == 0 && d->pad_t == 0 &&
-          d->out_tn <= 0 && d->stride_h == d->stride_w && (d->stride_h == 1 || d->stride_h == 2) && weights_direct(ctx, d)))
+          d->out_tn <= 0 && d->stride_h == d->stride_w && (d->stride_h == 1 || d->stride_h == 2)))
         return false;
     if (d->Cin % 64 || d->Cin / 64 < ctx->dbg_pwks || cout_pad_of(d) % 256) return false;
     if (d->out_cstride % 8 || d->out_cstride < d->Cout || d->out_cstride < 8) return false;
@@ -1249,11 +1248,10 @@ bool pwks_eligible(const dat_ctx* ctx, const dat_conv_desc* d) {
     if ((long long)Ho * Wo < 1 || (long long)Ho * Wo * Wo >= (1ll << 32)) return false;
     if (npos >= (1ll << 31) || (long long)d->frames * d->H * d->W >= (1ll << 31)) return false;
     const long long blocks = cdiv_ll(npos, 256) * (cout_pad_of(d) / 256);
-    return npos >= 256 && blocks * 4 >= 3ll * ctx->num_cu;
+    return npos >= 256 && blocks * 4 >= 3ll * ctx_num_cu(ctx);
 }
 
 int launch_pwks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
-    ctx_num_cu(ctx);
     PwKsParams p;
     p.x = cp.x; p.w = cp.w; p.scale = cp.scale; p.bias = cp.bias; p.res = cp.res; p.y = cp.y; p.res2 = cp.res2;
     p.npos = (unsigned)((long long)cp.frames * cp.Ho * cp.Wo);
@@ -1274,7 +1272,6 @@ int launch_pwks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
 }
 
 int launch_ws64(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
-    ctx_num_cu(ctx);
     Ws64Params p;
     p.x = cp.x; p.w = cp.w; p.scale = cp.scale; p.bias = cp.bias; p.res = cp.res; p.y = cp.y; p.zeros = cp.zeros;
     p.frames = cp.frames; p.H = cp.H; p.W = cp.W; p.out_cs = cp.out_cs; p.relu = cp.relu; p.res_mode = cp.res_mode;
@@ -1287,7 +1284,7 @@ int launch_ws64(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
         if ((ctx->dbg_ws64 == 2 && twl != 5) || (ctx->dbg_ws64 == 3 && twl != 4)) continue;   // DEBUG: DAT_CONV_WS64=2 / 3 force 8x32 / 16x16
         const int tw = 1 << twl, th = 256 >> twl;
         const long long tiles = (long long)p.frames * cdiv_ll(p.H, th) * cdiv_ll(p.W, tw);
-        const long long rounds = cdiv_ll(tiles, ctx->num_cu);
+        const long long rounds = cdiv_ll(tiles, ctx_num_cu(ctx));
         if (best_rounds < 0 || rounds < best_rounds) { best_rounds = rounds; best_twl = twl; best_tiles = tiles; }
     }
     const int tw = 1 << best_twl, th = 256 >> best_twl;

@@ -32,9 +32,8 @@ struct dat_ctx {
     // Launch-plan state of THIS context (no process globals: N contexts / N devices per process are independent,
     // SURVEY.md 8b "thread-safe per dat_ctx").  The debug knobs are read from the environment once, at dat_ctx_create.
     int force_bp, force_ks;                 // dat_conv3d_tune_plan / DAT_CONV_BP, DAT_CONV_KSPLIT; 0 = makespan model
-    int dbg_tw_log2, dbg_ablate, dbg_lds_pad, dbg_tps3;   // DAT_CONV_TW_LOG2 (-1 = off), DAT_CONV_ABLATE, DAT_CONV_LDS_PAD, DAT_CONV_TPS
-    int dbg_pack_simple;                    // DAT_PACK_SIMPLE (default 0): element-wise weight packing instead of the LDS-tiled kernel
-    int dbg_linear;                         // DAT_CONV_LINEAR (default 1): linear position tiling of small maps (RoI-head 3x3 convs on 14 x 14 maps); 5 = also the 320-position one-block-per-CU tiles
+    int dbg_ablate;                         // DAT_CONV_ABLATE (default 0): DEBUG timing ablations of the conv kernels (wrong results)
+    int dbg_linear;                         // DAT_CONV_LINEAR (default 1): linear position tiling of small maps (RoI-head 3x3 convs on 14 x 14 maps); 0 = 2-D tiles only
     int dbg_order;                          // DAT_CONV_ORDER (default 0): block order of the implicit-GEMM conv inside an XCD's queue, 0 patch-sharing, 1 weight-stationary (less fabric traffic, slower)
     int dbg_persist_pct;                    // DAT_PERSIST_PCT (default 100): percent of the CUs the persistent HBM-bound conv kernels take (experiment)
     int dbg_bt_min;                         // DAT_CONV_BT_MIN (default 390): the big-tile kernel takes grids of at least this many hundredths of a round of the CUs
@@ -45,18 +44,14 @@ struct dat_ctx {
     int dbg_wgrad_direct;                   // DAT_WGRAD_DIRECT (default 1): bf16 weight gradients straight from the NDHWC tensors (transposing LDS reads), no re-pack passes
     int dbg_ablate_wgrad;                   // DAT_WGRAD_ABLATE (default 0): DEBUG timing ablations of the nine-tap weight-gradient kernel (wrong results)
     int dbg_wgrad_sub;                      // DAT_WGRAD_SUB (default 2): 2 = eight-wave blocks of the nine-tap weight-gradient kernel (two K ranges per block, added through LDS)
-    int dbg_wgrad_ilv;                      // DAT_WGRAD_ILV (default 1): 1 = LDS-DMA pieces of the next-but-one chunk issued between the MFMA groups of the current one
-    int dbg_wgrad_xcd;                      // DAT_WGRAD_XCD (default 0): XCD-aware block order of wgrad_dma9_kernel (consecutive logical blocks on one XCD) -- measured neutral (round 6: R-50 iteration 20.22 vs 20.39 ms, R-18 14.60 vs 14.56)
     int dbg_pw_xcd;                         // DAT_CONV_PW_XCD (default 1): the cout parts / cout blocks of the 1x1 kernels (conv1x1_lw / conv1x1_ks) that read one input tile share an XCD
-    int dbg_wgrad_dma;                      // DAT_WGRAD_DMA (default 1): nine-tap weight gradient with LDS-DMA operand staging (three stages) instead of register staging
     int dbg_wgrad_ks;                       // DAT_WGRAD_KS (default 0 = heuristic): forced K split of the nine-tap direct weight-gradient kernel
     int dbg_wgrad_pw;                       // DAT_WGRAD_PW (default 1): eight-wave 64 K-accumulator kernel for pointwise weight gradients (0: the 128 x 128 per-tap kernel; 10 / 20 / 40: forced tile shape)
     int dbg_kps_sep;                        // DAT_KPS_DECODE_SEP (default 1): separable heatmap decode (horizontal pass per 64-column strip in LDS); 0 = the per-pixel 4 x 4 kernel
     int dbg_ws_poison;                      // DAT_WS_POISON (default 0): a grown scratch buffer is filled with 0xFF (tests: no kernel may rely on fresh hipMalloc pages reading as zero)
     int dbg_roi_fold;                       // DAT_ROI_BWD_FOLD (default 1): RoIAlign backward folds a bin's samples into one weight per distinct pixel before the atomics
     int num_cu;                             // compute units of the device (persistent-kernel grids)
-    int dbg_ntap;                           // DAT_CONV_NTAP (default 1): unrolled-tap variants of the WD kernels (3x3 stride 1, 1x1)
-    int dbg_wd;                             // DAT_CONV_WD (default 2): tiles read their weights straight from global memory (1: only the 128-channel ones)
+    int dbg_ntap;                           // DAT_CONV_NTAP (default 1): unrolled-tap variants of the implicit-GEMM kernel (3x3 stride 1, 1x1)
     // kernels whose dynamic-LDS limit was already raised on this context's device (the attribute is per device)
     std::unordered_set<const void*> lds_attr_done;
 };

@@ -389,8 +389,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad_direct_kernel(const WgradDirectPa
 // ROWS a spatial tap is a row offset: a block stages the g rows of an 8 x 8 patch of output positions (64 k) and the 10 x 10 patch of
 // input positions around it ONCE and accumulates all nine (kh, kw) taps from it -- the B fragment of tap (kh, kw) is the same
 // per-lane address + (kh * 10 + kw) rows, an immediate.  Block = (64 co x 64 ci) x one temporal tap, a wave = 32 x 32 x 9 taps (144
-// accumulator registers); K = frames x patches, split across blocks.  Row pitch 192 B (64 channels + 64 B): the four rows of a
-// transposing read and the neighbouring 16-column group fall on distinct banks.  Operand traffic per layer: 9 x less.
+// accumulator registers); K = frames x patches, split across blocks.  Operand traffic per layer: 9 x less.
 struct Wgrad9Params {
     const char* g;
     const char* x;
@@ -404,155 +403,16 @@ struct Wgrad9Params {
     int ablate;           // DEBUG (DAT_WGRAD_ABLATE): 1 no global loads, 2 no LDS fragment reads / MFMAs, 4 no final atomics / stores
     const char* zeros;    // >= 16 zero bytes in global memory (LDS-DMA source of halo / out-of-range pieces)
     int atomic;           // add into G with atomics (K split, or a caller-owned accumulator) instead of storing
-    int xcd;              // XCD-aware block order (DAT_WGRAD_XCD): consecutive logical blocks share an XCD's L2
 };
 
-constexpr int W9_PITCH = 192;
-constexpr int W9_GT = 64 * W9_PITCH;          // g tile: 64 positions
-constexpr int W9_XT = 100 * W9_PITCH;         // x patch: 10 x 10 positions
-constexpr int W9_STAGE = W9_GT + W9_XT + 512; // (+ pad: the 12-k row reads of the last patch rows reach two rows past the patch)
-
-__device__ __forceinline__ uint4 w9_tr_frag(const char* base) {
-    typedef __attribute__((address_space(3))) wd_v4s* lp_t;
-    const wd_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(base));
-    const wd_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(base + 4 * W9_PITCH));
-    uint2 l = __builtin_bit_cast(uint2, lo), h = __builtin_bit_cast(uint2, hi);
-    return make_uint4(l.x, l.y, h.x, h.y);
-}
-// one transposing read: 4 consecutive k (patch rows) of this lane's column
-__device__ __forceinline__ uint2 w9_tr4(const char* base) {
-    typedef __attribute__((address_space(3))) wd_v4s* lp_t;
-    return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(base)));
-}
-
-__global__ __launch_bounds__(NT, 2) void wgrad_direct9_kernel(const Wgrad9Params p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];     // 2 stages x (g tile, x patch)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wave_m = wave & 1, wave_n = wave >> 1;
-    unsigned bid = blockIdx.x;
-    const int kt = bid % p.KT; bid /= p.KT;
-    const int ci_t = bid % p.n_ci_tiles; bid /= p.n_ci_tiles;
-    const int co_t = bid % p.n_co_tiles;
-    const int split = bid / p.n_co_tiles;
-    const unsigned per_frame = (unsigned)(p.tiles_h * p.tiles_w);
-    const unsigned nchunks = (unsigned)(p.f_end - p.f_begin) * per_frame;
-    const unsigned c_lo = (unsigned)((unsigned long long)nchunks * split / p.ksplit), c_hi = (unsigned)((unsigned long long)nchunks * (split + 1) / p.ksplit);
-
-    // staging: 16-byte piece pc (8 per 64-channel row); g: rows r0 + 32 i (i < 2), x: patch rows r0 + 32 i (i < 4, < 100)
-    const int pc = tid & 7, r0 = tid >> 3;
-    const bool g_col_ok = co_t * 64 + pc * 8 < p.g_cs, x_col_ok = ci_t * 64 + pc * 8 < p.x_cs;
-    uint4 gqA[2], xqA[4], gqB[2], xqB[4];        // two register sets: the loads of chunk c + 2 are issued while chunk c computes
-#define W9_FETCH(CH_, GQ_, XQ_)                                                                                                   \
-    {                                                                                                                   \
-        const unsigned fr_ = (unsigned)(CH_) / per_frame, tl_ = (unsigned)(CH_) - fr_ * per_frame;                       \
-        const int f_ = p.f_begin + (int)fr_;                                                                            \
-        const int ty_ = (int)(tl_ / (unsigned)p.tiles_w), tx_ = (int)tl_ - ty_ * p.tiles_w;                             \
-        const int clip_ = f_ / p.T, t_ = f_ - clip_ * p.T, ti_ = t_ + kt - p.pt;                                        \
-        const bool tin_ = ti_ >= 0 && ti_ < p.T;                                                                        \
-        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                              \
-            const int r_ = r0 + 32 * i_, oy_ = ty_ * 8 + (r_ >> 3), ox_ = tx_ * 8 + (r_ & 7);                           \
-            GQ_[i_] = make_uint4(0, 0, 0, 0);                                                                            \
-            if (g_col_ok && tin_ && oy_ < p.H && ox_ < p.W)                                                             \
-                GQ_[i_] = *(const uint4*)(p.g + ((((size_t)f_ * p.H + oy_) * p.W + ox_) * (unsigned)p.g_cs + (unsigned)(co_t * 64 + pc * 8)) * 2u); \
-        }                                                                                                               \
-        _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                              \
-            const int r_ = r0 + 32 * i_, py_ = r_ / 10, px_ = r_ - py_ * 10;                                            \
-            const int iy_ = ty_ * 8 + py_ - 1, ix_ = tx_ * 8 + px_ - 1;                                                 \
-            XQ_[i_] = make_uint4(0, 0, 0, 0);                                                                            \
-            if (x_col_ok && tin_ && r_ < 100 && iy_ >= 0 && iy_ < p.H && ix_ >= 0 && ix_ < p.W)                         \
-                XQ_[i_] = *(const uint4*)(p.x + ((((size_t)(clip_ * p.T + ti_) * p.H + iy_) * p.W + ix_) * (unsigned)p.x_cs + (unsigned)(ci_t * 64 + pc * 8)) * 2u); \
-        }                                                                                                               \
-    }
-#define W9_STAGE_WRITE(BUF_, GQ_, XQ_)                                                                                            \
-    {                                                                                                                   \
-        char* gd_ = smem + (BUF_) * W9_STAGE;                                                                           \
-        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) *(uint4*)(gd_ + (r0 + 32 * i_) * W9_PITCH + pc * 16) = GQ_[i_];  \
-        _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                                \
-            if (r0 + 32 * i_ < 100) *(uint4*)(gd_ + W9_GT + (r0 + 32 * i_) * W9_PITCH + pc * 16) = XQ_[i_];             \
-    }
-    // fragment addressing.  g tile (rows = k = oy * 8 + ox): group G = lane >> 4 reads rows k0 + (G >> 1) * 8 [+4], columns (G & 1) * 16,
-    // lane i of the group row i >> 2, columns 4 (i & 3).  x patch: k -> patch row (oy + kh) * 10 + ox + kw; the 8 k of a fragment
-    // half are ONE output row (oy = 2 ks + (G >> 1)), so its two 4-k groups are patch rows ... + ox (0..3 | 4..7): +4 rows again.
-    const int grp = lane >> 4, li = lane & 15;
-    const int g_off = ((grp >> 1) * 8 + (li >> 2)) * W9_PITCH + ((grp & 1) * 16 + (li & 3) * 4) * 2 + (wave_m * 32) * 2;
-    const int x_off = ((grp >> 1) * 10 + (li >> 2)) * W9_PITCH + ((grp & 1) * 16 + (li & 3) * 4) * 2 + (wave_n * 32) * 2;
-    f32x16_t acc[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-    auto compute = [&](int buf) __attribute__((always_inline)) {
-        const char* gb = smem + buf * W9_STAGE + g_off;
-        const char* xb = smem + buf * W9_STAGE + W9_GT + x_off;
-        if (p.ablate & 2) return;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {            // 16 k = output rows 2 ks, 2 ks + 1 of the patch
-            const uint4 a = w9_tr_frag(gb + ks * 16 * W9_PITCH);
-#pragma unroll
-            for (int kh = 0; kh < 3; ++kh) {
-                // the three kw taps read three 8-wide windows of the SAME 10-wide patch row: 12 k (three 4-k transposing reads; the last
-                // two are past the row, never used) are fetched once and the windows cut out of the registers (LDS reads per MFMA 2.2 -> 1.2)
-                const char* rb = xb + ((2 * ks + kh) * 10) * W9_PITCH;
-                const uint2 q0 = w9_tr4(rb), q1 = w9_tr4(rb + 4 * W9_PITCH), q2 = w9_tr4(rb + 8 * W9_PITCH);
-                const uint4 b0 = make_uint4(q0.x, q0.y, q1.x, q1.y);
-                const uint4 b2 = make_uint4(q0.y, q1.x, q1.y, q2.x);
-                const uint4 b1 = make_uint4(__builtin_amdgcn_alignbyte(q0.y, q0.x, 2), __builtin_amdgcn_alignbyte(q1.x, q0.y, 2),
-                                            __builtin_amdgcn_alignbyte(q1.y, q1.x, 2), __builtin_amdgcn_alignbyte(q2.x, q1.y, 2));
-                MmaT<DAT_BF16>::step(a, b0, acc[kh * 3 + 0]);
-                MmaT<DAT_BF16>::step(a, b1, acc[kh * 3 + 1]);
-                MmaT<DAT_BF16>::step(a, b2, acc[kh * 3 + 2]);
-            }
-        }
-    };
-    // Prefetch distance TWO chunks (ablation, tools/probes/wgrad_bench.py ablate: loads, MFMAs and the final atomics each cost about a
-    // quarter of a launch and did not overlap -- a chunk's MFMA phase (~0.5 us) is shorter than a memory round trip): chunk c computes
-    // from LDS, chunk c + 1 is in registers on its way to the other LDS buffer, chunk c + 2 is being requested.
-    const bool ld = !(p.ablate & 1);
-    if (c_lo < c_hi) {
-        W9_FETCH(c_lo, gqA, xqA);
-        W9_STAGE_WRITE(0, gqA, xqA);
-        if (c_lo + 1 < c_hi && ld) W9_FETCH(c_lo + 1, gqA, xqA);
-    }
-    __syncthreads();
-    for (unsigned c = c_lo; c < c_hi; c += 2) {
-        if (c + 2 < c_hi && ld) W9_FETCH(c + 2, gqB, xqB);
-        compute(0);
-        if (c + 1 < c_hi) W9_STAGE_WRITE(1, gqA, xqA);
-        __syncthreads();
-        if (c + 1 >= c_hi) break;
-        if (c + 3 < c_hi && ld) W9_FETCH(c + 3, gqA, xqA);
-        compute(1);
-        if (c + 2 < c_hi) W9_STAGE_WRITE(0, gqB, xqB);
-        __syncthreads();
-    }
-#undef W9_FETCH
-#undef W9_STAGE_WRITE
-    const int khalf = lane >> 5;
-    const int ci = ci_t * 64 + wave_n * 32 + (lane & 31);
-    if (ci >= p.Cin || (p.ablate & 4)) return;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        float* Gt = p.G + (size_t)(kt * 9 + t) * p.Cout * p.Cin;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int co = co_t * 64 + wave_m * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-            if (co >= p.Cout) continue;
-            if (p.atomic) atomicAdd(Gt + (size_t)co * p.Cin + ci, acc[t][r]);
-            else Gt[(size_t)co * p.Cin + ci] = acc[t][r];
-        }
-    }
-}
-
-// ---- the same tile with the operands brought in by LDS-DMA (round 3, late) -------------------------------------------------------
-// wgrad_direct9_kernel stages its operands through registers: two chunks in flight cost 48 registers next to 144 accumulators, and the
-// counters (profiles/r03/train_r18/pmc_mfma.csv) show the MFMA pipe busy 21 % of the time: a 64-position chunk is ~0.5 us of MFMAs
-// behind a 20.8-KB operand fetch with ~2 us of loaded latency.  Here `global_load_lds_dwordx4` writes the 128-byte rows straight into
+// ---- the operands are brought in by LDS-DMA (round 3, late) -----------------------------------------------------------------------
+// Staged through registers (rounds 1-3), two chunks in flight cost 48 registers next to 144 accumulators, and the counters
+// (profiles/r03/train_r18/pmc_mfma.csv) showed the MFMA pipe busy 21 % of the time: a 64-position chunk is ~0.5 us of MFMAs behind a
+// 20.8-KB operand fetch with ~2 us of loaded latency.  Here `global_load_lds_dwordx4` writes the 128-byte rows straight into
 // one of THREE LDS stages (no staging registers, no ds_write pass): chunk c computes while chunks c + 1 and c + 2 are in flight.
 //   * stage = 192 rows x 128 B (64 g rows, 100 patch rows, 28 spare rows that make 24 one-KiB DMA pieces: every wave issues exactly
 //     six per chunk, so `s_waitcnt vmcnt(6)` at the top of an iteration means "my pieces of THIS chunk have landed");
-//   * rows are contiguous (the DMA writes lane * 16 B), so the bank spread the 192-byte pitch gave the transposing reads comes from a
-//     swizzle instead: 16-byte piece p of row r sits in slot p ^ 4 * bit1(r).  A transposing read touches four consecutive rows x 64 B per
+//   * rows are contiguous (the DMA writes lane * 16 B), so the bank spread of the transposing reads comes from a swizzle: 16-byte piece p of row r sits in slot p ^ 4 * bit1(r).  A transposing read touches four consecutive rows x 64 B per
 //     half wave: rows r .. r + 3 then start at banks 0 / 32 / 16 / 48 -- all 64 banks once.  The swizzle is applied by choosing which
 //     global piece a lane fetches; on the read side it is a per-lane constant XOR of 64 (g tile), toggled by kh == 1 for the patch rows
 //     ((2 ks + kh) * 10 flips bit 1 of the row exactly when kh == 1).
@@ -562,12 +422,12 @@ constexpr int W9D_STAGES = 3;
 // SUB = 2 (round 4): one block of EIGHT waves per CU instead of two blocks of four -- two sub-blocks with their own K range and their own three
 // stages work on the same (co, ci, kt) tile and add their accumulators through LDS before the atomics.  The grid is then one block per CU (the
 // ~384 four-wave blocks left half of the CUs with one block and half with two) and a tile's partial sums reach memory from half as many blocks.
-// ILV = 1 (round 4, the default): the six LDS-DMA pieces of chunk c + 2 are issued BETWEEN the MFMA groups of chunk c (one piece before every other
-// group of three MFMAs) instead of in one burst behind the barrier: a piece costs its wave 60-185 cycles of issue (MI355X_MICROARCH.md), and
+// The six LDS-DMA pieces of chunk c + 2 are issued BETWEEN the MFMA groups of chunk c (round 4: one piece before every other group of
+// three MFMAs) instead of in one burst behind the barrier: a piece costs its wave 60-185 cycles of issue (MI355X_MICROARCH.md), and
 // behind the barrier every wave of the CU pays them at the same time with no MFMA in flight.  Same box, per layer: res3 0.152 -> 0.147 ms,
 // res4 0.163 -> 0.161, res5 0.221 -> 0.216, P2 0.284 -> 0.274; letting the two sub-blocks take turns (one issues in the first half of the chunk,
 // the other in the second) needs a branch per group, which cuts the chunk's MFMA schedule into basic blocks: 1-2 % slower than the burst.
-template <int SUB, int ILV>
+template <int SUB>
 __global__ __launch_bounds__(NT * SUB, SUB == 1 ? 2 : 1) void wgrad_dma9_kernel(const Wgrad9Params p) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     typedef __attribute__((address_space(3))) void* lptr_t;
@@ -576,15 +436,6 @@ __global__ __launch_bounds__(NT * SUB, SUB == 1 ? 2 : 1) void wgrad_dma9_kernel(
     const int sub = SUB == 1 ? 0 : wave_all >> 2, wave = wave_all & 3;
     const int wave_m = wave & 1, wave_n = wave >> 1;
     unsigned bid = blockIdx.x;
-    if (p.xcd) {
-        // Blocks go to the XCDs round-robin (block i -> XCD i % 8), and the blocks that read the same operand chunks at the same time are the
-        // (kt, ci tile) / (kt, co tile) neighbours of one K range: consecutive ids.  Unmapped, the 12 readers of a g chunk (4 ci tiles x 3 kt) sit
-        // on 8 different L2s and the chunk crosses the fabric ~7 times; mapped (the bijection of conv3d_igemm_kernel), XCD x runs the
-        // consecutive logical ids [x * n / 8, (x + 1) * n / 8).
-        const unsigned nx = 8, q = gridDim.x / nx, r = gridDim.x % nx;
-        const unsigned xcd = bid % nx, k = bid / nx;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
     const int kt = bid % p.KT; bid /= p.KT;
     const int ci_t = bid % p.n_ci_tiles; bid /= p.n_ci_tiles;
     const int co_t = bid % p.n_co_tiles;
@@ -651,16 +502,17 @@ __global__ __launch_bounds__(NT * SUB, SUB == 1 ? 2 : 1) void wgrad_dma9_kernel(
         //  wait + barrier at the top of the loop is the ordering this pipeline needs)
         // (M0 is written without telling the compiler: nothing else in this kernel uses it -- no other LDS-DMA, no s_movrel)
         const unsigned lds_at = (unsigned)(size_t)(lptr_t)(a.dst0 + u * 4096);
-        if (ILV)    // no memory clobber: the fragment reads of the chunk being computed may be scheduled across the piece (another stage)
-            asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(lds_at));
-        else
-            asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(lds_at) : "memory");
+        // (no memory clobber: the fragment reads of the chunk being computed may be scheduled across the piece, which targets another stage)
+        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(lds_at));
     };
     auto issue = [&](unsigned ch, int stage) __attribute__((always_inline)) {
         const ChunkAt a = chunk_at(ch, stage);
         static_for(std::make_integer_sequence<int, 6>{}, [&](auto u_c) __attribute__((always_inline)) { issue_piece(a, u_c); });
     };
-    // fragment addressing (see wgrad_direct9_kernel), rows 128 B apart, the piece swizzle as a per-lane XOR
+    // fragment addressing.  g tile (rows = k = oy * 8 + ox): group G = lane >> 4 reads rows k0 + (G >> 1) * 8 [+4], columns (G & 1) * 16,
+    // lane i of the group row i >> 2, columns 4 (i & 3).  x patch: k -> patch row (oy + kh) * 10 + ox + kw; the 8 k of a fragment
+    // half are ONE output row (oy = 2 ks + (G >> 1)), so its two 4-k groups are patch rows ... + ox (0..3 | 4..7): +4 rows again.
+    // Rows are 128 B apart, the piece swizzle is a per-lane XOR.
     const int grp = lane >> 4, li = lane & 15;
     const int g_row = (grp >> 1) * 8 + (li >> 2), x_row = (grp >> 1) * 10 + (li >> 2);
     const int g_off = g_row * 128 + ((((grp & 1) * 16 + (li & 3) * 4) * 2 + wave_m * 64) ^ (((g_row >> 1) & 1) << 6));
@@ -675,7 +527,7 @@ __global__ __launch_bounds__(NT * SUB, SUB == 1 ? 2 : 1) void wgrad_dma9_kernel(
     auto tr4 = [&](const char* a) __attribute__((always_inline)) { return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)a)); };
     auto compute = [&](int stage, const ChunkAt& nx) __attribute__((always_inline)) {
         if (p.ablate & 2) {
-            if (ILV) static_for(std::make_integer_sequence<int, 6>{}, [&](auto u_c) __attribute__((always_inline)) { issue_piece(nx, u_c); });
+            static_for(std::make_integer_sequence<int, 6>{}, [&](auto u_c) __attribute__((always_inline)) { issue_piece(nx, u_c); });
             return;
         }
         const char* sb = sm + stage * W9D_STAGE;
@@ -687,7 +539,7 @@ __global__ __launch_bounds__(NT * SUB, SUB == 1 ? 2 : 1) void wgrad_dma9_kernel(
                 constexpr int kh = decltype(kh_c)::value, grp_i = ks * 3 + kh;      // MFMA group 0..11 of the chunk
                 const char* rb = sb + (kh == 1 ? x_off1 : x_off0) + ((2 * ks + kh) * 10) * 128;
                 const uint2 q0 = tr4(rb), q1 = tr4(rb + 4 * 128), q2 = tr4(rb + 8 * 128);
-                if (ILV && grp_i % 2 == 0) issue_piece(nx, std::integral_constant<int, (grp_i / 2) % 6>{});    // every other group: no branch in the chunk
+                if (grp_i % 2 == 0) issue_piece(nx, std::integral_constant<int, (grp_i / 2) % 6>{});    // every other group: no branch in the chunk
                 const uint4 b0 = make_uint4(q0.x, q0.y, q1.x, q1.y);
                 const uint4 b2 = make_uint4(q0.y, q1.x, q1.y, q2.x);
                 const uint4 b1 = make_uint4(__builtin_amdgcn_alignbyte(q0.y, q0.x, 2), __builtin_amdgcn_alignbyte(q1.x, q0.y, 2),
@@ -710,7 +562,6 @@ __global__ __launch_bounds__(NT * SUB, SUB == 1 ? 2 : 1) void wgrad_dma9_kernel(
             asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
             const int nstage = stage == 0 ? 2 : stage - 1;      // (c + 2) % 3 == (c - 1) % 3
             const ChunkAt nx = chunk_at(c + 2, nstage);
-            if (!ILV) static_for(std::make_integer_sequence<int, 6>{}, [&](auto u_c) __attribute__((always_inline)) { issue_piece(nx, u_c); });
             compute(stage, nx);
             stage = stage == 2 ? 0 : stage + 1;
         }
@@ -1503,7 +1354,7 @@ static int wgrad_impl(dat_ctx* ctx, dat_stream s_, const dat_conv_desc* d, const
     if (wgrad_direct_eligible(ctx, d, g_cstride)) {
         float* Gt = (float*)workspace;
         if (d->KH == 3 && d->KW == 3 && s == 1 && d->pad_h == 1 && d->pad_w == 1 && (ctx->dbg_wgrad_direct & 2) == 0) {
-            // nine spatial taps from one staged patch (wgrad_direct9_kernel)
+            // nine spatial taps from one staged patch (wgrad_dma9_kernel)
             Wgrad9Params q;
             memset(&q, 0, sizeof(q));
             q.g = (const char*)g; q.x = (const char*)x; q.G = Gt;
@@ -1521,7 +1372,7 @@ static int wgrad_impl(dat_ctx* ctx, dat_stream s_, const dat_conv_desc* d, const
             const long long tiles = (long long)d->KT * q.n_co_tiles * q.n_ci_tiles;
             const long long nchunks = (long long)(q.f_end - q.f_begin) * q.tiles_h * q.tiles_w;
             // K split (per-layer sweep of the LDS-DMA kernel, tools/probes/wgrad_bench.py, blocks = tiles x ks): ~384 blocks -- 1.5 per CU --
-            // beat the 640 (1.25 rounds of the 512 slots) the register-staged kernel liked: res3 (12 tiles) ks 53 -> 32 0.181 -> 0.157 ms,
+            // beat the 640 (1.25 rounds of the 512 slots) the register-staged kernel of rounds 1-3 liked: res3 (12 tiles) ks 53 -> 32 0.181 -> 0.157 ms,
             // res4 / P3 (48) 13 -> 8 0.192 -> 0.167 / 0.136 -> 0.109, P2 13 -> 8 0.328 -> 0.304; fewer, longer blocks mean fewer atomics and
             // fewer pipeline fills.  Layers with many tiles (res5: 192) want two blocks per CU again: ks 3 -> 4 0.224 -> 0.205.
             // Eight-wave blocks (DAT_WGRAD_SUB = 2, the default; round 4): one block per CU, two K ranges per block -- ks counts the RANGES, so it
@@ -1529,8 +1380,8 @@ static int wgrad_impl(dat_ctx* ctx, dat_stream s_, const dat_conv_desc* d, const
             // 0.157, P2 0.306 -> 0.274, P3 0.109 -> 0.104).  Layers with more tiles than half the CUs (res5: 192) take ONE block per tile with
             // its two ranges -- no K split across blocks, so no contended atomics at all (plain stores outside the deferred-finish mode):
             // 0.210 -> 0.192 ms against the four-wave blocks' ks = 4 (768 blocks, 113 MB of atomics); two blocks per tile: 0.230.
-            const int sub = ctx->dbg_wgrad_dma && ctx->dbg_wgrad_sub >= 2 ? 2 : 1;
-            long long ks = ctx->dbg_wgrad_dma ? (tiles <= 96 ? (384 + tiles - 1) / tiles : (768 + tiles - 1) / tiles) : 640 / tiles;
+            const int sub = ctx->dbg_wgrad_sub >= 2 ? 2 : 1;
+            long long ks = tiles <= 96 ? (384 + tiles - 1) / tiles : (768 + tiles - 1) / tiles;
             if (sub == 2) ks = tiles <= 128 ? 2 * (256 / tiles) : 2;
             if (ks > nchunks / 4) ks = nchunks / 4;             // at least 4 patches per block
             if (ctx->dbg_wgrad_ks > 0) ks = ctx->dbg_wgrad_ks;
@@ -1544,26 +1395,14 @@ static int wgrad_impl(dat_ctx* ctx, dat_stream s_, const dat_conv_desc* d, const
             if (q.atomic && !acc_mode && hipMemsetAsync(Gt, 0, g_elems * sizeof(float), st) != hipSuccess)
                 DAT_FAIL(ctx, DAT_ERR_LAUNCH, "conv3d_wgrad: memset failed");
             q.zeros = (const char*)ctx->zeros;
-            q.xcd = ctx->dbg_wgrad_xcd != 0;
-            const bool ilv = ctx->dbg_wgrad_ilv != 0;
-            const void* fn;
             if (sub2) {
                 const size_t lds = 2 * W9D_STAGES * W9D_STAGE;
-                const dim3 grid((unsigned)(tiles * ks / 2)), blk(2 * NT);
-                fn = ilv ? (const void*)wgrad_dma9_kernel<2, 1> : (const void*)wgrad_dma9_kernel<2, 0>;
-                if (dat_ensure_lds(ctx, fn, lds) != DAT_OK) return DAT_ERR_LAUNCH;
-                if (ilv) hipLaunchKernelGGL((wgrad_dma9_kernel<2, 1>), grid, blk, lds, st, q);
-                else hipLaunchKernelGGL((wgrad_dma9_kernel<2, 0>), grid, blk, lds, st, q);
-            } else if (ctx->dbg_wgrad_dma) {   // operands by LDS-DMA into three stages (DAT_WGRAD_DMA, default 1)
-                const size_t lds = W9D_STAGES * W9D_STAGE;
-                const dim3 grid((unsigned)(tiles * ks)), blk(NT);
-                fn = ilv ? (const void*)wgrad_dma9_kernel<1, 1> : (const void*)wgrad_dma9_kernel<1, 0>;
-                if (dat_ensure_lds(ctx, fn, lds) != DAT_OK) return DAT_ERR_LAUNCH;
-                if (ilv) hipLaunchKernelGGL((wgrad_dma9_kernel<1, 1>), grid, blk, lds, st, q);
-                else hipLaunchKernelGGL((wgrad_dma9_kernel<1, 0>), grid, blk, lds, st, q);
+                if (dat_ensure_lds(ctx, (const void*)wgrad_dma9_kernel<2>, lds) != DAT_OK) return DAT_ERR_LAUNCH;
+                hipLaunchKernelGGL((wgrad_dma9_kernel<2>), dim3((unsigned)(tiles * ks / 2)), dim3(2 * NT), lds, st, q);
             } else {
-                if (dat_ensure_lds(ctx, (const void*)wgrad_direct9_kernel, 2 * W9_STAGE) != DAT_OK) return DAT_ERR_LAUNCH;
-                hipLaunchKernelGGL(wgrad_direct9_kernel, dim3((unsigned)(tiles * ks)), dim3(NT), 2 * W9_STAGE, st, q);
+                const size_t lds = W9D_STAGES * W9D_STAGE;
+                if (dat_ensure_lds(ctx, (const void*)wgrad_dma9_kernel<1>, lds) != DAT_OK) return DAT_ERR_LAUNCH;
+                hipLaunchKernelGGL((wgrad_dma9_kernel<1>), dim3((unsigned)(tiles * ks)), dim3(NT), lds, st, q);
             }
             if (!acc_mode)
                 hipLaunchKernelGGL(wgrad_finish_kernel, dim3(grid_for((long long)g_elems, 256)), dim3(256), 0, st, (const float*)Gt, scale, dW,

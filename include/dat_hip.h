@@ -131,7 +131,7 @@ typedef struct dat_pack_item {
     const float* w;
     void* packed;
     const float* scale;
-    int rows, cols, ntap, cout_pad, cin, frag, dgrad, dtype;
+    int rows, cols, ntap, cout_pad, cin, dgrad, dtype;
     int tile0, tiles_x;
     int cit;                 /* input channels per block tile (set by dat_conv3d_pack_item: 64 / 32 / 16 by tap count) */
 } dat_pack_item;

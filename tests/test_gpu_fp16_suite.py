@@ -26,7 +26,7 @@ MUST_PASS = [
     K + 'test_conv3d[heads_100x14x14_c512-bf16]',
     K + 'test_conv3x3_c64_weights_stationary[res2_like]',           # ws64
     K + 'test_conv1x1_k64_c256_weights_stationary[many_tiles]',     # 256-channel pointwise
-    K + 'test_conv3x3_linear_320_position_tiles',
+    K + 'test_conv3x3_linear_tiles_100_maps_512_channels',
     K + 'test_conv3x3x3_linear_strips_per_frame[2x4x24x42_128_256-bp128_ks3]',
     K + 'test_conv3x3x3_linear_strips_with_key_frame_outputs',
     K + 'test_conv3x3_big_tile[3x3x3_ragged_16x16]',

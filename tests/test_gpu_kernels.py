@@ -195,7 +195,7 @@ CONV_CASES = [
     ('heads_7x7', 9, 1, 7, 7, 64, 128, (1, 3, 3), (1, 1), True, 0, False),
     ('heads_14x14_many', 40, 1, 14, 14, 64, 128, (1, 3, 3), (1, 1), False, 0, True),
     ('heads_5x9_odd', 11, 1, 5, 9, 64, 192, (1, 3, 3), (1, 1), True, 1, False),
-    # 308 blocks of 256 positions > 256 CUs, 248 blocks of 320 positions: the one-block-per-CU 320-position linear tiles
+    # a grid just above one block per CU: 308 linear tiles of 256 positions
     ('heads_100x14x14_c512', 100, 1, 14, 14, 64, 512, (1, 3, 3), (1, 1), True, 1, True),
     # temporal taps on maps that 2-D tiles cover badly (res5 / res4 of the 3-D bodies): one linear strip per frame, two clips
     ('res5_like_24x42', 2, 4, 24, 42, 128, 256, (3, 3, 3), (1, 1), True, 1, True),
@@ -421,9 +421,9 @@ def _in_fresh_context(env, fn):
                 os.environ[k] = v
 
 
-def test_conv3x3_linear_320_position_tiles(ops):
-    """The opt-in 320-position linear tiles (DAT_CONV_LINEAR=5; a grid just above one block per CU: 100 maps of 14 x 14, 512 output
-    channels = 308 blocks of 256 positions, 248 of 320) against torch and bit for bit against the 2-D tiling (DAT_CONV_LINEAR=0)."""
+def test_conv3x3_linear_tiles_100_maps_512_channels(ops):
+    """The linear tiles of the default dispatch on a grid just above one block per CU (100 maps of 14 x 14, 512 output channels = 308
+    blocks of 256 positions) against torch and bit for bit against the 2-D tiling (DAT_CONV_LINEAR=0)."""
     rs = np.random.RandomState(5)
     q = nm.q16
     N, H, W, Cin, Cout = 100, 14, 14, 64, 512
@@ -435,12 +435,12 @@ def test_conv3x3_linear_320_position_tiles(ops):
     layer = ops.ConvLayer(_dev(w), None, _dev(bias), stride=(1, 1), pads=(0, 1, 1), relu=True, dtype=1)
     xd, rd = ops.to_ndhwc(_dev(x), 1), ops.to_ndhwc(_dev(res), 1, layer.cstride)
     run = lambda: layer(xd, T=1, residual=rd, res_mode=1)
-    y320 = _in_fresh_context({'DAT_CONV_LINEAR': '5'}, run)
+    y_lin = _in_fresh_context({}, run)
     y2d = _in_fresh_context({'DAT_CONV_LINEAR': '0'}, run)
-    assert torch.equal(y320, y2d)
-    got = ops.to_ncdhw(y320, 1, N, Cout, 1).cpu().numpy()
+    assert torch.equal(y_lin, y2d)
+    got = ops.to_ncdhw(y_lin, 1, N, Cout, 1).cpu().numpy()
     assert np.abs(got - ref).max() < 3e-2 * max(1.0, np.abs(ref).max() / 4)
-    _bound(got, (x, w, None, bias, res, (1, 1), (0, 1, 1), True), Cin, (1, 3, 3), 'linear-320')
+    _bound(got, (x, w, None, bias, res, (1, 1), (0, 1, 1), True), Cin, (1, 3, 3), 'linear 100 maps')
 
 
 @pytest.mark.parametrize('plan', [(256, 1), (256, 2), (128, 1), (128, 3)], ids=lambda p: 'bp%d_ks%d' % p)

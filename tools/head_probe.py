@@ -1,5 +1,5 @@
 """Timing of the one-round 3x3 layers (keypoint-head conv, res4, res5, P4 shapes of the R-18 bench clip) under the environment's launch
-plan -- the harness for experiments with blocks per CU / tile size / split-K (DAT_CONV_BP, DAT_CONV_KSPLIT, DAT_CONV_LDS_PAD ...).
+plan -- the harness for experiments with blocks per CU / tile size / split-K (DAT_CONV_BP, DAT_CONV_KSPLIT ...).
 Developer tool (GPU only)."""
 import os
 import sys

@@ -57,26 +57,13 @@ def fresh(env, tag):
             else: os.environ[k] = v
 
 import sys as _s
-if len(_s.argv) > 1 and _s.argv[1] == 'dma':      # register-staged vs LDS-DMA nine-tap kernel (DAT_WGRAD_DMA), twice each
-    LAYERS[:] = LAYERS[:5]
-    for rep in range(2):
-        fresh({'DAT_WGRAD_DMA': '0'}, 'regs')
-        fresh({'DAT_WGRAD_DMA': '1'}, 'dma')
-elif len(_s.argv) > 1 and _s.argv[1] == 'sub':    # four-wave blocks (two per CU) vs eight-wave blocks with two K ranges (DAT_WGRAD_SUB), K-split sweep of the latter
+if len(_s.argv) > 1 and _s.argv[1] == 'sub':    # four-wave blocks (two per CU) vs eight-wave blocks with two K ranges (DAT_WGRAD_SUB), K-split sweep of the latter
     LAYERS[:] = LAYERS[:5]
     fresh({'DAT_WGRAD_SUB': '1'}, 'sub1')
     fresh({'DAT_WGRAD_SUB': '2'}, 'sub2')
     for ks in (4, 6, 8, 10, 12, 16, 20, 32, 42, 64):
         fresh({'DAT_WGRAD_SUB': '2', 'DAT_WGRAD_KS': str(ks)}, 'sub2ks%d' % ks)
     fresh({'DAT_WGRAD_SUB': '1'}, 'sub1')
-    for name, rs in RESULTS.items():
-        ref = rs[0][1]
-        worst = max(((r - ref).abs().max() / ref.abs().max()).item() for _, r in rs[1:])
-        print('%-28s worst max-abs difference to the first run / max-abs: %.3g' % (name, worst))
-elif len(_s.argv) > 1 and _s.argv[1] == 'ilv':    # LDS-DMA pieces in one burst behind the barrier (0) vs between the MFMA groups (1)
-    LAYERS[:] = LAYERS[:5]
-    for m in (0, 1, 0, 1):
-        fresh({'DAT_WGRAD_ILV': str(m)}, 'ilv%d' % m)
     for name, rs in RESULTS.items():
         ref = rs[0][1]
         worst = max(((r - ref).abs().max() / ref.abs().max()).item() for _, r in rs[1:])
