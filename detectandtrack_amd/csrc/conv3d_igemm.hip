@@ -1047,6 +1047,9 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
     } else if (pwks_eligible(ctx, d) && !force_bp && !force_ks) {       // (its epilogue knows the masking combine too)
         tag = 256 * 10000 + 340 + d->dtype;     // (the K-streaming 1x1 kernel: 256 positions x 256 channels per block)
         rc = launch_pwks(ctx, st, p);
+    } else if (tks_eligible(ctx, d) && !force_bp && !force_ks) {
+        tag = 256 * 10000 + 350 + d->dtype;     // (the temporal-tap K-streaming kernel: kT x 1 x 1, 256 positions x 256 channels per block)
+        rc = launch_tks(ctx, st, p);
     } else if (pwlw_eligible(ctx, d) && !force_bp && !force_ks && d->res_mode != 3) {   // (knows the sum + mask combine; plain mask layers -- K >= 512 data
                                                                                         //  gradients of `branch2c` on small maps -- measured faster on the generic kernel)
         tag = 256 * 10000 + 330 + d->dtype;     // (the weights-in-LDS 1x1 kernel: 32 positions per wave tile)

@@ -122,6 +122,8 @@ bool pwlw_eligible(dat_ctx* ctx, const dat_conv_desc* d);
 int launch_pwlw(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const dat_conv_desc* d);
 bool pwks_eligible(dat_ctx* ctx, const dat_conv_desc* d);
 int launch_pwks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp);
+bool tks_eligible(dat_ctx* ctx, const dat_conv_desc* d);
+int launch_tks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp);
 bool bt_eligible(const dat_ctx* ctx, const dat_conv_desc* d);
 int bt_tile_twl(const ConvParams& p, long long* nblocks);
 int launch_bt(dat_ctx* ctx, hipStream_t st, ConvParams& p);

@@ -793,6 +793,198 @@ __global__ __launch_bounds__(KS_THREADS) void conv1x1_ks_kernel(const PwKsParams
     }
 }
 
+// ---- temporal-tap K-streaming kernel: kT x 1 x 1 convs (the temporal half of a ResNet-(2+1)D block, Tran et al. CVPR 2018) ------------
+// The K-streaming 1x1 kernel above with the reduction walking (temporal tap kt, 64-channel chunk) in the order of the packed weights
+// ([tap][chunk][row block][k-slice][lane][16 B]: consecutive K chunks are mb_total * 4 KB apart for every tap, exactly as for one tap).
+// An output position of frame t reads, for tap kt, the same pixel of frame t + kt - pad_t of ITS clip; a source frame outside [0, T)
+// reads zeros from the context's zero buffer (the generic kernel's patch halo), so a 256-position tile may straddle frame and clip
+// boundaries freely.  A block is conv1x1_ks_kernel's: 256 positions x 256 output channels, eight waves of 128 positions x 64 channels.
+// Epilogue: affine, Sum (res_mode 1), ReLU.  (A 128-channel tile for the Cout-128 res3 layers was built and measured slower than the
+// generic kernel there, 0.95-0.99x: DESIGN.md section 3.7; those layers stay on the generic kernel.)
+struct TkParams {
+    const char* x;
+    const char* w;              // MFMA-fragment order: [tap][64-channel chunk][32-row block][k-slice][lane][16 B]
+    const float* scale;
+    const float* bias;
+    const char* res;
+    const char* zeros;
+    char* y;
+    unsigned npos;              // output positions = input positions: frames * H * W
+    unsigned how;               // H * W
+    int T, pt, kt_n;            // clip length, temporal pad, taps
+    int in_cs, out_cs, cout;
+    int relu, res_mode;
+    int ncb;                    // cout blocks of 256 channels
+    int ncc, kchunks, mb_total; // Cin / 64; KT * Cin / 64; Cout_pad / 32
+    int xcd;                    // XCD-aware block order (more than one cout block)
+};
+
+__global__ __launch_bounds__(KS_THREADS) void conv_kt1x1_ks_kernel(const TkParams p) {
+    constexpr int CB = 256;                             // output channels per block
+    constexpr int NWQ = CB / 64;                        // 64-channel cout quarters per block
+    constexpr int NJ = NWQ;                             // 32-position tiles per wave (8 / NWQ position parts of 32 * NWQ positions)
+    constexpr int WBYTES = CB / 32 * 4 * 1024;          // one K chunk of the weights of a cout block: 32 KB
+    constexpr int WPIECES = CB / 64;                    // 1-KB weight pieces each wave copies per chunk
+    constexpr int EPITCH = 64 * 4 + 16;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* const xb = smem;                              // [3][256 rows x 128 B], XOR-swizzled 16-byte slots
+    char* const wb = smem + 3 * KS_XBYTES;              // [2][CB / 32 row blocks][4 k-slices][64 lanes][16 B]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int khalf = lane >> 5, n = lane & 31;
+    unsigned bid = blockIdx.x;
+    if (p.xcd) {
+        const unsigned nx = 8, q = gridDim.x / nx, r = gridDim.x % nx;
+        const unsigned xcd = bid % nx, k = bid / nx;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+    }
+    const int cb = bid % p.ncb;
+    const unsigned pos0 = (bid / p.ncb) * 256u;
+    const int wq = wave % NWQ, ph = wave / NWQ;         // cout quarter (row blocks 2 wq, 2 wq + 1) / position part (tiles NJ ph .. NJ ph + NJ - 1)
+    typedef const __attribute__((address_space(1))) void* gptr_t;
+    typedef __attribute__((address_space(3))) void* lptr_t;
+    // wave w copies input rows 32 w .. 32 w + 31 (4 pieces of 8 rows); per row: its own pixel's address and its frame inside the clip
+    const char* xsrc[4];
+    int tq[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int row = wave * 32 + u * 8 + (lane >> 3);
+        const int slot = (lane & 7) ^ ((row >> 1) & 7);
+        const unsigned pos = min(pos0 + (unsigned)row, p.npos - 1u);
+        const unsigned f = pos / p.how;
+        tq[u] = (int)(f % (unsigned)p.T);
+        xsrc[u] = p.x + (size_t)pos * (unsigned)p.in_cs * 2u + slot * 16;
+    }
+    const char* wsrc = p.w + (size_t)cb * (CB / 32) * 4096 + (size_t)(wave * WPIECES) * 1024 + lane * 16;
+    const size_t wstep = (size_t)p.mb_total * 4096;
+    const ptrdiff_t fstep = (ptrdiff_t)p.how * p.in_cs * 2;     // bytes between the same pixel of consecutive frames
+    char* const xdma = xb + wave * (32 * 128);
+    char* const wdma = wb + wave * (WPIECES * 1024);
+    // (tap, chunk) of the next input-row request; past the last chunk the last one again, into a buffer nobody reads
+    int rq_t = 0, rq_c = 0;
+#define TK_DMA_X(BUF_)                                                                                       \
+    {                                                                                                        \
+        const int kt_ = min(rq_t, p.kt_n - 1), cc_ = rq_t < p.kt_n ? rq_c : p.ncc - 1;                       \
+        const int dt_ = kt_ - p.pt;                                                                          \
+        const ptrdiff_t off_ = (ptrdiff_t)dt_ * fstep + cc_ * 128;                                           \
+        _Pragma("unroll") for (int u_ = 0; u_ < 4; ++u_) {                                                   \
+            const bool in_ = (unsigned)(tq[u_] + dt_) < (unsigned)p.T;                                       \
+            const char* s_ = in_ ? xsrc[u_] + off_ : p.zeros;                                     \
+            __builtin_amdgcn_global_load_lds((gptr_t)s_, (lptr_t)(xdma + (BUF_) * KS_XBYTES + u_ * 1024), 16, 0, 0); \
+        }                                                                                                    \
+        if (++rq_c == p.ncc) { rq_c = 0; ++rq_t; }                                                           \
+    }
+#define TK_DMA_W(KC_, BUF_)                                                                                  \
+    {                                                                                                        \
+        const char* ws_ = wsrc + (size_t)min((KC_), p.kchunks - 1) * wstep;                                  \
+        _Pragma("unroll") for (int u_ = 0; u_ < WPIECES; ++u_)                                               \
+            __builtin_amdgcn_global_load_lds((gptr_t)(ws_ + u_ * 1024), (lptr_t)(wdma + (BUF_) * WBYTES + u_ * 1024), 16, 0, 0); \
+    }
+#define TK_COMPUTE(XBUF_, WBUF_)                                                                             \
+    {                                                                                                        \
+        const char* xc_ = xb + (XBUF_) * KS_XBYTES + b_base;                                                 \
+        const char* wc_ = wb + (WBUF_) * WBYTES + a_off;                                                     \
+        _Pragma("unroll") for (int ks_ = 0; ks_ < 4; ++ks_) {                                                \
+            uint4 a_[2], b_[NJ];                                                                             \
+            _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) a_[i_] = *(const uint4*)(wc_ + (i_ * 4 + ks_) * 1024); \
+            _Pragma("unroll") for (int j_ = 0; j_ < NJ; ++j_) b_[j_] = *(const uint4*)(xc_ + j_ * 4096 + b_slot[ks_]); \
+            _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_)                                                 \
+                _Pragma("unroll") for (int j_ = 0; j_ < NJ; ++j_) Mma<DAT_BF16>::step(a_[i_], b_[j_], acc[i_][j_]); \
+        }                                                                                                    \
+    }
+    TK_DMA_W(0, 0);
+    TK_DMA_X(0);
+    TK_DMA_X(1);
+    f32x16_t acc[2][NJ];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    const int a_off = (2 * wq) * 4096 + lane * 16;
+    const int b_base = (ph * (32 * NJ) + n) * 128;
+    int b_slot[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) b_slot[ks] = (((ks * 2 + khalf) ^ (n >> 1)) & 7) << 4;
+    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");    // chunk 0 (weights + rows) has landed; the rows of chunk 1 may still be on their way
+    __syncthreads();
+    // the pipeline of conv1x1_ks_kernel: weights one chunk ahead (two buffers), input rows two chunks ahead (three buffers), one barrier per chunk
+    int xi = 0;
+    for (int kc = 0; kc < p.kchunks; ++kc) {
+        const int x2 = xi >= 1 ? xi - 1 : 2;
+        TK_DMA_W(kc + 1, (kc + 1) & 1);
+        TK_DMA_X(x2);
+        TK_COMPUTE(xi, kc & 1);
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        __syncthreads();
+        xi = xi == 2 ? 0 : xi + 1;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+#undef TK_DMA_X
+#undef TK_DMA_W
+#undef TK_COMPUTE
+    // ---- epilogue (conv1x1_ks_kernel's, modes 0 / 1) ----
+    char* const est = smem + wave * (32 * EPITCH);
+    const int sq = lane & 7, spl = lane >> 3;
+    const int c0 = cb * CB + wq * 64 + sq * 8;
+    float sc[8], bi[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const bool ok = c0 + e < p.cout;
+        const int c = ok ? c0 + e : 0;
+        sc[e] = ok ? (p.scale ? p.scale[c] : 1.f) : 0.f;
+        bi[e] = (ok && p.bias) ? p.bias[c] : 0.f;
+    }
+    const unsigned cres = (unsigned)min(c0, p.out_cs - 8);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const unsigned tile0 = pos0 + (unsigned)(ph * (32 * NJ) + j * 32);
+        uint4 rr[4];
+        if (p.res_mode) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const unsigned pc = min(tile0 + (unsigned)(r * 8 + spl), p.npos - 1u);
+                rr[r] = *(const uint4*)(p.res + ((size_t)pc * (unsigned)p.out_cs + cres) * 2u);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                *(float4*)(est + n * EPITCH + (i * 32 + g * 8 + khalf * 4) * 4) =
+                    make_float4(acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1], acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int pl = r * 8 + spl;
+            const float4 t0 = *(const float4*)(est + pl * EPITCH + sq * 32);
+            const float4 t1 = *(const float4*)(est + pl * EPITCH + sq * 32 + 16);
+            float v[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = v[e] * sc[e] + bi[e];
+            if (p.res_mode) {
+                const uint32_t ru[4] = {rr[r].x, rr[r].y, rr[r].z, rr[r].w};
+#pragma unroll
+                for (int e2 = 0; e2 < 4; ++e2) {
+                    v[2 * e2] = res_combine(v[2 * e2], bf2f((uint16_t)(ru[e2] & 0xffff)), 1);
+                    v[2 * e2 + 1] = res_combine(v[2 * e2 + 1], bf2f((uint16_t)(ru[e2] >> 16)), 1);
+                }
+            }
+            if (p.relu) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+            }
+            const unsigned pos = tile0 + (unsigned)pl;
+            if (pos < p.npos && c0 < p.cout)
+                *(uint4*)(p.y + ((size_t)pos * (unsigned)p.out_cs + (unsigned)c0) * 2u) =
+                    make_uint4(f2bf2(v[0], v[1]), f2bf2(v[2], v[3]), f2bf2(v[4], v[5]), f2bf2(v[6], v[7]));
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // ---- big-tile 3x3 kernel: 256 output channels x 256 positions per block, one block per CU, one wave per SIMD ---------------------
 // The 128 x 256 kernel above feeds 8 MFMAs per k-slice from 6 operand fragments per wave, two blocks per CU: the CU's operand
 // delivery (L1 64 B/clk for the weight fragments, LDS for the patch) is what holds it at ~55 % of the matrix peak (DESIGN.md
@@ -1268,6 +1460,46 @@ int launch_pwks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
     if (dat_ensure_lds(ctx, (const void*)conv1x1_ks_kernel, 160 * 1024) != DAT_OK) return DAT_ERR_LAUNCH;
     hipLaunchKernelGGL(conv1x1_ks_kernel, dim3((unsigned)blocks), dim3(KS_THREADS), lds, st, p);
     DAT_CHECK_LAUNCH(ctx, "conv1x1_ks");
+    return DAT_OK;
+}
+
+// Temporal-tap K-streaming kernel (DAT_CONV_TEMPORAL, default 1): kT x 1 x 1 bf16 convs with "same" temporal padding over whole clips,
+// spatial stride 1, epilogue modes 0 / 1.  The masking modes of the data gradients, windowed calls, the fp16 build, fp32 / bf16x3 and
+// forced plans keep the generic kernel.  The rule follows the per-layer A/B of DESIGN.md section 3.7 (tools/probes/temporal_probe.py):
+// the kernel wins 1.38-1.40x on the Cout 256 / 512 layers of res4 / res5 at 4 clips (256-504 blocks) and loses 0.71-0.95x on the same
+// layers at one clip (64-126 blocks: under one block per CU the generic kernel's 2-4x more blocks win), so it takes grids of >= 3/4
+// block per CU; Cout 128 (res3) measured slower at every size and stays generic (Cout must pad to a multiple of 256).
+// DAT_CONV_TEMPORAL=2 drops the grid rule (tests, the probe).
+bool tks_eligible(dat_ctx* ctx, const dat_conv_desc* d) {
+    if (!(ctx->dbg_temporal > 0 && DAT_H16_FORMAT == 0 && d->dtype == DAT_BF16 && d->KT > 1 && d->KH == 1 && d->KW == 1 && d->pad_h == 0 &&
+          d->pad_w == 0 && d->pad_t * 2 + 1 == d->KT && d->out_tn <= 0 && d->in_tn <= 0 && d->stride_h == 1 && d->stride_w == 1 &&
+          (d->res_mode == 0 || d->res_mode == 1)))
+        return false;
+    if (d->Cin % 64 || cout_pad_of(d) % 256) return false;
+    if (d->out_cstride % 8 || d->out_cstride < d->Cout || d->out_cstride < 8) return false;
+    const long long how = (long long)d->H * d->W, npos = (long long)d->frames * how;
+    if (how < 1 || npos >= (1ll << 31) || npos * d->Cin >= (1ll << 40)) return false;
+    const long long blocks = cdiv_ll(npos, 256) * (cout_pad_of(d) / 256);
+    return npos >= 256 && (ctx->dbg_temporal >= 2 || blocks * 4 >= 3ll * ctx_num_cu(ctx));
+}
+
+int launch_tks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
+    TkParams p;
+    p.x = cp.x; p.w = cp.w; p.scale = cp.scale; p.bias = cp.bias; p.res = cp.res; p.zeros = cp.zeros; p.y = cp.y;
+    p.npos = (unsigned)((long long)cp.frames * cp.Ho * cp.Wo);
+    p.how = (unsigned)(cp.Ho * cp.Wo);
+    p.T = cp.T; p.pt = cp.pt; p.kt_n = cp.KT;
+    p.in_cs = cp.Cin; p.out_cs = cp.out_cs; p.cout = cp.Cout; p.relu = cp.relu; p.res_mode = cp.res_mode;
+    p.ncb = cp.Cout_pad / 256; p.ncc = cp.Cin / 64; p.kchunks = cp.KT * p.ncc; p.mb_total = cp.Cout_pad / 32;
+    p.xcd = ctx->dbg_pw_xcd && p.ncb > 1;
+    const long long blocks = cdiv_ll(p.npos, 256) * p.ncb;
+    DAT_ENFORCE(ctx, blocks > 0 && blocks < (1ll << 31), "conv_kt1x1_ks: grid of %lld blocks unsupported", blocks);
+    DAT_ENFORCE(ctx, cp.Ho == cp.H && cp.Wo == cp.W && cp.res_mode <= 1 && cp.Cout_pad % 256 == 0 && cp.zeros,
+                "conv_kt1x1_ks: unsupported call");
+    const size_t lds = (size_t)3 * KS_XBYTES + 2 * KS_WBYTES;     // 160 KB: three input buffers, two weight buffers (the epilogue reuses them)
+    if (dat_ensure_lds(ctx, (const void*)conv_kt1x1_ks_kernel, 160 * 1024) != DAT_OK) return DAT_ERR_LAUNCH;
+    hipLaunchKernelGGL(conv_kt1x1_ks_kernel, dim3((unsigned)blocks), dim3(KS_THREADS), lds, st, p);
+    DAT_CHECK_LAUNCH(ctx, "conv_kt1x1_ks");
     return DAT_OK;
 }
 

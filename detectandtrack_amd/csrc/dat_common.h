@@ -52,6 +52,7 @@ struct dat_ctx {
     int dbg_roi_fold;                       // DAT_ROI_BWD_FOLD (default 1): RoIAlign backward folds a bin's samples into one weight per distinct pixel before the atomics
     int num_cu;                             // compute units of the device (persistent-kernel grids)
     int dbg_ntap;                           // DAT_CONV_NTAP (default 1): unrolled-tap variants of the implicit-GEMM kernel (3x3 stride 1, 1x1)
+    int dbg_temporal;                       // DAT_CONV_TEMPORAL (default 1): temporal-tap K-streaming kernel for kT x 1 x 1 layers ((2+1)D blocks) with Cout a multiple of 256 on grids of >= 3/4 block per CU; 2 = every supported shape (tests, tools/probes/temporal_probe.py); 0 = the generic kernel
     // kernels whose dynamic-LDS limit was already raised on this context's device (the attribute is per device)
     std::unordered_set<const void*> lds_attr_done;
 };

@@ -25,6 +25,14 @@ def add_fpn_ResNet18_conv5_body(model):
     return _onto(model, ResNet.add_ResNet18_conv5_body, ResNet.stage_info_ResNet18_conv5)
 
 
+def add_fpn_ResNet18_2plus1d_conv5_body(model):
+    return _onto(model, ResNet.add_ResNet18_2plus1d_conv5_body, ResNet.stage_info_ResNet18_2plus1d_conv5)
+
+
+def add_fpn_ResNet50_2plus1d_conv5_body(model):
+    return _onto(model, ResNet.add_ResNet50_2plus1d_conv5_body, ResNet.stage_info_ResNet50_2plus1d_conv5)
+
+
 def add_fpn_ResNet34_conv5_body(model):
     return _onto(model, ResNet.add_ResNet34_conv5_body, ResNet.stage_info_ResNet34_conv5)
 

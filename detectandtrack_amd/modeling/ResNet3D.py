@@ -3,7 +3,9 @@
 Same public function names (they are referenced BY NAME from YAML: `MODEL.CONV_BODY:
 ResNet3D.add_ResNet18_conv4_body`, model_builder.py:39-49), same blob / parameter names, same stage
 arithmetic.  "3D" here means full kT x 3 x 3 kernels with kT = VIDEO.TIME_KERNEL_DIM.BODY in res3..res5 and
-kT = 1 in conv1/res2, never a temporal stride (reference ResNet3D.py:258-284).
+kT = 1 in conv1/res2, never a temporal stride (reference ResNet3D.py:258-284).  The `*_2plus1d_*` bodies
+(ResNet-(2+1)D, Tran et al., CVPR 2018; no reference code) factorise every kT x 3 x 3 conv of res3..res5 into a 1 x 3 x 3 conv,
+affine, ReLU and a kT x 1 x 1 conv, affine; blob names of block outputs, stage outputs and FPN taps stay those of the I3D body.
 """
 from detectandtrack_amd.core.config import cfg
 from detectandtrack_amd.modeling.common import ConvStageInfo
@@ -44,7 +46,58 @@ def basic_transformation(model, blob_in, dim_in, dim_out, stride, prefix, dim_in
                               pads=2 * [kt // 2, dilation, dilation], dilations=dilation, group=group, inplace=False)
 
 
-_TRANS = {'bottleneck_transformation': bottleneck_transformation, 'basic_transformation': basic_transformation}
+def mid_planes_2plus1d(dim_in, dim_out, kt):
+    """Mid-plane count M of a factorised kT x 3 x 3 conv (Tran et al., CVPR 2018, eq. 1): the 1 x 3 x 3 (dim_in -> M) and
+    kT x 1 x 1 (M -> dim_out) pair holds as many weights as the kT x 3 x 3 conv it replaces, to within M's rounding."""
+    return (kt * 9 * dim_in * dim_out) // (9 * dim_in + kt * dim_out)
+
+
+def conv_affine_2plus1d(model, blob_in, prefix, dim_in, dim_out, kt, stride, dilation=1, inplace=True):
+    """A kT x 3 x 3 conv + AffineChannelNd (kT > 1), factorised: `<prefix>_spatial` 1 x 3 x 3 (spatial stride, pad 1) + `_spatial_bn`
+    + ReLU, then `<prefix>_temporal` kT x 1 x 1 (temporal pad kT // 2, spatial stride 1) + `_temporal_bn`."""
+    mid = mid_planes_2plus1d(dim_in, dim_out, kt)
+    cur = model.ConvAffineNd(blob_in, prefix + '_spatial', dim_in, mid, kernels=[1, 3, 3], strides=[1, stride, stride],
+                             pads=2 * [0, dilation, dilation], dilations=[1, dilation, dilation], inplace=True)
+    cur = model.Relu(cur, cur)
+    return model.ConvAffineNd(cur, prefix + '_temporal', mid, dim_out, kernels=[kt, 1, 1], strides=[1, 1, 1],
+                              pads=2 * [kt // 2, 0, 0], inplace=inplace)
+
+
+def bottleneck_2plus1d_transformation(model, blob_in, dim_in, dim_out, stride, prefix, dim_inner, dilation=1, group=1,
+                                      time_kernel_dim=1, time_stride_on=False):
+    """bottleneck_transformation with its kT x 3 x 3 `branch2b` factorised (conv_affine_2plus1d); no temporal stride.  kT = 1 (res2,
+    TIME_KERNEL_DIM.BODY 1): the I3D block itself."""
+    if time_kernel_dim == 1:
+        return bottleneck_transformation(model, blob_in, dim_in, dim_out, stride, prefix, dim_inner, dilation, group, 1, time_stride_on)
+    assert not time_stride_on and group == 1, 'the (2+1)D body has no temporal stride and no groups'
+    s1, s3 = (stride, 1) if cfg.RESNETS.STRIDE_1X1 else (1, stride)
+    cur = model.ConvAffineNd(blob_in, prefix + '_branch2a', dim_in, dim_inner, kernels=[1, 1, 1], strides=[1, s1, s1],
+                             pads=2 * [0, 0, 0], inplace=True)
+    cur = model.Relu(cur, cur)
+    cur = conv_affine_2plus1d(model, cur, prefix + '_branch2b', dim_inner, dim_inner, time_kernel_dim, s3, dilation)
+    cur = model.Relu(cur, cur)
+    return model.ConvAffineNd(cur, prefix + '_branch2c', dim_inner, dim_out, kernels=[1, 1, 1], strides=[1, 1, 1],
+                              pads=2 * [0, 0, 0], inplace=False)
+
+
+def basic_2plus1d_transformation(model, blob_in, dim_in, dim_out, stride, prefix, dim_inner, dilation=1, group=1,
+                                 time_kernel_dim=1, time_stride_on=False):
+    """basic_transformation with both kT x 3 x 3 convs factorised (conv_affine_2plus1d); no temporal stride.  kT = 1 (res2,
+    TIME_KERNEL_DIM.BODY 1): the I3D block itself."""
+    if time_kernel_dim == 1:
+        return basic_transformation(model, blob_in, dim_in, dim_out, stride, prefix, dim_inner, dilation, group, 1, time_stride_on)
+    assert not time_stride_on and group == 1, 'the (2+1)D body has no temporal stride and no groups'
+    if dim_inner is None:
+        dim_inner = dim_out
+    kt = time_kernel_dim
+    cur = conv_affine_2plus1d(model, blob_in, prefix + '_branch2a', dim_in, dim_inner, kt, stride)
+    cur = model.Relu(cur, cur)
+    return conv_affine_2plus1d(model, cur, prefix + '_branch2b', dim_inner, dim_out, kt, 1, dilation, inplace=False)
+
+
+_TRANS = {'bottleneck_transformation': bottleneck_transformation, 'basic_transformation': basic_transformation,
+          'bottleneck_2plus1d_transformation': bottleneck_2plus1d_transformation,
+          'basic_2plus1d_transformation': basic_2plus1d_transformation}
 
 
 def add_shortcut(model, prefix, blob_in, dim_in, dim_out, stride, time_stride_on):
@@ -168,6 +221,22 @@ def add_ResNet152_conv5_body(model):
     return _body(model, (3, 8, 36, 3), 'bottleneck_transformation')
 
 
+def add_ResNet18_2plus1d_conv4_body(model):
+    return _body(model, (2, 2, 2), 'basic_2plus1d_transformation', (64, 64, 128, 256))
+
+
+def add_ResNet18_2plus1d_conv5_body(model):
+    return _body(model, (2, 2, 2, 2), 'basic_2plus1d_transformation', (64, 64, 128, 256, 512))
+
+
+def add_ResNet50_2plus1d_conv4_body(model):
+    return _body(model, (3, 4, 6), 'bottleneck_2plus1d_transformation')
+
+
+def add_ResNet50_2plus1d_conv5_body(model):
+    return _body(model, (3, 4, 6, 3), 'bottleneck_2plus1d_transformation')
+
+
 def add_ResNet18_roi_conv5_head(*args, **kwargs):
     kwargs.update(dim_out=512, block_counts=2)
     return add_ResNet_roi_conv5_head(*args, **kwargs)
@@ -202,3 +271,11 @@ def stage_info_ResNet101_conv5():
 
 def stage_info_ResNet152_conv5():
     return _stage_info((2, 35, 7, 2), (2048, 1024, 512, 256))
+
+
+def stage_info_ResNet18_2plus1d_conv5():
+    return stage_info_ResNet18_conv5()
+
+
+def stage_info_ResNet50_2plus1d_conv5():
+    return stage_info_ResNet50_conv5()

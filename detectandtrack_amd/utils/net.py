@@ -59,7 +59,7 @@ def synthetic_params(model, seed=3):
     up-sampling kernel is the fixed one of detector.py:356-372."""
     rs = np.random.RandomState(seed)
     trans = cfg.RESNETS.TRANS_FUNC
-    last_bn = '_branch2c_bn_s' if trans == 'bottleneck_transformation' else '_branch2b_bn_s'
+    last_bn = ('_branch2c_bn_s',) if trans.startswith('bottleneck') else ('_branch2b_bn_s', '_branch2b_temporal_bn_s')
     linear = ('fpn_', 'rpn_cls', 'rpn_bbox', 'cls_score', 'bbox_pred', 'kps_score')
     out = {}
     for name in model.params:
@@ -69,7 +69,7 @@ def synthetic_params(model, seed=3):
             out[name] = _fill('BilinearFill', spec['init'][1], shape, rs)
         elif spec.get('affine'):
             if name.endswith('_s'):
-                lo, hi = (0.2, 0.4) if name.endswith(last_bn) else (0.5, 1.0)
+                lo, hi = (0.2, 0.4) if name.endswith(last_bn) else (0.5, 1.0)   # (the (2+1)D bodies: their last affine is `_temporal_bn`)
                 out[name] = rs.uniform(lo, hi, shape).astype(np.float32)
             else:
                 out[name] = (rs.randn(*shape) * 0.1).astype(np.float32)
