@@ -450,8 +450,9 @@ int dat_spatial_mean(dat_ctx* ctx, dat_stream s, int dtype, const void* x, float
 }
 
 int dat_softmax_rows(dat_ctx* ctx, dat_stream s, const float* x, float* y, int rows, int K, int ld_in, int ld_out) {
-    DAT_ENFORCE(ctx, x && y && K > 0, "softmax: bad argument");
+    DAT_ENFORCE(ctx, K > 0 && rows >= 0, "softmax: bad argument (rows %d, K %d)", rows, K);
     if (rows == 0) return DAT_OK;
+    DAT_ENFORCE(ctx, x && y, "softmax: null argument");
     hipLaunchKernelGGL(softmax_rows_kernel, dim3(grid_for(rows)), dim3(TPB), 0, (hipStream_t)s, x, y, rows, K, ld_in, ld_out);
     DAT_CHECK_LAUNCH(ctx, "softmax_rows");
     return DAT_OK;
@@ -467,13 +468,16 @@ int dat_deconv_k4s2_weights(dat_ctx* ctx, dat_stream s, const float* w, int Cin,
 
 int dat_kps_finalize(dat_ctx* ctx, dat_stream s, int dtype, const void* sub, int R, int Tr, int S, int cs, int K, int up,
                      float* out) {
-    DAT_ENFORCE(ctx, sub && out && up >= 2 && up % 2 == 0, "kps_finalize: up_scale must be even (detector.py:354), got %d", up);
+    DAT_ENFORCE(ctx, up >= 2 && up % 2 == 0, "kps_finalize: up_scale must be even (detector.py:354), got %d", up);
+    // both kernels read the sub-pixel channels ab * K + k, ab in 0..3, of every cell: a narrower cell would make them read its neighbour
+    DAT_ENFORCE(ctx, K > 0 && 4 * K <= cs, "kps_finalize: the 4*K = %d sub-pixel channels do not fit the channel stride %d", 4 * K, cs);
     if (R == 0) return DAT_OK;
+    DAT_ENFORCE(ctx, sub && out, "kps_finalize: null argument");
     const size_t total = (size_t)R * Tr * K * (2 * S * up) * (2 * S * up);
     const int M = 2 * S * up;
     const size_t lds = (size_t)(2 * S) * (2 * S) * sizeof(float);
     static const bool tile_off = getenv("DAT_KPS_FINALIZE_TILE") && atoi(getenv("DAT_KPS_FINALIZE_TILE")) == 0;   // (A/B switch)
-    if (!tile_off && M <= 256 && lds <= 48 * 1024 && 4 * K <= cs && (long long)R * Tr * K < (1ll << 31) && (long long)R * Tr * K >= 1024) {   // (small jobs: the per-element kernel has more threads)
+    if (!tile_off && M <= 256 && lds <= 48 * 1024 && (long long)R * Tr * K < (1ll << 31) && (long long)R * Tr * K >= 1024) {   // (small jobs: the per-element kernel has more threads)
         // one block per output map: ng * M threads, ng output rows per step
         const int ng = std::max(1, std::min(4, 256 / M));
         if (dtype == DAT_BF16)

@@ -332,7 +332,8 @@ int dat_soft_nms_host(const float* boxes_in, int n, float sigma, float Nt, float
 int dat_deconv_k4s2_weights(dat_ctx* ctx, dat_stream s, const float* w, int Cin, int K, float* w3x3);
 /* sub [R*Tr, S, S, cs] (4K sub-pixel channels, bias already added) -> kps_score fp32 NCHW
  * [R, Tr*K, 2*up*S, 2*up*S]: pixel-shuffle to 2S then the fixed bilinear ConvTranspose (k=2*up, s=up,
- * p=up/2; model_builder.py:858-868 incl. time->channel ordering t*K+k). */
+ * p=up/2; model_builder.py:858-868 incl. time->channel ordering t*K+k).  The channel stride must hold the sub-pixel channels
+ * (4*K <= cs, an error otherwise); R = 0 is a no-op. */
 int dat_kps_finalize(dat_ctx* ctx, dat_stream s, int dtype, const void* sub, int R, int Tr, int S, int cs, int K,
                      int up, float* out);
 

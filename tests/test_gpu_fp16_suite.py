@@ -1,7 +1,8 @@
 """The fp16 library build (libdat_hip_f16.so: the same sources with -DDAT_H16_IS_FP16, cfg.HIP.DTYPE 'fp16'), kernel by kernel.
 
 The 16-bit format belongs to the loaded library, so the format-generic kernel tests run again in ONE child process started with
-DAT_H16=fp16: tests/test_gpu_kernels.py, tests/test_gpu_fp16_edges.py and the persistent-kernel test of tests/test_gpu_model.py.
+DAT_H16=fp16: tests/test_gpu_kernels.py, tests/test_gpu_fp16_edges.py, tests/test_gpu_infer_kernels.py and the persistent-kernel test
+of tests/test_gpu_model.py.
 The parent reads the child's JUnit report: no failure or error, every skip is a bf16-only test, and one test per kernel family (plus
 the NMS and proposal goldens) is among the passed -- so that a collection mistake cannot pass for a green run.  The child is never
 retried."""
@@ -15,11 +16,12 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD_FILES = ['tests/test_gpu_kernels.py', 'tests/test_gpu_fp16_edges.py',
+CHILD_FILES = ['tests/test_gpu_kernels.py', 'tests/test_gpu_fp16_edges.py', 'tests/test_gpu_infer_kernels.py',
                'tests/test_gpu_model.py::test_persistent_kernel_cu_share_does_not_change_results']
 
 K = 'tests.test_gpu_kernels::'
 E = 'tests.test_gpu_fp16_edges::'
+I = 'tests.test_gpu_infer_kernels::'
 MUST_PASS = [
     K + 'test_layout_roundtrip[1]',
     K + 'test_conv3d[3x3x3-bf16]',                                   # generic kernel + the split-K finish
@@ -56,6 +58,11 @@ MUST_PASS = [
     E + 'test_subnormal_operands_and_outputs[big_tile_3x3]',
     E + 'test_layout_conversion_is_torch_rounding_bit_for_bit',
     'tests.test_gpu_model::test_persistent_kernel_cu_share_does_not_change_results',
+    I + 'test_roi_align[tube3_adaptive_c72-16]',                      # four FPN levels, tube rois, 16-bit maps
+    I + 'test_roi_align[two_grid_passes_c256-16]',
+    I + 'test_kps_finalize_tile_kernel[4-2-28-128-16]',
+    I + 'test_time_avg[3-3-5x7x13-16]',
+    I + 'test_copy_frames[4012-129]',
 ]
 
 

@@ -142,11 +142,12 @@ def roi_levels(rois, Tr, n_levels, k_min, canon_scale, canon_level):
     return (np.clip(lv, k_min, k_min + n_levels - 1) - k_min).astype(np.int64)
 
 
-def _axis(c1, c2, size, P, grid):
+def _axis(c1, c2, size, P, grid, strict=True):
     """Bilinear weights of one axis of a roi: A[p, i] = sum over the grid samples of bin p of their weight on pixel i (0 for samples
     outside [-1, size]), I = the number of taps on (p, i), E = the taps' weight error from the fp32 sample coordinate (8 ulps of the
     magnitudes it is computed from).  The kernels' per-sample weight is the product of the two axes' weights, its validity the product
-    of their indicators, so a bin's scatter is A_y^T G A_x."""
+    of their indicators, so a bin's scatter is A_y^T G A_x.  A sample within that error of a validity cut-off (-1 or size) raises: the
+    kernel may decide it either way.  strict=False decides it in float64 instead (hand-worked cases with samples exactly on a cut-off)."""
     A, I, E = np.zeros((P, size)), np.zeros((P, size)), np.zeros((P, size))
     rw = max(c2 - c1, 1.0)
     b = rw / P
@@ -154,7 +155,7 @@ def _axis(c1, c2, size, P, grid):
         for i in range(grid):
             y = c1 + p * b + (i + 0.5) * b / grid
             e = 8 * U32 * (abs(c1) + abs(c2) + abs(y) + 1.0)
-            if min(abs(y + 1.0), abs(y - size)) < 4 * e:
+            if strict and min(abs(y + 1.0), abs(y - size)) < 4 * e:
                 raise ValueError('sample %.7f within the fp32 coordinate error of a validity cut-off: the kernel may decide it either '
                                  'way' % y)
             if y < -1.0 or y > size:
@@ -184,21 +185,15 @@ def _scatter(Ay, Ax, G):
     return h0, w0, np.tensordot(t1, Ax[:, w0:w1], axes=(1, 0)).transpose(0, 2, 1)
 
 
-def roi_align_bwd_ref(shapes, scales, rois, dout, T, Tr, t0, pooled, sampling, k_min=2, canon_scale=224., canon_level=4):
-    """dat_roi_align_bwd: the transpose of the legacy RoIAlign (oracle/roi_align.py) with the FPN level picked per roi.
-    shapes: [(frames, H, W)] per level (finest first); rois [R, 4*Tr + 1]; dout [R*Tr, P, P, C].  Returns (ref, abs, extra) lists of
-    float64 [frames, H, W, C] maps and K, the largest number of atomic contributions to one element."""
+def roi_frames(shapes, scales, rois, T, Tr, t0, pooled, sampling, k_min=2, canon_scale=224., canon_level=4, strict=True):
+    """What the RoIAlign kernels (forward and backward) decide per roi and frame, for rois [R, 4*Tr + 1] over levels of shapes
+    [(frames, H, W)]: yields (row, level, frame, gh, gw, (Ay, Iy, Ey), (Ax, Ix, Ex)) with row = r * Tr + t the roi-frame's row of the
+    pooled tensor and the axis matrices of `_axis`."""
     r32 = _f64(rois).astype(np.float32)
-    G_all = _f64(dout).astype(np.float64)
-    C = G_all.shape[-1]
     P = pooled
     lv = roi_levels(r32, Tr, len(shapes), k_min, canon_scale, canon_level)
-    ref = [np.zeros(s + (C,)) for s in shapes]
-    ab = [np.zeros(s + (C,)) for s in shapes]
-    ex = [np.zeros(s + (C,)) for s in shapes]
-    cnt = [np.zeros(s) for s in shapes]
     for r in range(r32.shape[0]):
-        li = lv[r]
+        li = int(lv[r])
         _, H, W = shapes[li]
         sc32 = np.float32(scales[li])
         n = int(r32[r, 0])
@@ -210,15 +205,28 @@ def roi_align_bwd_ref(shapes, scales, rois, dout, T, Tr, t0, pooled, sampling, k
             gh = sampling if sampling > 0 else int(np.ceil(np.float32(max(y2 - y1, np.float32(1.))) / np.float32(P)))
             gw = sampling if sampling > 0 else int(np.ceil(np.float32(max(x2 - x1, np.float32(1.))) / np.float32(P)))
             c = [float(v) * float(sc32) for v in bx]          # sample coordinates in float64
-            Ay, Iy, Ey = _axis(c[1], c[3], H, P, gh)
-            Ax, Ix, Ex = _axis(c[0], c[2], W, P, gw)
-            G = G_all[r * Tr + t] / (gh * gw)
-            aG = np.abs(G)
-            for dst, ay, ax, g in ((ref, Ay, Ax, G), (ab, Ay, Ax, aG), (ex, Ey, Ix, aG), (ex, Iy, Ex, aG)):
-                h0, w0, blk = _scatter(ay, ax, g)
-                if blk is not None:
-                    dst[li][fr, h0:h0 + blk.shape[0], w0:w0 + blk.shape[1]] += blk
-            cnt[li][fr] += np.outer(Iy.sum(0), Ix.sum(0))
+            yield r * Tr + t, li, fr, gh, gw, _axis(c[1], c[3], H, P, gh, strict), _axis(c[0], c[2], W, P, gw, strict)
+
+
+def roi_align_bwd_ref(shapes, scales, rois, dout, T, Tr, t0, pooled, sampling, k_min=2, canon_scale=224., canon_level=4):
+    """dat_roi_align_bwd: the transpose of the legacy RoIAlign (oracle/roi_align.py) with the FPN level picked per roi.
+    shapes: [(frames, H, W)] per level (finest first); rois [R, 4*Tr + 1]; dout [R*Tr, P, P, C].  Returns (ref, abs, extra) lists of
+    float64 [frames, H, W, C] maps and K, the largest number of atomic contributions to one element."""
+    G_all = _f64(dout).astype(np.float64)
+    C = G_all.shape[-1]
+    ref = [np.zeros(s + (C,)) for s in shapes]
+    ab = [np.zeros(s + (C,)) for s in shapes]
+    ex = [np.zeros(s + (C,)) for s in shapes]
+    cnt = [np.zeros(s) for s in shapes]
+    for row, li, fr, gh, gw, (Ay, Iy, Ey), (Ax, Ix, Ex) in roi_frames(shapes, scales, rois, T, Tr, t0, pooled, sampling, k_min,
+                                                                      canon_scale, canon_level):
+        G = G_all[row] / (gh * gw)
+        aG = np.abs(G)
+        for dst, ay, ax, g in ((ref, Ay, Ax, G), (ab, Ay, Ax, aG), (ex, Ey, Ix, aG), (ex, Iy, Ex, aG)):
+            h0, w0, blk = _scatter(ay, ax, g)
+            if blk is not None:
+                dst[li][fr, h0:h0 + blk.shape[0], w0:w0 + blk.shape[1]] += blk
+        cnt[li][fr] += np.outer(Iy.sum(0), Ix.sum(0))
     return ref, ab, ex, int(max(c.max() for c in cnt))
 
 
@@ -228,13 +236,32 @@ def _bilinear_up(K, up):
     return torch.from_numpy(np.ascontiguousarray(bilinear_kernel(K, up), np.float64))
 
 
+def _bilinear_up_matrix(L, up):
+    """The fixed bilinear ConvTranspose (k = 2*up, s = up, p = up/2) of oracle.net3d.bilinear_kernel along one axis, as a matrix
+    U [L*up, L]: the kernel is the outer product f f^T of one 1-D factor and acts on every channel alone, so a map's output is
+    U low U^T (tests/test_train_refs_cpu.py holds this to the ConvTranspose itself)."""
+    from oracle.net3d import bilinear_kernel
+    k2 = np.asarray(bilinear_kernel(2, up), np.float64)
+    assert np.all(k2[0, 1] == 0) and np.array_equal(k2[0, 0], k2[1, 1]), 'the bilinear kernel is diagonal over the channels'
+    f = k2[0, 0].sum(1) / np.sqrt(k2[0, 0].sum())
+    assert np.allclose(np.outer(f, f), k2[0, 0], rtol=1e-15, atol=0)
+    U = np.zeros((L * up, L))
+    for o in range(L * up):
+        for y in range(L):
+            ky = o + up // 2 - up * y
+            if 0 <= ky < 2 * up:
+                U[o, y] = f[ky]
+    return torch.from_numpy(U)
+
+
 def kps_finalize_ref(sub, R, Tr, K, up):
     """dat_kps_finalize in float64: the sub-pixel channels (a*2 + b)*K + k of sub [R*Tr, S, S, cs] unfolded into kps_score_lowres
     [R*Tr, K, 2S, 2S], then the fixed bilinear ConvTranspose of oracle.net3d.kps_outputs_2d -> [R, Tr*K, M, M]."""
     s = torch.from_numpy(_f64(sub).astype(np.float64))
     Fr, S = s.shape[0], s.shape[1]
     low = s[..., :4 * K].reshape(Fr, S, S, 2, 2, K).permute(0, 5, 1, 3, 2, 4).reshape(Fr, K, 2 * S, 2 * S)
-    out = F.conv_transpose2d(low, _bilinear_up(K, up), None, stride=up, padding=up // 2)
+    U = _bilinear_up_matrix(2 * S, up)
+    out = torch.matmul(torch.matmul(U, low), U.t())
     return out.reshape(R, Tr * K, out.shape[-2], out.shape[-1]).numpy()
 
 
