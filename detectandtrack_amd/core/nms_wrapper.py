@@ -2,8 +2,8 @@
 
 Boxes (5 columns) use the cython_nms semantics (suppress at IoU >= thresh, ascending original indices); tubes use
 py_cpu_nms_tubes semantics (mean IoU over frames, keep while <= thresh, score order) -- both on the device.  Soft-NMS
-(lib/utils/cython_nms.pyx:98-203) is a sequential host algorithm: `dat_soft_nms_host` runs the reference's loop in the same C float
-arithmetic.  `nms(..., soft_nms=True)` is rejected loudly: the reference's dispatcher accepts the flag and silently ignores it."""
+(lib/utils/cython_nms.pyx:98-203) for host arrays runs the reference's loop in the same C float arithmetic (`dat_soft_nms_host`);
+callers that hold device tensors use ops.hip_ops.soft_nms / box_results(soft_nms=...), the device twin the engine runs.  `nms(..., soft_nms=True)` is rejected loudly: the reference's dispatcher accepts the flag and silently ignores it."""
 import ctypes as C
 
 import numpy as np

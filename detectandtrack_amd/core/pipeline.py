@@ -234,7 +234,7 @@ class ClipPipeline(object):
         self.finish_times = []      # perf_counter() at every completed forward (steady-state rate of a run: see rate())
         self.trunk = None           # FrameTrunkCache, made by the first submit_frames(..., frame_ids=...) with cfg.HIP.FRAME_TRUNK_CACHE > 0
         self.device_glue = engine.device_results_supported()
-        assert self.device_glue, 'the pipelined engine runs the device post-processing path (cfg.HIP.DEVICE_BOX_RESULTS, hard NMS)'
+        assert self.device_glue, 'the pipelined engine runs the device post-processing path (cfg.HIP.DEVICE_BOX_RESULTS)'
 
     # ---- slot management ---------------------------------------------------------------------------------------------------
     def _acquire(self):

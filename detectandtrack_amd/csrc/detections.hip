@@ -7,8 +7,8 @@
 //                             then TEST.DETECTIONS_PER_IM over all classes (scores >= the D-th best);
 //   lib/core/test.py:78-123   _get_rois_blob: the kept boxes * im_scale with a leading level column = `keypoint_rois`.
 // The reference fetches rois / cls_prob / bbox_pred to the host (a device sync per clip), loops over classes in NumPy, calls
-// the NMS, and feeds `keypoint_rois` back.  Here the chain is: one select+decode kernel and one NMS per foreground class, one
-// limit+emit kernel; the keypoint net then runs on the device-resident `keypoint_rois`.
+// the NMS, and feeds `keypoint_rois` back.  Here the chain is: one select+decode kernel and one NMS per foreground class (or, with
+// TEST.SOFT_NMS / TEST.BBOX_VOTE of test.py:766-779, one Soft-NMS block and one voting wave set per class), one limit+emit kernel; the keypoint net then runs on the device-resident `keypoint_rois`.
 //
 // Arithmetic is fp32 in NumPy's operation order (this file is compiled with -ffp-contract=off): `rois / im_scale` is a float32
 // division by float32(scale) (value-based casting of the reference's NumPy 1.14, test.py:216), `boxes * im_scale` for the
@@ -231,6 +231,252 @@ __global__ __launch_bounds__(SEL_THREADS) void det_limit_emit_kernel(const EmitP
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
+// ---- Soft-NMS on the device (lib/utils/cython_nms.pyx:98-203; the host twin is dat_soft_nms_host below) -------------------------
+// One block per (image, class).  The class's rows [x1 y1 x2 y2 score] and their original indices stay in LDS (structure of arrays)
+// for the whole greedy loop.  Iteration i of the reference:
+//   1. arg-max of the scores at positions [i, N) -- strict `<` scan, so the EARLIEST position wins a tie -- swapped into position i;
+//   2. positions (i, N) are re-scored against box i, one after the other; a row whose new score is < threshold is overwritten by
+//      row N - 1, N shrinks and the slot is visited again.
+// Each re-score depends on box i and the position's own row only, so step 2 is: re-score all positions in parallel, then put the
+// rows where the serial swap-with-last walk leaves them (positions decide later ties): with N' = N - #removed, survivors below N'
+// stay, and the holes below N', in ascending order, receive the surviving rows at positions >= N' in DESCENDING order (the walk
+// pulls row N - 1, N - 2, ... into the current hole, dropping the pulled rows that die there).  tests/test_soft_nms_cpu.py pins
+// this restatement to dat_soft_nms_host on tie-heavy inputs.
+// Every loop is bounded by the row count read once at entry (<= SOFT_NMS_CAP, checked on the host): a wrong arrangement is a
+// mismatch, never a hang.
+constexpr int SOFT_THREADS = 256;
+constexpr int SOFT_WAVES = SOFT_THREADS / 64;
+constexpr int SOFT_NMS_CAP = DAT_SOFT_NMS_MAX_BOXES;     // 6 words + 1 flag byte + a 2-byte hole slot per row = 27 B: 54 KB of the 64 KB a block may declare
+
+struct SoftParams {
+    const float* dets;      // rows [n, 5]; block (img, c) reads dets + img * img_stride bytes + c * cls_stride floats
+    const int* n_dev;       // device row counts (n_dev + img * img_stride bytes + c), or nullptr: n_host rows
+    float* out;             // re-scored rows in selection order, same addressing as dets
+    int* inds;              // original row of every output row (nullable), [cap] per class
+    int* ident;             // nullable: ident[k] = k for the output rows (the `keep` list det_limit_emit_kernel walks)
+    int* n_out;             // rows left, addressed like n_dev
+    size_t img_stride;
+    int cls_stride, cap, n_host, method;
+    float sigma, Nt, threshold;
+};
+
+struct SoftBest { float s; int pos; };
+__device__ inline SoftBest soft_better(SoftBest a, SoftBest b) {       // larger score, then the earlier position
+    return (b.s > a.s || (b.s == a.s && b.pos < a.pos)) ? b : a;
+}
+
+__global__ __launch_bounds__(SOFT_THREADS) void soft_nms_kernel(const SoftParams p) {
+    __shared__ float X1[SOFT_NMS_CAP], Y1[SOFT_NMS_CAP], X2[SOFT_NMS_CAP], Y2[SOFT_NMS_CAP], SC[SOFT_NMS_CAP];
+    __shared__ int IDX[SOFT_NMS_CAP];
+    __shared__ unsigned short HOLE[SOFT_NMS_CAP];
+    __shared__ unsigned char DEAD[SOFT_NMS_CAP];
+    __shared__ float w_row[SOFT_WAVES][5];
+    __shared__ int w_idx[SOFT_WAVES], w_pos[SOFT_WAVES];
+    __shared__ unsigned w_scan[SOFT_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int img = blockIdx.x, c = blockIdx.y;
+    const size_t ioff = (size_t)img * p.img_stride;
+    const float* src = (const float*)((const char*)p.dets + ioff) + (size_t)c * p.cls_stride;
+    float* dst = (float*)((char*)p.out + ioff) + (size_t)c * p.cls_stride;
+    int n = p.n_dev ? ((const int*)((const char*)p.n_dev + ioff))[c] : p.n_host;
+    n = max(0, min(n, min(p.cap, SOFT_NMS_CAP)));
+    for (int r = tid; r < n; r += SOFT_THREADS) {
+        X1[r] = src[r * 5 + 0]; Y1[r] = src[r * 5 + 1]; X2[r] = src[r * 5 + 2]; Y2[r] = src[r * 5 + 3]; SC[r] = src[r * 5 + 4];
+        IDX[r] = r;
+    }
+    __syncthreads();
+    int N = n;
+    for (int i = 0; i < n; ++i) {              // (N only shrinks; every thread holds the same N)
+        if (i >= N) break;
+        // row i as it is before the swap: the row that moves to the arg-max position
+        const float ix1 = X1[i], iy1 = Y1[i], ix2 = X2[i], iy2 = Y2[i], is = SC[i];
+        const int ii = IDX[i];
+        SoftBest b = {is, i};
+        for (int q = i + 1 + tid; q < N; q += SOFT_THREADS) {
+            const float s = SC[q];
+            if (b.s < s) { b.s = s; b.pos = q; }       // ascending q per thread: the strict `<` of the reference
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            SoftBest o = {__shfl_xor(b.s, off), __shfl_xor(b.pos, off)};
+            b = soft_better(b, o);
+        }
+        if (lane == 0) {
+            const int m = b.pos;
+            w_row[wave][0] = X1[m]; w_row[wave][1] = Y1[m]; w_row[wave][2] = X2[m]; w_row[wave][3] = Y2[m]; w_row[wave][4] = SC[m];
+            w_idx[wave] = IDX[m]; w_pos[wave] = m;
+        }
+        __syncthreads();
+        int bw = 0;
+        SoftBest best = {w_row[0][4], w_pos[0]};
+#pragma unroll
+        for (int w = 1; w < SOFT_WAVES; ++w) {
+            const SoftBest o = {w_row[w][4], w_pos[w]};
+            const SoftBest r = soft_better(best, o);
+            if (r.pos != best.pos) bw = w;
+            best = r;
+        }
+        const int maxpos = best.pos;
+        const float tx1 = w_row[bw][0], ty1 = w_row[bw][1], tx2 = w_row[bw][2], ty2 = w_row[bw][3];
+        if (tid == 0) {                        // nobody reads position i again in this iteration
+            X1[i] = tx1; Y1[i] = ty1; X2[i] = tx2; Y2[i] = ty2; SC[i] = w_row[bw][4]; IDX[i] = w_idx[bw];
+        }
+        const double tarea = ((double)(tx2 - tx1) + 1.0) * ((double)(ty2 - ty1) + 1.0);
+        int ndead_local = 0;                   // (a flag: did this thread remove a row)
+        for (int q = i + 1 + tid; q < N; q += SOFT_THREADS) {
+            float x1, y1, x2, y2, s;
+            if (q == maxpos) {                 // the swap: this position now holds the old row i
+                x1 = ix1; y1 = iy1; x2 = ix2; y2 = iy2; s = is;
+                X1[q] = x1; Y1[q] = y1; X2[q] = x2; Y2[q] = y2; IDX[q] = ii;
+            } else {
+                x1 = X1[q]; y1 = Y1[q]; x2 = X2[q]; y2 = Y2[q]; s = SC[q];
+            }
+            // (`+ 1` is a DOUBLE constant in the C that Cython emits: see dat_soft_nms_host)
+            const float area = (float)(((double)(x2 - x1) + 1.0) * ((double)(y2 - y1) + 1.0));
+            const float iw = (float)((double)(fminf(tx2, x2) - fmaxf(tx1, x1)) + 1.0);
+            bool dead = false;
+            if (iw > 0) {
+                const float ih = (float)((double)(fminf(ty2, y2) - fmaxf(ty1, y1)) + 1.0);
+                if (ih > 0) {
+                    const float ua = (float)((tarea + (double)area) - (double)(iw * ih));
+                    const float ov = iw * ih / ua;
+                    float weight;
+                    if (p.method == 1) weight = ov > p.Nt ? (float)(1.0 - (double)ov) : 1.f;
+                    else if (p.method == 2) weight = (float)exp((double)(-(ov * ov) / p.sigma));
+                    else weight = ov > p.Nt ? 0.f : 1.f;
+                    s = weight * s;
+                    dead = s < p.threshold;
+                }
+            }
+            SC[q] = s;
+            DEAD[q] = dead ? 1 : 0;
+            ndead_local |= dead ? 1 : 0;
+        }
+        // (the barrier also orders this iteration's LDS writes before the next iteration's reads)
+        if (!__syncthreads_or(ndead_local)) continue;
+        // ---- compaction: holes below N' (ascending) <- survivors at >= N' (descending).  One block scan of the removed flags gives
+        // every removed row its ascending rank r (the holes below N' are the ranks 0 .. #holes - 1) and every survivor at q >= N'
+        // its descending rank among the tail's survivors, (N - 1 - q) - #removed above q
+        const int span = N - (i + 1);
+        const int per = (span + SOFT_THREADS - 1) / SOFT_THREADS;
+        const int lo = min(N, i + 1 + tid * per), hi = min(N, lo + per);
+        unsigned cnt = 0;
+        for (int q = lo; q < hi; ++q) cnt += DEAD[q];
+        unsigned incl = cnt;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned u = __shfl_up(incl, off);
+            if (lane >= off) incl += u;
+        }
+        if (lane == 63) w_scan[wave] = incl;
+        __syncthreads();
+        unsigned before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < SOFT_WAVES; ++w) {
+            if (w < wave) before += w_scan[w];
+            total += w_scan[w];
+        }
+        const int ndead = (int)total;
+        const int N2 = N - ndead;
+        int rank = (int)(before + incl - cnt);             // removed rows before position lo
+        for (int q = lo; q < hi; ++q) {
+            if (DEAD[q]) {
+                if (q < N2) HOLE[rank] = (unsigned short)q;
+                ++rank;
+            }
+        }
+        __syncthreads();
+        rank = (int)(before + incl - cnt);
+        for (int q = lo; q < hi; ++q) {
+            if (DEAD[q]) { ++rank; continue; }
+            if (q >= N2) {
+                const int h = HOLE[(N - 1 - q) - (ndead - rank)];      // the highest survivor fills the lowest hole
+                X1[h] = X1[q]; Y1[h] = Y1[q]; X2[h] = X2[q]; Y2[h] = Y2[q]; SC[h] = SC[q]; IDX[h] = IDX[q];
+            }
+        }
+        N = N2;
+        __syncthreads();
+    }
+    for (int r = tid; r < N; r += SOFT_THREADS) {
+        dst[r * 5 + 0] = X1[r]; dst[r * 5 + 1] = Y1[r]; dst[r * 5 + 2] = X2[r]; dst[r * 5 + 3] = Y2[r]; dst[r * 5 + 4] = SC[r];
+        if (p.inds) ((int*)((char*)p.inds + ioff))[(size_t)c * p.cap + r] = IDX[r];
+        if (p.ident) ((int*)((char*)p.ident + ioff))[(size_t)c * p.cap + r] = r;
+    }
+    if (tid == 0) ((int*)((char*)p.n_out + ioff))[c] = N;
+}
+
+// ---- box voting on the device (lib/utils/boxes.py:294-310): every kept row's coordinates become the score-weighted mean of the
+// class's selected rows (before NMS, original scores) whose IoU with it (lib/utils/cython_bbox.pyx:16-57 in the C float order
+// utils/boxes._iou_matrix restates) is >= thresh; the row's score stays.  One wave per kept row: lane l visits rows l, l + 64, ...
+// and accumulates its five sums in double in that order, then a butterfly adds the lanes -- a fixed order, so runs repeat bit for
+// bit -- and the mean is rounded to float once.
+constexpr int VOTE_THREADS = 256;
+constexpr int VOTE_BLOCKS = 8;
+
+struct VoteParams {
+    const float* top;       // kept rows [., 5]: row k is top[keep ? keep[k] : k]; addressing as SoftParams
+    const int* keep;        // nullable, [cap] per class
+    const int* n_top;       // device counts (nullable: n_top_host)
+    const float* all;       // the class's selected rows [., 5]
+    const int* n_all;       // device counts (nullable: n_all_host)
+    float* out;             // [., 5] voted rows, row k (may alias top when keep == nullptr)
+    int* ident;             // nullable: ident[k] = k
+    size_t img_stride;
+    int cls_stride, cap, n_top_host, n_all_host;
+    float thresh;
+};
+
+__global__ __launch_bounds__(VOTE_THREADS) void box_vote_kernel(const VoteParams p) {
+    const int lane = threadIdx.x & 63;
+    const int img = blockIdx.x, c = blockIdx.y;
+    const size_t ioff = (size_t)img * p.img_stride;
+    const size_t coff = (size_t)c * p.cls_stride;
+    const float* top = (const float*)((const char*)p.top + ioff) + coff;
+    const float* all = (const float*)((const char*)p.all + ioff) + coff;
+    float* out = (float*)((char*)p.out + ioff) + coff;
+    const int n_top = p.n_top ? ((const int*)((const char*)p.n_top + ioff))[c] : p.n_top_host;
+    const int n_all = p.n_all ? ((const int*)((const char*)p.n_all + ioff))[c] : p.n_all_host;
+    const int* keep = p.keep ? (const int*)((const char*)p.keep + ioff) + (size_t)c * p.cap : nullptr;
+    int* ident = p.ident ? (int*)((char*)p.ident + ioff) + (size_t)c * p.cap : nullptr;
+    const int wpb = VOTE_THREADS / 64;
+    for (int k = blockIdx.z * wpb + (threadIdx.x >> 6); k < n_top; k += gridDim.z * wpb) {
+        const float* t = top + (size_t)(keep ? keep[k] : k) * 5;
+        const float b0 = t[0], b1 = t[1], b2 = t[2], b3 = t[3], bs = t[4];
+        const double barea = ((double)(b2 - b0) + 1.0) * ((double)(b3 - b1) + 1.0);
+        double sw = 0., s0 = 0., s1 = 0., s2 = 0., s3 = 0.;
+        for (int m = lane; m < n_all; m += 64) {
+            const float* q = all + (size_t)m * 5;
+            const float q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], w = q[4];
+            const float iw = (float)((double)(fminf(b2, q2) - fmaxf(b0, q0)) + 1.0);
+            const float ih = (float)((double)(fminf(b3, q3) - fmaxf(b1, q1)) + 1.0);
+            float iou = 0.f;
+            if (iw > 0 && ih > 0) {
+                const float qa = (float)(((double)(q2 - q0) + 1.0) * ((double)(q3 - q1) + 1.0));
+                const float inter = iw * ih;
+                const float ua = (float)((barea + (double)qa) - (double)inter);
+                iou = inter / ua;
+            }
+            if (iou >= p.thresh) {
+                const double dw = (double)w;
+                sw += dw; s0 += dw * (double)q0; s1 += dw * (double)q1; s2 += dw * (double)q2; s3 += dw * (double)q3;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            sw += __shfl_xor(sw, off); s0 += __shfl_xor(s0, off); s1 += __shfl_xor(s1, off);
+            s2 += __shfl_xor(s2, off); s3 += __shfl_xor(s3, off);
+        }
+        // In-place use: `out` may be `top` (Soft-NMS + voting) and `ident` may be `keep` (NMS + voting).  Only this wave touches row k of
+        // either, every lane has loaded t[] and keep[k] above, and the butterfly between those loads and the stores below keeps the
+        // wave in step, so lane 0's stores cannot overtake another lane's load.
+        if (lane == 0) {
+            float* o = out + (size_t)k * 5;
+            o[0] = (float)(s0 / sw); o[1] = (float)(s1 / sw); o[2] = (float)(s2 / sw); o[3] = (float)(s3 / sw); o[4] = bs;
+            if (ident) ident[k] = k;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -241,9 +487,18 @@ size_t dat_box_results_workspace_bytes(int roi_cap, int num_classes, int T) {
            dat_nms_ws_bytes(roi_cap, T);
 }
 
-int dat_box_results_batch(dat_ctx* ctx, dat_stream s, const float* rois, const int* n_rois, int roi_cap, const float* cls_prob,
-                          int prob_ld, const float* bbox_pred, int pred_ld, const dat_det_desc* d, int n_images, void* workspace,
-                          int out_cap, float* dets_out, float* keypoint_rois, int* n_out) {
+// + the re-scored / voted rows [K-1][roi_cap][5] that Soft-NMS and box voting hand to det_limit_emit_kernel
+size_t dat_box_results_ex_workspace_bytes(int roi_cap, int num_classes, int T, const dat_det_opts* o) {
+    const size_t base = dat_box_results_workspace_bytes(roi_cap, num_classes, T);
+    if (!o || (!o->soft_nms_enabled && !o->bbox_vote_enabled)) return base;
+    const int nc = num_classes > 1 ? num_classes - 1 : 1;
+    return base + align_up((size_t)nc * roi_cap * (4 * T + 1) * 4);
+}
+
+// o == nullptr: hard NMS, no voting (dat_box_results_batch); otherwise at least one of the two switches is on
+static int box_results_impl(dat_ctx* ctx, dat_stream s, const float* rois, const int* n_rois, int roi_cap, const float* cls_prob,
+                            int prob_ld, const float* bbox_pred, int pred_ld, const dat_det_desc* d, const dat_det_opts* o, int n_images,
+                            void* workspace, int out_cap, float* dets_out, float* keypoint_rois, int* n_out) {
     DAT_ENFORCE(ctx, rois && n_rois && cls_prob && bbox_pred && d && workspace && dets_out && keypoint_rois && n_out,
                 "box_results: null argument");
     DAT_ENFORCE(ctx, n_images >= 1 && n_images <= MAX_IMAGES, "box_results: %d images per launch (1..%d)", n_images, MAX_IMAGES);
@@ -253,14 +508,23 @@ int dat_box_results_batch(dat_ctx* ctx, dat_stream s, const float* rois, const i
                 "box_results: row strides %d / %d too small for %d classes x T %d", prob_ld, pred_ld, d->num_classes, d->T);
     hipStream_t st = (hipStream_t)s;
     const int nc = d->num_classes - 1, T = d->T, cols = 4 * T + 1;
-    const size_t img_ws = dat_box_results_workspace_bytes(roi_cap, d->num_classes, T);
+    const bool soft = o && o->soft_nms_enabled, vote = o && o->bbox_vote_enabled;
+    if (soft || vote) {
+        DAT_ENFORCE(ctx, T == 1, "box_results: Soft-NMS / box voting are defined for boxes, not for tubes of %d frames", T);
+        DAT_ENFORCE(ctx, !soft || (o->soft_nms_method >= 0 && o->soft_nms_method <= 2), "box_results: Soft-NMS method %d (0 hard, 1 linear, 2 gaussian)",
+                    soft ? o->soft_nms_method : 0);
+        DAT_ENFORCE(ctx, !soft || roi_cap <= SOFT_NMS_CAP, "box_results: Soft-NMS holds a class's rows in LDS: roi capacity %d > %d", roi_cap,
+                    SOFT_NMS_CAP);
+    }
+    const size_t img_ws = dat_box_results_ex_workspace_bytes(roi_cap, d->num_classes, T, o);
     char* ws = (char*)workspace;
     size_t off = 0;
     float* dets = (float*)(ws + off); off += align_up((size_t)nc * roi_cap * cols * 4);
     int* keep = (int*)(ws + off); off += align_up((size_t)nc * roi_cap * 4);
     int* n_sel = (int*)(ws + off); off += align_up((size_t)nc * 4);
     int* n_keep = (int*)(ws + off); off += align_up((size_t)nc * 4);
-    char* nms_ws = ws + off;
+    char* nms_ws = ws + off; off += dat_nms_ws_bytes(roi_cap, T);
+    float* rows2 = (float*)(ws + off);     // (Soft-NMS / voting only: the workspace ends at nms_ws otherwise)
     DetParams p;
     memset(&p, 0, sizeof(p));
     p.rois = rois; p.n_rois = n_rois; p.prob = cls_prob; p.pred = bbox_pred;
@@ -281,14 +545,78 @@ int dat_box_results_batch(dat_ctx* ctx, dat_stream s, const float* rois, const i
         float* dets_c = dets + (size_t)c * roi_cap * cols;
         if (p.T == 1) hipLaunchKernelGGL(det_select_kernel<1>, dim3(ni), dim3(SEL_THREADS), 0, st, p, c + 1, dets_c, n_sel + c);
         else hipLaunchKernelGGL(det_select_kernel<DET_MAX_T>, dim3(ni), dim3(SEL_THREADS), 0, st, p, c + 1, dets_c, n_sel + c);
+        if (soft) continue;                // (test.py:766-772: Soft-NMS replaces the NMS)
         int rc = dat_nms_impl_batch(ctx, st, nms_ws, img_ws, dets_c, img_ws / 4, 0, n_sel + c, (int)(img_ws / 4), roi_cap, T, d->nms_thresh,
                                     0, 0, keep + (size_t)c * roi_cap, (int)(img_ws / 4), n_keep + c, (int)(img_ws / 4), n_images);
         if (rc != DAT_OK) return rc;
     }
-    e.dets = dets; e.keep = keep; e.n_keep = n_keep; e.K = d->num_classes; e.T = T; e.cap = roi_cap; e.D = d->detections_per_im;
+    if (soft) {
+        // every (image, class) at once: rows2 = the re-scored rows in selection order, keep = 0, 1, 2, ... over them
+        SoftParams sp;
+        memset(&sp, 0, sizeof(sp));
+        sp.dets = dets; sp.n_dev = n_sel; sp.out = rows2; sp.ident = keep; sp.n_out = n_keep; sp.img_stride = img_ws;
+        sp.cls_stride = roi_cap * cols; sp.cap = roi_cap; sp.method = o->soft_nms_method; sp.sigma = o->soft_nms_sigma;
+        sp.Nt = d->nms_thresh; sp.threshold = o->soft_nms_score_thresh;
+        hipLaunchKernelGGL(soft_nms_kernel, dim3(ni, nc), dim3(SOFT_THREADS), 0, st, sp);
+    }
+    if (vote) {
+        // (test.py:776-779) the kept rows -- dets[keep] after the NMS, rows2 after Soft-NMS -- voted by the class's selected rows
+        VoteParams vp;
+        memset(&vp, 0, sizeof(vp));
+        vp.top = soft ? rows2 : dets; vp.keep = soft ? nullptr : keep; vp.n_top = n_keep; vp.all = dets; vp.n_all = n_sel;
+        vp.out = rows2; vp.ident = soft ? nullptr : keep; vp.img_stride = img_ws; vp.cls_stride = roi_cap * cols; vp.cap = roi_cap;
+        vp.thresh = o->bbox_vote_thresh;
+        hipLaunchKernelGGL(box_vote_kernel, dim3(ni, nc, VOTE_BLOCKS), dim3(VOTE_THREADS), 0, st, vp);
+    }
+    e.dets = (soft || vote) ? rows2 : dets; e.keep = keep; e.n_keep = n_keep; e.K = d->num_classes; e.T = T; e.cap = roi_cap; e.D = d->detections_per_im;
     e.out_cap = out_cap; e.img_ws = img_ws; e.dets_out = dets_out; e.kp_rois = keypoint_rois; e.n_out = n_out;
     hipLaunchKernelGGL(det_limit_emit_kernel, dim3(ni), dim3(SEL_THREADS), 0, st, e);
     DAT_CHECK_LAUNCH(ctx, "box_results");
+    return DAT_OK;
+}
+
+int dat_box_results_batch(dat_ctx* ctx, dat_stream s, const float* rois, const int* n_rois, int roi_cap, const float* cls_prob,
+                          int prob_ld, const float* bbox_pred, int pred_ld, const dat_det_desc* d, int n_images, void* workspace,
+                          int out_cap, float* dets_out, float* keypoint_rois, int* n_out) {
+    return box_results_impl(ctx, s, rois, n_rois, roi_cap, cls_prob, prob_ld, bbox_pred, pred_ld, d, nullptr, n_images, workspace, out_cap,
+                            dets_out, keypoint_rois, n_out);
+}
+
+int dat_box_results_ex(dat_ctx* ctx, dat_stream s, const float* rois, const int* n_rois, int roi_cap, const float* cls_prob, int prob_ld,
+                       const float* bbox_pred, int pred_ld, const dat_det_desc* d, const dat_det_opts* o, int n_images, void* workspace,
+                       int out_cap, float* dets_out, float* keypoint_rois, int* n_out) {
+    DAT_ENFORCE(ctx, o, "box_results_ex: null options");
+    const bool plain = !o->soft_nms_enabled && !o->bbox_vote_enabled;     // both off: dat_box_results_batch itself
+    return box_results_impl(ctx, s, rois, n_rois, roi_cap, cls_prob, prob_ld, bbox_pred, pred_ld, d, plain ? nullptr : o, n_images, workspace,
+                            out_cap, dets_out, keypoint_rois, n_out);
+}
+
+// Soft-NMS of n <= DAT_SOFT_NMS_MAX_BOXES device rows [n, 5]: the device twin of dat_soft_nms_host below.
+int dat_soft_nms(dat_ctx* ctx, dat_stream s, const float* dets, int n, float sigma, float Nt, float threshold, int method, float* dets_out,
+                 int* inds_out, int* n_out) {
+    DAT_ENFORCE(ctx, dets_out && inds_out && n_out && (dets || n == 0), "soft_nms: null argument");
+    DAT_ENFORCE(ctx, n >= 0 && n <= SOFT_NMS_CAP, "soft_nms: %d boxes (0..%d: the rows stay in LDS)", n, SOFT_NMS_CAP);
+    DAT_ENFORCE(ctx, method >= 0 && method <= 2, "soft_nms: method %d (0 hard, 1 linear, 2 gaussian)", method);
+    SoftParams sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.dets = dets; sp.n_host = n; sp.out = dets_out; sp.inds = inds_out; sp.n_out = n_out; sp.cap = SOFT_NMS_CAP;
+    sp.method = method; sp.sigma = sigma; sp.Nt = Nt; sp.threshold = threshold;
+    hipLaunchKernelGGL(soft_nms_kernel, dim3(1, 1), dim3(SOFT_THREADS), 0, (hipStream_t)s, sp);
+    DAT_CHECK_LAUNCH(ctx, "soft_nms");
+    return DAT_OK;
+}
+
+// Box voting of n_top device rows [n_top, 5] by n_all device rows [n_all, 5] -> out [n_top, 5] (out may be top_dets).
+int dat_box_voting(dat_ctx* ctx, dat_stream s, const float* top_dets, int n_top, const float* all_dets, int n_all, float thresh, float* out) {
+    DAT_ENFORCE(ctx, n_top >= 0 && n_all >= 0 && (n_top == 0 || (top_dets && all_dets && out)), "box_voting: null argument or negative count");
+    if (n_top == 0) return DAT_OK;
+    DAT_ENFORCE(ctx, n_all >= 1, "box_voting: %d rows to refine and no row to vote with (the weight sum would be zero)", n_top);
+    VoteParams vp;
+    memset(&vp, 0, sizeof(vp));
+    vp.top = top_dets; vp.all = all_dets; vp.out = out; vp.n_top_host = n_top; vp.n_all_host = n_all; vp.thresh = thresh;
+    const int blocks = min((n_top + VOTE_THREADS / 64 - 1) / (VOTE_THREADS / 64), 1024);
+    hipLaunchKernelGGL(box_vote_kernel, dim3(1, 1, blocks), dim3(VOTE_THREADS), 0, (hipStream_t)s, vp);
+    DAT_CHECK_LAUNCH(ctx, "box_voting");
     return DAT_OK;
 }
 
@@ -302,7 +630,7 @@ int dat_box_results(dat_ctx* ctx, dat_stream s, const float* rois, const int* n_
 // Soft-NMS on the HOST (lib/utils/cython_nms.pyx:98-203; caller lib/core/nms_wrapper.py:29-46, lib/core/test.py:766-772): the
 // greedy in-place re-scoring loop in C float arithmetic, statement for statement what Cython emits for the reference's .pyx
 // (differences in float, `+ 1` and the area products in double, the Gaussian weight through a double exp, the
-// discard-by-swap-with-last that makes the result order-dependent).  Plain host code: the algorithm is sequential by construction and off in every shipped config.
+// discard-by-swap-with-last that makes the result order-dependent).  Plain host code: the comparison path of dat_soft_nms (soft_nms_kernel above) and what core/nms_wrapper.soft_nms runs for host arrays.
 int dat_soft_nms_host(const float* boxes_in, int n, float sigma, float Nt, float threshold, int method, float* boxes_out,
                       int* inds_out, int* n_out) {
     if (!boxes_in || !boxes_out || !inds_out || !n_out || n < 0 || method < 0 || method > 2) return DAT_ERR_ARG;

@@ -62,6 +62,11 @@ class DetDesc(C.Structure):
                 ('reg_weights', C.c_float * 4), ('xform_clip', C.c_float), ('score_thresh', C.c_float), ('nms_thresh', C.c_float)]
 
 
+class DetOpts(C.Structure):
+    _fields_ = [('soft_nms_enabled', C.c_int), ('soft_nms_method', C.c_int), ('soft_nms_sigma', C.c_float),
+                ('soft_nms_score_thresh', C.c_float), ('bbox_vote_enabled', C.c_int), ('bbox_vote_thresh', C.c_float)]
+
+
 class RpnLevel(C.Structure):
     _fields_ = [('H', C.c_int), ('W', C.c_int), ('A', C.c_int), ('T', C.c_int), ('feat_stride', C.c_float),
                 ('cstride', C.c_int), ('logit_off', C.c_int), ('delta_off', C.c_int), ('frame', C.c_int),
@@ -127,6 +132,10 @@ _PROTOS = {
     'dat_box_results_workspace_bytes': (C.c_size_t, [_i, _i, _i]),
     'dat_box_results': (_i, [_p, _p, _p, _p, _i, _p, _i, _p, _i, C.POINTER(DetDesc), _p, _i, _p, _p, _p]),
     'dat_box_results_batch': (_i, [_p, _p, _p, _p, _i, _p, _i, _p, _i, C.POINTER(DetDesc), _i, _p, _i, _p, _p, _p]),
+    'dat_box_results_ex_workspace_bytes': (C.c_size_t, [_i, _i, _i, C.POINTER(DetOpts)]),
+    'dat_box_results_ex': (_i, [_p, _p, _p, _p, _i, _p, _i, _p, _i, C.POINTER(DetDesc), C.POINTER(DetOpts), _i, _p, _i, _p, _p, _p]),
+    'dat_soft_nms': (_i, [_p, _p, _p, _i, _f, _f, _f, _i, _p, _p, _p]),
+    'dat_box_voting': (_i, [_p, _p, _p, _i, _p, _i, _f, _p]),
     'dat_soft_nms_host': (_i, [C.POINTER(_f), _i, _f, _f, _f, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     'dat_deconv_k4s2_weights': (_i, [_p, _p, _p, _i, _i, _p]),
     'dat_kps_finalize': (_i, [_p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),

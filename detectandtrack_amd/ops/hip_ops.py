@@ -940,13 +940,46 @@ def nms_host(dets_np, thresh):
     return keep[:num.value]
 
 
+SOFT_NMS_METHODS = {'hard': 0, 'linear': 1, 'gaussian': 2}
+SOFT_NMS_MAX_BOXES = 2048      # DAT_SOFT_NMS_MAX_BOXES: a class's rows stay in LDS
+
+
+def soft_nms(dets, sigma=0.5, overlap_thresh=0.3, score_thresh=0.001, method='linear'):
+    """dat_soft_nms (lib/utils/cython_nms.pyx:98-203 on the device): dets CUDA fp32 [n <= SOFT_NMS_MAX_BOXES, 5]; returns
+    (re-scored rows [n, 5], original row indices int32 [n], count int32[1]) on the device -- the first count[0] rows are the result,
+    in the order the greedy loop leaves them; no host synchronisation."""
+    if dets.dim() != 2 or dets.shape[1] != 5:
+        raise NotImplementedError('Need to handle tubes..')       # (lib/core/nms_wrapper.py:34-35)
+    assert dets.dtype == torch.float32
+    m = SOFT_NMS_METHODS[method] if isinstance(method, str) else int(method)
+    n = int(dets.shape[0])
+    out = torch.empty((max(n, 1), 5), dtype=torch.float32, device=dets.device)
+    inds = torch.empty((max(n, 1),), dtype=torch.int32, device=dets.device)
+    cnt = torch.empty((1,), dtype=torch.int32, device=dets.device)
+    ctx().call('dat_soft_nms', _stream(), _ptr(dets.contiguous()), n, C.c_float(sigma), C.c_float(overlap_thresh), C.c_float(score_thresh), m,
+               _ptr(out), _ptr(inds), _ptr(cnt))
+    return out[:n], inds[:n], cnt
+
+
+def box_voting(top_dets, all_dets, thresh):
+    """dat_box_voting (lib/utils/boxes.py:294-310 on the device): CUDA fp32 [n_top, 5], [n_all, 5] -> voted rows [n_top, 5]."""
+    assert top_dets.dtype == all_dets.dtype == torch.float32 and top_dets.shape[1] == 5 and all_dets.shape[1] == 5
+    out = torch.empty_like(top_dets, memory_format=torch.contiguous_format)
+    ctx().call('dat_box_voting', _stream(), _ptr(top_dets.contiguous()), int(top_dets.shape[0]), _ptr(all_dets.contiguous()),
+               int(all_dets.shape[0]), C.c_float(thresh), _ptr(out))
+    return out
+
+
 def box_results(rois, n_rois, cls_prob, bbox_pred, num_classes, T, im_scale, im_shape, reg_weights, xform_clip, score_thresh,
-                nms_thresh, detections_per_im, out_cap, cls_agnostic=False, n_images=1):
+                nms_thresh, detections_per_im, out_cap, cls_agnostic=False, n_images=1, soft_nms=None, bbox_vote=None):
     """dat_box_results (lib/core/test.py:215-252, 750-806, 78-123 on the device).  rois CUDA fp32 [cap, 4T+1] with the DEVICE count
     n_rois (int32[1]); cls_prob [R, K], bbox_pred [R, K*4T] CUDA fp32.  Returns (dets [out_cap, 4T+2], keypoint_rois [out_cap, 4T+1],
     n_out int32[2]) on the device -- no host synchronisation.  n_images > 1 (dat_box_results_batch): rois [n_images * cap, ...] with
     counts n_rois[n_images], im_scale / im_shape sequences per image; returns dets [n_images * out_cap, 4T+2], keypoint_rois
-    [n_images * out_cap, 4T+1] (col 0 = image index) and n_out int32[n_images, 2]."""
+    [n_images * out_cap, 4T+1] (col 0 = image index) and n_out int32[n_images, 2].
+    soft_nms: None | dict(method='hard'|'linear'|'gaussian', sigma, score_thresh) -- TEST.SOFT_NMS in place of the NMS (overlap
+    threshold = nms_thresh; detections carry the re-scored scores); bbox_vote: None | the voting IoU threshold (TEST.BBOX_VOTE).
+    Either one routes to dat_box_results_ex (boxes only: T == 1)."""
     ni = int(n_images)
     cap = int(rois.shape[0]) // ni
     assert cap * ni == int(rois.shape[0])
@@ -965,12 +998,28 @@ def box_results(rois, n_rois, cls_prob, bbox_pred, num_classes, T, im_scale, im_
             d.reg_weights[k] = float(reg_weights[k])
         d.xform_clip, d.score_thresh, d.nms_thresh = float(xform_clip), float(score_thresh), float(nms_thresh)
     cols = 4 * T + 1
-    wsb = torch.empty(ni * L.lib().dat_box_results_workspace_bytes(cap, int(num_classes), int(T)), dtype=torch.uint8, device=rois.device)
+    opts = None
+    if soft_nms is not None or bbox_vote is not None:
+        opts = L.DetOpts()
+        if soft_nms is not None:
+            m = soft_nms.get('method', 'linear')
+            opts.soft_nms_enabled, opts.soft_nms_method = 1, SOFT_NMS_METHODS[m] if isinstance(m, str) else int(m)
+            opts.soft_nms_sigma, opts.soft_nms_score_thresh = float(soft_nms.get('sigma', 0.5)), float(soft_nms.get('score_thresh', 0.0001))
+        if bbox_vote is not None:
+            opts.bbox_vote_enabled, opts.bbox_vote_thresh = 1, float(bbox_vote)
+        ws_bytes = L.lib().dat_box_results_ex_workspace_bytes(cap, int(num_classes), int(T), C.byref(opts))
+    else:
+        ws_bytes = L.lib().dat_box_results_workspace_bytes(cap, int(num_classes), int(T))
+    wsb = torch.empty(ni * ws_bytes, dtype=torch.uint8, device=rois.device)
     dets = torch.empty((ni * out_cap, cols + 1), dtype=torch.float32, device=rois.device)
     kp = torch.empty((ni * out_cap, cols), dtype=torch.float32, device=rois.device)
     n_out = torch.empty((2,) if ni == 1 else (ni, 2), dtype=torch.int32, device=rois.device)
     assert rois.dtype == cls_prob.dtype == bbox_pred.dtype == torch.float32 and rois.is_contiguous()
     assert n_rois.numel() == ni
+    if opts is not None:
+        ctx().call('dat_box_results_ex', _stream(), _ptr(rois), _ptr(n_rois), cap, _ptr(cls_prob), int(cls_prob.stride(0)), _ptr(bbox_pred),
+                   int(bbox_pred.stride(0)), ds, C.byref(opts), ni, _ptr(wsb), int(out_cap), _ptr(dets), _ptr(kp), _ptr(n_out))
+        return dets, kp, n_out
     ctx().call('dat_box_results_batch', _stream(), _ptr(rois), _ptr(n_rois), cap, _ptr(cls_prob), int(cls_prob.stride(0)), _ptr(bbox_pred),
                int(bbox_pred.stride(0)), ds, ni, _ptr(wsb), int(out_cap), _ptr(dets), _ptr(kp), _ptr(n_out))
     return dets, kp, n_out

@@ -287,7 +287,8 @@ void _nms(int* keep_out, int* num_out, const float* boxes_host, int boxes_num, i
  * Replaces the reference's host glue (a device sync + NumPy per clip): lib/core/test.py:215-252 (rois / im_scale, bbox_transform
  * with MODEL.BBOX_REG_WEIGHTS, clip to the image), :750-806 box_results_with_nms_and_limit (per class: score > SCORE_THRESH,
  * NMS at TEST.NMS; then TEST.DETECTIONS_PER_IM over all classes: scores >= the D-th best) and :78-123 _get_rois_blob for the
- * keypoint net.  Soft-NMS / box voting are not covered here (host path, lib/utils/cython_nms.pyx:98-203). */
+ * keypoint net.  TEST.SOFT_NMS (lib/utils/cython_nms.pyx:98-203) and TEST.BBOX_VOTE (lib/utils/boxes.py:294-310) run on the device
+ * too: dat_box_results_ex below. */
 typedef struct {
     int num_classes;            /* K incl. background (class 0 is skipped) */
     int T;                      /* frames per tube (1 = boxes) */
@@ -320,9 +321,45 @@ int dat_box_results_batch(dat_ctx* ctx, dat_stream s, const float* rois, const i
                           int prob_ld, const float* bbox_pred, int pred_ld, const dat_det_desc* d, int n_images, void* workspace,
                           int out_cap, float* dets_out, float* keypoint_rois, int* n_out);
 
+/* ---- Soft-NMS and box voting on the device (lib/core/test.py:766-779) ----------------------------------------------------------
+ * Soft-NMS keeps a class's rows in LDS for the whole greedy loop (one block per image and class), so it accepts at most
+ * DAT_SOFT_NMS_MAX_BOXES rows (2048 x 27 bytes = 54 KB of the 64 KB a block may declare; the reference's TEST.RPN_POST_NMS_TOP_N
+ * is 1000); more is a DAT_ERR_ARG.  Boxes only (T = 1): the reference has no Soft-NMS for tubes (lib/core/nms_wrapper.py:34-35). */
+#define DAT_SOFT_NMS_MAX_BOXES 2048
+/* The device twin of dat_soft_nms_host: dets fp32 [n, 5] -> dets_out [*n_out <= n, 5] (re-scored, in the order the greedy loop leaves
+ * them), inds_out (rows of dets), n_out int32[1]; all DEVICE pointers, buffers of n rows, no host synchronisation.  method 0 = hard,
+ * 1 = linear, 2 = gaussian.  Rows, order and indices are those of the reference's compiled Cython; scores are bit-identical for
+ * methods 0 and 1 and within one float ulp per re-scoring for method 2 (the device's double exp is not correctly rounded). */
+int dat_soft_nms(dat_ctx* ctx, dat_stream s, const float* dets, int n, float sigma, float Nt, float threshold, int method, float* dets_out,
+                 int* inds_out, int* n_out);
+/* box_voting (lib/utils/boxes.py:294-310): out [n_top, 5] = top_dets with the four coordinates of every row replaced by the
+ * score-weighted mean of the all_dets [n_all, 5] rows whose float32 IoU (lib/utils/cython_bbox.pyx:16-57) with it is >= thresh; the
+ * score stays.  DEVICE pointers; sums in double in a fixed order (runs repeat bit for bit), rounded to float once; out may be
+ * top_dets.  n_all >= 1 when n_top > 0 (DAT_ERR_ARG otherwise); a row whose voters' scores sum to zero gets NaN coordinates, as a
+ * zero weight sum is an error in the reference (all_dets normally holds the row itself, IoU 1, with a positive score). */
+int dat_box_voting(dat_ctx* ctx, dat_stream s, const float* top_dets, int n_top, const float* all_dets, int n_all, float thresh, float* out);
+/* dat_box_results_batch with the two switches of lib/core/test.py:766-779.  Soft-NMS replaces the per-class NMS (overlap threshold =
+ * dat_det_desc.nms_thresh, as the reference passes TEST.NMS) and the detections carry the RE-SCORED scores, on which the
+ * DETECTIONS_PER_IM rule (and n_out[1]) then works; voting replaces the kept boxes' coordinates, and keypoint_rois are formed from
+ * the voted boxes.  With both switches off this IS dat_box_results_batch (same code, same workspace size, byte-identical outputs).
+ * Requires T == 1 when a switch is on, and roi_cap <= DAT_SOFT_NMS_MAX_BOXES with Soft-NMS.  workspace: n_images x
+ * dat_box_results_ex_workspace_bytes. */
+typedef struct {
+    int soft_nms_enabled;         /* TEST.SOFT_NMS.ENABLED */
+    int soft_nms_method;          /* 0 hard, 1 linear, 2 gaussian (TEST.SOFT_NMS.METHOD) */
+    float soft_nms_sigma;         /* TEST.SOFT_NMS.SIGMA */
+    float soft_nms_score_thresh;  /* rows re-scored below it are dropped (the reference passes 0.0001) */
+    int bbox_vote_enabled;        /* TEST.BBOX_VOTE.ENABLED */
+    float bbox_vote_thresh;       /* TEST.BBOX_VOTE.VOTE_TH */
+} dat_det_opts;
+size_t dat_box_results_ex_workspace_bytes(int roi_cap, int num_classes, int T, const dat_det_opts* o);
+int dat_box_results_ex(dat_ctx* ctx, dat_stream s, const float* rois, const int* n_rois, int roi_cap, const float* cls_prob, int prob_ld,
+                       const float* bbox_pred, int pred_ld, const dat_det_desc* d, const dat_det_opts* o, int n_images, void* workspace,
+                       int out_cap, float* dets_out, float* keypoint_rois, int* n_out);
+
 /* Soft-NMS, HOST pointers, host arithmetic (lib/utils/cython_nms.pyx:98-203 statement for statement in C float): boxes_in
  * [n, 5] -> boxes_out [*n_out <= n, 5] (re-scored, in the order the greedy loop leaves them) and inds_out (rows of boxes_in).
- * method 0 = hard, 1 = linear, 2 = gaussian (nms_wrapper.py:37).  Buffers hold n rows.  Off in every shipped config. */
+ * method 0 = hard, 1 = linear, 2 = gaussian (nms_wrapper.py:37).  Buffers hold n rows.  The comparison path of dat_soft_nms. */
 int dat_soft_nms_host(const float* boxes_in, int n, float sigma, float Nt, float threshold, int method, float* boxes_out,
                       int* inds_out, int* n_out);
 
