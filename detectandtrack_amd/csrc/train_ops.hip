@@ -252,7 +252,8 @@ struct WgradDirectParams {
     int ntaps, ksplit, n_ci_tiles, n_co_tiles;
     int atomic;                 // add into G with atomics (K split, or a caller-owned accumulator: dat_conv3d_wgrad_acc) instead of storing
     unsigned p_begin, p_end;    // output positions [p_begin, p_end) carry a non-zero gradient (frame window)
-    unsigned how, wo_magic;     // Ho * Wo; ceil(2^32 / Wo): row = umulhi(position in frame, wo_magic) (Ho * Wo * Wo < 2^32 checked by the launcher)
+    unsigned how, wo_magic;     // Ho * Wo; ceil(2^32 / Wo): row = umulhi(position in frame, wo_magic), exact while position x Wo < 2^32 (checked by
+                                // wgrad_direct_eligible); 0 for a 1 x 1 map.  A one-column map arrives relabelled as a one-row strip (column_strip)
 };
 
 constexpr int WD_PITCH = 320;                 // bytes per staged position row: 128 channels + 64 B (bank rotation, see above)
@@ -1243,8 +1244,31 @@ static bool wgrad_direct_eligible(const dat_ctx* ctx, const dat_conv_desc* d, in
     int Ho, Wo;
     dat_conv3d_out_shape(d, &Ho, &Wo);
     const long long npos_out = (long long)d->frames * Ho * Wo, npos_in = (long long)d->frames * d->H * d->W;
+    // A one-column output map with several rows (Wo == 1 < Ho): wgrad_pw_kernel and wgrad_direct_kernel split a position of a frame into
+    // (row, column) with a multiply-high by ceil(2^32 / Wo), which no 32-bit constant expresses for Wo == 1.  Both launchers relabel such a
+    // map the same way, as ONE row of Ho columns (column_strip below) -- possible when the layer has no spatial taps, i.e. no bound to check
+    // across the relabelled axis; a layer WITH spatial taps on such a map (3 x 3 at stride 2 on a map one or two columns wide) takes the
+    // re-pack kernels.  The nine-tap kernel walks 8 x 8 patches and has no such split.
+    const bool nine_tap = d->KH == 3 && d->KW == 3 && d->stride_h == 1 && d->pad_h == 1 && d->pad_w == 1 && (ctx->dbg_wgrad_direct & 2) == 0;
+    const bool no_spatial_taps = d->KH == 1 && d->KW == 1 && d->pad_h == 0 && d->pad_w == 0;
+    if (Wo == 1 && Ho > 1 && !nine_tap && !no_spatial_taps) return false;
+    // (the multiply-high is exact while position-in-frame x divisor < 2^32; the relabelled strip divides its positions, < Ho, by Ho)
+    const long long split_range = Wo == 1 ? (long long)Ho * Ho : (long long)Ho * Wo * Wo;
     return d->dtype == DAT_BF16 && ctx->dbg_wgrad_direct && d->Cin % 64 == 0 && g_cstride % 64 == 0 && npos_out < (1ll << 31) && npos_in < (1ll << 31) &&
-           (long long)Ho * Wo * Wo < (1ll << 32);
+           split_range < (1ll << 32);
+}
+
+// The geometry of a layer without spatial taps whose output map is one column of Ho > 1 rows, as the position split of the two kernels
+// can address it -- ONE convention for both launchers: the output becomes one row of Ho columns (row = position / Ho = 0, column =
+// position, through the ordinary multiply-high), the input frame one row of H * W pixels read with stride s * W: input pixel (s * oy, 0)
+// of frame f is row (f * H + s * oy) * W = f * (H * W) + (s * W) * oy of the tensor.  Every other map is left exactly as it is.
+static void column_strip(int* Ho, int* Wo, int* H, int* W, int* stride) {
+    if (*Wo != 1 || *Ho <= 1) return;
+    *Wo = *Ho;
+    *Ho = 1;
+    *stride *= *W;
+    *W *= *H;
+    *H = 1;
 }
 
 // ---- pointwise layers: plan (tile shape, geometry) and grouped launch ------------------------------------------------------------
@@ -1266,7 +1290,9 @@ static int pw_plan(dat_ctx* ctx, const dat_conv_desc* d, const void* x, const vo
     memset(&q, 0, sizeof(q));
     q.g = (const char*)g; q.x = (const char*)x; q.G = Gt;
     q.Cout = Cout_real; q.Cin = Cin_real; q.g_cs = g_cstride; q.x_cs = d->Cin;
-    q.H = d->H; q.W = d->W; q.Wo = Wo; q.stride = d->stride_h;
+    q.H = d->H; q.W = d->W; q.stride = d->stride_h;
+    column_strip(&Ho, &Wo, &q.H, &q.W, &q.stride);      // (a one-column map becomes a one-row strip)
+    q.Wo = Wo;
     q.how = (unsigned)(Ho * Wo);
     q.how_magic = q.how == 1 ? 0xffffffffu : (unsigned)(0x100000000ull / q.how);
     q.wo_magic = Wo == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)Wo - 1) / (unsigned)Wo);
@@ -1437,11 +1463,12 @@ static int wgrad_impl(dat_ctx* ctx, dat_stream s_, const dat_conv_desc* d, const
         wp.g = (const char*)g; wp.x = (const char*)x; wp.G = Gt;
         wp.Cout = Cout_real; wp.Cin = Cin_real; wp.g_cs = g_cstride; wp.x_cs = d->Cin;
         wp.T = d->T; wp.H = d->H; wp.W = d->W; wp.Ho = Ho; wp.Wo = Wo; wp.stride = s;
+        column_strip(&wp.Ho, &wp.Wo, &wp.H, &wp.W, &wp.stride);     // (kT x 1 x 1 on a one-column map, see wgrad_direct_eligible: a one-row strip)
         wp.KT = d->KT; wp.KH = d->KH; wp.KW = d->KW; wp.pt = d->pad_t; wp.ph = d->pad_h; wp.pw = d->pad_w;
         wp.ntaps = d->KT * d->KH * d->KW;
         wp.n_co_tiles = (Cout_real + 127) / 128; wp.n_ci_tiles = (Cin_real + 127) / 128;
         wp.how = (unsigned)(Ho * Wo);
-        wp.wo_magic = Wo == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)Wo - 1) / (unsigned)Wo);
+        wp.wo_magic = wp.Wo == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)wp.Wo - 1) / (unsigned)wp.Wo);
         wp.p_begin = 0; wp.p_end = (unsigned)npos_out;
         if (d->out_tn > 0 && clips == 1) {   // g is non-zero only in frames [out_t0, out_t0 + out_tn) of the clip
             DAT_ENFORCE(ctx, d->out_t0 >= 0 && d->out_t0 + d->out_tn <= d->T, "conv3d_wgrad: gradient frames [%d, %d) outside T %d",

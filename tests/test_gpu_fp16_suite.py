@@ -1,8 +1,8 @@
 """The fp16 library build (libdat_hip_f16.so: the same sources with -DDAT_H16_IS_FP16, cfg.HIP.DTYPE 'fp16'), kernel by kernel.
 
 The 16-bit format belongs to the loaded library, so the format-generic kernel tests run again in ONE child process started with
-DAT_H16=fp16: tests/test_gpu_kernels.py, tests/test_gpu_fp16_edges.py, tests/test_gpu_infer_kernels.py and the persistent-kernel test
-of tests/test_gpu_model.py.
+DAT_H16=fp16: tests/test_gpu_kernels.py, tests/test_gpu_fp16_edges.py, tests/test_gpu_infer_kernels.py, tests/test_gpu_wgrad.py (the
+weight-gradient kernels) and the persistent-kernel test of tests/test_gpu_model.py.
 The parent reads the child's JUnit report: no failure or error, every skip is a bf16-only test, and one test per kernel family (plus
 the NMS and proposal goldens) is among the passed -- so that a collection mistake cannot pass for a green run.  The child is never
 retried."""
@@ -16,12 +16,13 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD_FILES = ['tests/test_gpu_kernels.py', 'tests/test_gpu_fp16_edges.py', 'tests/test_gpu_infer_kernels.py',
+CHILD_FILES = ['tests/test_gpu_kernels.py', 'tests/test_gpu_fp16_edges.py', 'tests/test_gpu_infer_kernels.py', 'tests/test_gpu_wgrad.py',
                'tests/test_gpu_model.py::test_persistent_kernel_cu_share_does_not_change_results']
 
 K = 'tests.test_gpu_kernels::'
 E = 'tests.test_gpu_fp16_edges::'
 I = 'tests.test_gpu_infer_kernels::'
+G = 'tests.test_gpu_wgrad::'
 MUST_PASS = [
     K + 'test_layout_roundtrip[1]',
     K + 'test_conv3d[3x3x3-bf16]',                                   # generic kernel + the split-K finish
@@ -63,6 +64,15 @@ MUST_PASS = [
     I + 'test_kps_finalize_tile_kernel[4-2-28-128-16]',
     I + 'test_time_avg[3-3-5x7x13-16]',
     I + 'test_copy_frames[4012-129]',
+    G + 'test_wgrad_dma9_kernel_sub2_and_sub1_every_split[130to70_k333_s1_n1t2_7x7]',
+    G + 'test_wgrad_pw_kernel_8_and_10_panels_every_tile_and_split[256to128_k111_s2_n1t2_6x2]',
+    G + 'test_wgrad_pw_kernel_grouped_launch_against_the_reference',
+    G + 'test_wgrad_direct_kernel_temporal_and_stride2_layers[230to128_k311_s1_n1t4_6x7]',
+    G + 'test_wgrad_direct_kernel_temporal_and_stride2_layers[230to128_k311_s1_n1t8_16x17]',       # several K ranges
+    G + 'test_cq_pack_and_wgrad_gemm_kernel_f32_on_every_geometry[64to128_k333_s2_n1t3_9x11]',
+    G + 'test_cq_pack_and_wgrad_gemm_kernel_bf16_under_direct_0[64to128_k333_s2_n1t4_9x11_win2+2]',
+    G + 'test_wgrad_finish_batch_kernel_transposes_scales_and_accumulates[0]',
+    G + 'test_results_on_maps_wider_than_one_column_are_bit_identical_to_the_recorded_ones',
 ]
 
 

@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import numerics as nm
+from tests.wgrad_refs import wgrad_ref64
 
 pytestmark = pytest.mark.gpu
 
@@ -758,6 +759,11 @@ def test_direct_weight_gradient_over_a_frame_window(ops, k, win):
     assert float((full.cpu() - ref).abs().max()) < 2e-3 * scale
     assert float((part.cpu() - ref).abs().max()) < 2e-3 * scale
     assert float((part - full).abs().max()) < 1e-4 * scale      # (same products; the K split differs, fp32 sums in another order)
+    # every element against float64 (tests/wgrad_refs.py): the full launch reduces all T frames (g is zero outside the window: same
+    # reference, same |x| |g| sum), the window launch n of them
+    ref64, absref, K = wgrad_ref64(x, gy, None, k, 1, pads, window=(t0, n))
+    nm.assert_elementwise(full.cpu(), ref64, absref, gy.numel() // cout, 'fp32', 'dW, full launch')
+    nm.assert_elementwise(part.cpu(), ref64, absref, K, 'fp32', 'dW, window launch')
 
 
 @pytest.mark.parametrize('T,n_props,n_persons,jitter', [(1, 2000, 8, 400), (1, 300, 3, 20), (2, 1000, 5, 200), (1, 2000, 8, 0), (1, 0, 4, 0)])
@@ -960,9 +966,11 @@ def test_nine_tap_weight_gradient_variants_agree(ops, monkeypatch, cin, cout, T,
         for k in env:
             monkeypatch.delenv(k)
     ops.drop_ctx()
+    ref64, absref, K = wgrad_ref64(x, gy, None, (3, 3, 3), 1, (1, 1, 1))
     for name, o in outs.items():
         assert float((o - ref).abs().max()) < 2e-3 * mx, name
         assert float((o - outs['sub2']).abs().max()) < 2e-5 * mx, name
+        nm.assert_elementwise(o, ref64, absref, K, 'fp32', 'dW ' + name)       # every element against float64 (tests/wgrad_refs.py)
 
 
 @pytest.mark.parametrize('sampling,pooled', [(2, 7), (2, 14), (0, 7)])
@@ -1047,6 +1055,9 @@ def test_pointwise_weight_gradient_kernel(ops, monkeypatch, case, acc):
         return (gt.view(cout, cin, 1, 1, 1) * 0.5 * scale.cuda().view(-1, 1, 1, 1, 1)).cpu()
     new = run()
     assert float((new - ref).abs().max()) < 2e-3 * mx, float((new - ref).abs().max()) / mx
+    # every element against float64 (tests/wgrad_refs.py).  acc: twice the raw sum, halved (exact) and scaled (one fp32 rounding)
+    ref64, absref, K = wgrad_ref64(x, gy, scale, (1, 1, 1), st, (0, 0, 0), window=win)
+    nm.assert_elementwise(new, ref64, absref, K, 'fp32', 'dW')
     monkeypatch.setenv('DAT_WGRAD_PW', '0')
     old = run()
     monkeypatch.delenv('DAT_WGRAD_PW')
@@ -1064,7 +1075,7 @@ def test_pointwise_weight_gradient_batch_equals_the_single_launches(ops):
     and executed as grouped launches -- both tile classes, stride 1 and 2, a frame window, ragged channel counts, layers shorter than one
     block's pipeline -- must leave in every accumulator what one dat_conv3d_wgrad_acc call per layer leaves (same products; the K ranges
     differ, so fp32 sums in another order), twice in a row (the accumulators add)."""
-    jobs, singles, keep = [], [], []
+    jobs, singles, keep, refs = [], [], [], []
     for k, (cin, cout, st, N, T, H, W, win) in enumerate(PW_CASES + [(64, 128, 1, 1, 3, 12, 14, None)]):
         ker = (3, 3, 3) if k == len(PW_CASES) else (1, 1, 1)
         pads = tuple(v // 2 for v in ker)
@@ -1088,6 +1099,7 @@ def test_pointwise_weight_gradient_batch_equals_the_single_launches(ops):
         jobs.append(job)
         singles.append((cg, xd, gd, T, gt_s, win))
         keep.append((gt_b, gt_s))
+        refs.append(wgrad_ref64(x, gy, None, ker, st, pads, window=win))
     for rep in range(2):
         ops.wgrad_acc_batch(jobs)
         for cg, xd, gd, T, gt_s, win in singles:
@@ -1097,6 +1109,12 @@ def test_pointwise_weight_gradient_batch_equals_the_single_launches(ops):
         mx = float(gt_s.abs().max())
         assert mx > 0
         assert float((gt_b - gt_s).abs().max()) < 2e-5 * mx, (k, float((gt_b - gt_s).abs().max()) / mx)
+        # every element of both accumulators ([tap][Cout][Cin], two additions of the raw sum) against float64 (tests/wgrad_refs.py)
+        ref64, absref, K = refs[k]
+        cout, cin = ref64.shape[:2]
+        for what, gt in (('grouped', gt_b), ('single', gt_s)):
+            got = gt.view(-1, cout, cin).permute(1, 2, 0).reshape(ref64.shape).cpu()
+            nm.assert_elementwise(got, 2 * ref64, 2 * absref, K, 'fp32', 'layer %d, %s launches' % (k, what))
 
 
 # ---- two ranks (VERDICT r3 item 4 / missing #3) ---------------------------------------------------------------------------------------
