@@ -1,0 +1,486 @@
+// Grouped forward 3D convolution (ResNeXt `branch2b`: kT x 3 x 3, C -> C in G groups of cg = C / G channels) for gfx950, with the fused
+// epilogue of the dense kernel (affine scale / bias, residual Sum, ReLU).  DESIGN.md section 3.8.
+//
+// The slab rule: an activation row in LDS is one 128-byte line = 64 bf16 channels, and for cg | 64 no group straddles a 64-channel slab.
+// The layer is therefore C / 64 independent 64 -> 64 convs: the block that owns output channels [64 s, 64 s + 64) stages ONLY the
+// input lines of slab s (bf16: one line per pixel, fp32: two 32-channel lines, bf16x3: the hi and the lo line of the split tensor) and
+// multiplies them by a packed 64 x 64 x taps weight image that is block-diagonal inside the slab (64 / cg blocks of cg x cg, zeros
+// elsewhere).  HBM traffic is the algorithmic minimum -- every input line is read by exactly one channel block per tile (plus halo),
+// the weights are C * 64 * taps elements instead of C * C * taps -- and the MFMA utilisation is cg / 64 by construction.
+//
+// The kernel keeps the dense implicit-GEMM kernel's machinery (conv3d_igemm.hip): LDS-DMA patch staging of tile + halo per (kt, chunk,
+// stride-parity plane), the ((row >> 1) & 7) XOR swizzle of the 16-byte slots, weights in MFMA A-fragment order straight from global
+// memory into registers, the XCD-aware block map and the LDS-transposed epilogue.  One variant: 64 channels x 256 positions per block,
+// every wave 64 channels x 64 positions, the table-driven tap loop (stride 1: one plane of 9 taps; stride 2: four parity planes).
+#include "conv_internal.h"
+
+using namespace dat_conv;
+
+namespace {
+
+constexpr int G_BN = 64;       // output channels per block = one slab
+constexpr int G_BP = 256;      // output positions per block
+constexpr int G_BP_LOG2 = 8;
+
+#define DAT_GRP_UNSUPPORTED(ctx, cond, ...)                          \
+    do {                                                             \
+        if (!(cond)) DAT_FAIL(ctx, DAT_ERR_UNSUPPORTED, __VA_ARGS__); \
+    } while (0)
+
+// ConvParams as the dense kernel reads them, with two fields re-read: n_cchunks = K chunks of ONE slab (bf16 1, fp32 2, bf16x3 3) and
+// nblk_n = slabs (C / 64).  ksplit is 1, lin_* / order / res2 / part are unused.
+template <int DT, int ODT>
+__global__ __launch_bounds__(NTHREADS, 2) void conv3d_grouped_kernel(const ConvParams p) {
+    constexpr int ES = ElemOf<DT>::size;
+    constexpr int OES = ElemOf<ODT>::size;
+    constexpr int WN = G_BN;              // channels per wave (all four waves share the slab)
+    constexpr int WP = G_BP / 4;          // positions per wave
+    constexpr int MT = WN / 32;
+    constexpr int PT = WP / 32;
+
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* patch = smem;                                      // PH*PW x 128 B
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+    // ---- XCD-aware block -> (slab, tile) map (bijective for any grid size): the slabs of one tile and neighbouring tiles share an XCD
+    unsigned bid = blockIdx.x;
+    {
+        const unsigned nx = 8, q = p.nblocks / nx, r = p.nblocks % nx;
+        const unsigned xcd = bid % nx, k = bid / nx;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+    }
+    const int slab = bid % p.nblk_n;
+    unsigned tile = bid / p.nblk_n;
+    const int fc = tile % p.otn;             // frame index fastest: the temporal re-reads of neighbouring output frames meet in the XCD's L2
+    tile /= p.otn;
+    const int tw_i = tile % p.tiles_w;
+    tile /= p.tiles_w;
+    const int th_i = tile % p.tiles_h;
+    const int clip = tile / p.tiles_h;
+    const int f = clip * p.otn + fc;         // output frame
+    const int t = p.ot0 + fc;
+    const int f_in = clip * p.T + t;         // input frame aligned with this output frame
+    const int n0 = slab * G_BN;
+    const int TW = 1 << p.tw_log2;
+    const int oh0 = th_i << p.th_log2;
+    const int ow0 = tw_i * p.tile_w;
+    const int ih0 = oh0 * p.sh - p.ph;       // input coordinate of patch cell (0,0)
+    const int iw0 = ow0 * p.sw - p.pw;
+
+    int rowbase[PT];
+#pragma unroll
+    for (int j = 0; j < PT; ++j) {
+        const int pos = wave * WP + j * 32 + (lane & 31);
+        const int ohl = pos >> p.tw_log2, owl = pos & (TW - 1);
+        rowbase[j] = ohl * p.PW + owl;
+    }
+    const int khalf = lane >> 5;
+
+    f32x16_t acc[MT][PT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < PT; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    // valid temporal taps for this output frame (a tap outside the clip reads zeros: skipped)
+    int kt_lo = 0, kt_hi = p.KT - 1;
+    while (kt_lo < p.KT && (t + kt_lo - p.pt) < p.in_lo) ++kt_lo;
+    while (kt_hi >= 0 && (t + kt_hi - p.pt) >= p.in_hi) --kt_hi;
+    const int n_kt = kt_hi - kt_lo + 1;
+    const int ntap = p.KH * p.KW;
+    const int ntab = p.tab_n;
+    const int total = n_kt * p.n_cchunks * ntab;           // tap steps
+    const int npatch_items = p.PH * p.PW * 8;
+
+    typedef const __attribute__((address_space(1))) void* gptr_t;
+    typedef __attribute__((address_space(3))) void* lptr_t;
+
+    // this wave's A fragments: 4 KiB per (tap, slab chunk, 32-row block), this lane's 16 B inside it
+    const size_t wd_cc_stride = (size_t)(p.Cout_pad >> 5) * 4096;
+    const char* const wd_lane = p.w + (size_t)(n0 >> 5) * 4096 + lane * 16;
+#define WD_PTR(KT_, CC_, TI_) (wd_lane + ((size_t)((KT_) * ntap + p.tab_tap[(TI_)]) * p.n_cchunks + (CC_)) * wd_cc_stride)
+    if (total > 0) {
+        // temporal taps in order of the INPUT frame index mod KT (see the dense kernel): queue neighbours stage the same frame together
+        const int kt_hi_x = kt_lo + n_kt;
+        int kshift = 0;
+        if (n_kt == p.KT && (DAT_KT_ROTATE)) kshift = (p.KT - (t + kt_lo - p.pt) % p.KT) % p.KT;
+        int kt = kt_lo + kshift, cc = 0, ti = 0;
+        if (kt >= kt_hi_x) kt -= n_kt;
+        uint4 wa[MT][4];
+        {
+            const char* w0 = WD_PTR(kt, cc, 0);
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) wa[i][ks] = *(const uint4*)(w0 + i * 4096 + ks * 1024);
+        }
+        const int nchunks = (npatch_items + 63) >> 6;    // 1-KiB LDS-DMA pieces (8 patch rows each)
+        for (int step = 0; step < total; ++step) {
+            const bool reload = (p.tab_new >> ti) & 1u;
+            // (bf16x3, one stride plane: chunk 1 -- x_hi against W_lo -- re-uses the patch of chunk 0)
+            const bool x3_same = p.x3 && p.tab_new == 1u && step > 0 && cc == 1;
+            if (reload && !x3_same) {
+                __syncthreads();  // all waves finished reading the previous patch
+                // ---- stage the input patch (tile + halo) of (kt, slab chunk, plane): global -> LDS by LDS-DMA.  Lane (row, phys slot)
+                // fetches the pixel's logical 16-B slot phys ^ ((row >> 1) & 7); halo pixels outside the frame fetch zeros.  Only the
+                // 128-byte lines of THIS slab are read: line slab * chunks + cc of the pixel (bf16x3: 2 * slab = hi, 2 * slab + 1 = lo).
+                const int fin = f_in + kt - p.pt;
+                const int line = p.x3 ? slab * 2 + (cc == 2) : slab * p.n_cchunks + cc;
+                const char* xbase = p.x + ((size_t)fin * p.H * p.W) * p.Cin * ES + (size_t)line * PPITCH;
+                const int py0 = ih0 + p.tab_dy[ti], px0 = iw0 + p.tab_dx[ti];
+#pragma unroll 2
+                for (int c = wave; c < nchunks; c += 4) {
+                    const int it = c * 64 + lane;
+                    if (it < npatch_items) {
+                        const int row = it >> 3;
+                        const int slot = (it ^ (row >> 1)) & 7;
+                        const int prow = (int)__umulhi((unsigned)row, p.pw_magic), pcol = row - prow * p.PW;
+                        const int ih = py0 + prow * p.psh, iw = px0 + pcol * p.psw;
+                        const char* src = p.zeros;
+                        if (ih >= 0 && ih < p.H && iw >= 0 && iw < p.W)
+                            src = xbase + ((unsigned)(ih * p.W + iw) * (unsigned)(p.Cin * ES) + (unsigned)(slot * 16));
+                        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(patch + c * 1024), 16, 0, 0);
+                    }
+                }
+            }
+            if (reload) {   // only a patch reload needs the block to meet (a ds_read is ordered behind an LDS-DMA by vmcnt + a barrier)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+            }
+            int nti = ti + 1, ncc = cc, nkt = kt;
+            if (nti == ntab) {
+                nti = 0;
+                if (++ncc == p.n_cchunks) { ncc = 0; if (++nkt == kt_hi_x) nkt = kt_lo; }
+            }
+            const char* const wnext = (step + 1 < total) ? WD_PTR(nkt, ncc, nti) : WD_PTR(kt, cc, ti);
+
+            __builtin_amdgcn_s_setprio(1);
+            {
+                const int tapoff = p.tab_rowoff[ti];
+                // patch fragment of (row, k-slice ks, k-half): 16-B slot (2*ks + khalf) ^ ((row >> 1) & 7) of the row's line
+                const char* bp[PT];
+                int bx[PT];
+#pragma unroll
+                for (int j = 0; j < PT; ++j) {
+                    const int row = rowbase[j] + tapoff;
+                    const int g = (row >> 1) & 7;
+                    bp[j] = patch + (row * PPITCH + ((khalf ^ (g & 1)) << 4));
+                    bx[j] = g >> 1;
+                }
+                uint4 b[2][PT];
+#pragma unroll
+                for (int j = 0; j < PT; ++j) b[0][j] = *(const uint4*)(bp[j] + (bx[j] << 5));
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) {
+                    const int cur = ks & 1, nxt = cur ^ 1;
+                    if (ks < 3) {
+#pragma unroll
+                        for (int j = 0; j < PT; ++j) b[nxt][j] = *(const uint4*)(bp[j] + (((ks + 1) ^ bx[j]) << 5));
+                    }
+#pragma unroll
+                    for (int i = 0; i < MT; ++i)
+#pragma unroll
+                        for (int j = 0; j < PT; ++j) Mma<DT>::step(wa[i][ks], b[cur][j], acc[i][j]);
+                    // this k-slice's fragments of the NEXT tap: a whole tap to land (unconditional and pinned, see the dense kernel)
+#pragma unroll
+                    for (int i = 0; i < MT; ++i) wa[i][ks] = *(const uint4*)(wnext + i * 4096 + ks * 1024);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            __builtin_amdgcn_s_setprio(0);
+            ti = nti; cc = ncc; kt = nkt;
+        }
+    }
+#undef WD_PTR
+
+    // ---- epilogue: affine/bias + residual + relu, transposed through LDS so that HBM sees whole 16-byte channel runs per lane ----
+    // (the dense kernel's: MFMA register r of a lane = channel (r&3) + 8*(r>>2) + 4*(lane>>5) of ONE position; each wave transposes
+    //  32 positions x 64 channels at a time through its own fp32 slice, pitch 64*4+16 B)
+    constexpr int EPITCH = WN * 4 + 16;
+    constexpr int CPL = 16 / OES;                 // channels per lane in the store phase (8 bf16 / 4 fp32)
+    constexpr int LPP = WN / CPL;                // lanes per position (8 / 16)
+    constexpr int PPI = 64 / LPP;                // positions per store instruction (8 / 4)
+    constexpr int NQ = 32 / PPI;
+    __syncthreads();                             // every wave is done with the patch
+    char* est = smem + wave * (32 * EPITCH);
+    const int sl_c = (lane % LPP) * CPL;
+    const int sl_p = lane / LPP;
+    const int c_st = n0 + sl_c;                  // (< Cout: Cout is a multiple of 64)
+    float sc[CPL], bi[CPL];
+#pragma unroll
+    for (int e = 0; e < CPL; ++e) {
+        sc[e] = p.scale ? p.scale[c_st + e] : 1.f;
+        bi[e] = p.bias ? p.bias[c_st + e] : 0.f;
+    }
+    // block-uniform 64-bit base + 32-bit per-lane offset inside the frame (the launcher checks one frame of output is < 2 GB)
+    const size_t tile_pos = ((size_t)f * p.Ho + oh0) * p.Wo + ow0;
+    char* const ybase = p.y + tile_pos * p.out_cs * OES;
+    const char* const rbase = p.res + tile_pos * p.out_cs * OES;
+#pragma unroll
+    for (int j = 0; j < PT; ++j) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                *(float4*)(est + (lane & 31) * EPITCH + (i * 32 + g * 8 + khalf * 4) * 4) =
+                    make_float4(acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1], acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int pl = q * PPI + sl_p;
+            float v[CPL];
+#pragma unroll
+            for (int e4 = 0; e4 < CPL / 4; ++e4) {
+                const float4 t4 = *(const float4*)(est + pl * EPITCH + (sl_c + e4 * 4) * 4);
+                v[e4 * 4 + 0] = t4.x; v[e4 * 4 + 1] = t4.y; v[e4 * 4 + 2] = t4.z; v[e4 * 4 + 3] = t4.w;
+            }
+            const int pos = wave * WP + j * 32 + pl;
+            const int ohl = pos >> p.tw_log2, owl = pos & (TW - 1);
+            if (oh0 + ohl >= p.Ho || ow0 + owl >= p.Wo) continue;
+            const unsigned off = ((unsigned)(ohl * p.Wo + owl) * (unsigned)p.out_cs + (unsigned)c_st) * (unsigned)OES;
+#pragma unroll
+            for (int e = 0; e < CPL; ++e) v[e] = v[e] * sc[e] + bi[e];
+            if (p.res_mode) {
+                const uint4 r = *(const uint4*)(rbase + off);
+                if (ODT == DAT_BF16) {
+                    const uint32_t ru[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+                    for (int e2 = 0; e2 < CPL / 2; ++e2) {
+                        v[2 * e2] += bf2f((uint16_t)(ru[e2 % 4] & 0xffff));
+                        v[2 * e2 + 1] += bf2f((uint16_t)(ru[e2 % 4] >> 16));
+                    }
+                } else {
+                    v[0] += __uint_as_float(r.x); v[1] += __uint_as_float(r.y);
+                    v[2] += __uint_as_float(r.z); v[3] += __uint_as_float(r.w);
+                }
+            }
+            if (p.relu) {
+#pragma unroll
+                for (int e = 0; e < CPL; ++e) v[e] = fmaxf(v[e], 0.f);
+            }
+            char* yp = ybase + off;
+            if (ODT == DAT_BF16) {
+                uint32_t o[CPL / 2];
+#pragma unroll
+                for (int e2 = 0; e2 < CPL / 2; ++e2) o[e2] = f2bf2(v[2 * e2], v[2 * e2 + 1]);
+                *(uint4*)yp = make_uint4(o[0], o[1 % (CPL / 2)], o[2 % (CPL / 2)], o[3 % (CPL / 2)]);
+            } else {
+                *(float4*)yp = make_float4(v[0], v[1], v[2], v[3]);
+                if (DT == DAT_BF16 && p.y_split) {
+                    // bf16x3: the same values as hi / lo bf16 halves for the next conv (bit-identical to dat_split_bf16x2 of the stored y):
+                    // 64-channel chunk q of the pixel: line 2q = hi, line 2q + 1 = lo; this lane's 4 channels = 8 bytes in each line
+                    const uint32_t h0 = f2bf2(v[0], v[1]), h1 = f2bf2(v[2], v[3]);
+                    const uint32_t l0 = f2bf2(v[0] - __uint_as_float(h0 << 16), v[1] - __uint_as_float(h0 & 0xffff0000u));
+                    const uint32_t l1 = f2bf2(v[2] - __uint_as_float(h1 << 16), v[3] - __uint_as_float(h1 & 0xffff0000u));
+                    char* sp = p.y_split + ((tile_pos + (size_t)(ohl * p.Wo + owl)) * (size_t)(2 * p.out_cs) + (size_t)((c_st >> 6) * 128 + (c_st & 63))) * 2;
+                    *(uint2*)sp = make_uint2(h0, h1);
+                    *(uint2*)(sp + 128) = make_uint2(l0, l1);
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// Packed grouped weights: the dense kernel's A-fragment order of a "64 -> C" conv -- [tap][slab chunk][32-row block][k-slice][lane][16 B],
+// lane = k-half * 32 + row, 16-B slot (2 * k-slice + k-half) of the row's 128-B chunk -- whose row co holds, at the slab-local input
+// channels of its own group, w[co][0 .. cg); zeros elsewhere (the block-diagonal 64 x 64 image) and in the rows past C.
+// x3: three bf16 chunks [W_hi | W_lo | W_hi] per slab, met in the kernel by the input lines [hi | hi | lo].
+template <int DT>
+__global__ void grouped_pack_kernel(const float* __restrict__ w, void* __restrict__ out, int C, int cg, int ntap, int Cout_pad, int nck, int x3) {
+    constexpr int CK = Mma<DT>::CK, EPS = 16 / ElemOf<DT>::size;
+    const size_t total = (size_t)ntap * nck * Cout_pad * CK;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int cl = i % CK;
+        const int co = (i / CK) % Cout_pad;
+        const int cc = (i / ((size_t)CK * Cout_pad)) % nck;
+        const int tap = i / ((size_t)CK * Cout_pad * nck);
+        const int j = x3 ? cl : cc * CK + cl;             // input channel inside the slab
+        float v = 0.f;
+        if (co < C) {
+            const int cil = j - ((co & 63) / cg) * cg;    // ... inside the row's group
+            if (cil >= 0 && cil < cg) v = w[((size_t)co * cg + cil) * ntap + tap];
+        }
+        if (x3) {
+            const float hi = bf2f(f2bf(v));
+            v = cc == 1 ? v - hi : hi;
+        }
+        const int slot = cl / EPS, e = cl % EPS;
+        const int lane = (slot & 1) * 32 + (co & 31);
+        const size_t dst = (((((size_t)tap * nck + cc) * (Cout_pad >> 5) + (co >> 5)) * 4 + (slot >> 1)) * 64 + lane) * EPS + e;
+        ElemOf<DT>::st(out, dst, v);
+    }
+}
+
+inline int slab_chunks(int dtype) { return dtype == DAT_BF16X3 ? 3 : dtype == DAT_F32 ? 2 : 1; }
+
+// what every grouped entry point accepts (anything else is DAT_ERR_UNSUPPORTED: there is no dense fall-back)
+int grouped_check(dat_ctx* ctx, const dat_conv_desc* d, int groups, const char* who) {
+    DAT_ENFORCE(ctx, d, "%s: null descriptor", who);
+    DAT_GRP_UNSUPPORTED(ctx, d->dtype == DAT_F32 || d->dtype == DAT_BF16 || d->dtype == DAT_BF16X3, "%s: bad dtype %d", who, d->dtype);
+    DAT_GRP_UNSUPPORTED(ctx, d->dtype != DAT_BF16X3 || DAT_H16_FORMAT == 0,
+                        "%s: DAT_BF16X3 needs the bf16 build of the library (this one holds IEEE half in its 16-bit tensors)", who);
+    DAT_GRP_UNSUPPORTED(ctx, groups >= 1 && d->Cin > 0 && d->Cin == d->Cout && d->Cin % groups == 0 && d->Cin % 64 == 0,
+                        "%s: %d groups must divide Cin %d == Cout %d, a multiple of 64", who, groups, d->Cin, d->Cout);
+    const int cg = d->Cin / groups;
+    DAT_GRP_UNSUPPORTED(ctx, cg == 4 || cg == 8 || cg == 16 || cg == 32 || cg == 64,
+                        "%s: %d channels per group (supported: 4, 8, 16, 32, 64 -- a group must not straddle a 64-channel slab)", who, cg);
+    DAT_GRP_UNSUPPORTED(ctx, d->KH == 3 && d->KW == 3 && (d->KT == 1 || d->KT == 3) && d->pad_h == 1 && d->pad_w == 1 && d->pad_t == d->KT / 2,
+                        "%s: kernel %dx%dx%d pads %d,%d,%d (supported: 1x3x3 and 3x3x3 with \"same\" padding)", who, d->KT, d->KH, d->KW,
+                        d->pad_t, d->pad_h, d->pad_w);
+    DAT_GRP_UNSUPPORTED(ctx, d->stride_h == d->stride_w && (d->stride_h == 1 || d->stride_h == 2), "%s: stride %dx%d (supported: 1, 2)", who,
+                        d->stride_h, d->stride_w);
+    DAT_GRP_UNSUPPORTED(ctx, d->res_mode == 0 || d->res_mode == 1, "%s: res_mode %d (supported: 0, 1)", who, d->res_mode);
+    return DAT_OK;
+}
+
+// the 2^a x 2^b tile (a + b = log2 positions) that wastes the fewest output positions, tie -> smaller halo (the dense kernel's rule)
+void grouped_tile(int Ho, int Wo, int s, int* th_log2, int* tw_log2) {
+    double best = 1e30;
+    for (int a = 0; a <= G_BP_LOG2; ++a) {
+        const int b = G_BP_LOG2 - a;
+        const long long th = 1 << a, tw = 1 << b;
+        const double waste = (double)(cdiv_ll(Ho, th) * cdiv_ll(Wo, tw) * th * tw) / ((double)Ho * Wo);
+        const double halo = (double)((th + 2 / s) * (tw + 2 / s)) / (double)(th * tw);
+        const double cost = waste * (1.0 + 0.15 * (halo - 1.0)) * (tw < 32 ? 1.06 : 1.0);
+        if (cost < best - 1e-9) { best = cost; *th_log2 = a; *tw_log2 = b; }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dat_conv3d_grouped_packed_weight_bytes(const dat_conv_desc* d, int groups) {
+    if (!d || groups < 1 || d->Cout < 1) return 0;
+    return (size_t)d->KT * d->KH * d->KW * slab_chunks(d->dtype) * cout_pad_of(d) * PPITCH;
+}
+
+double dat_conv3d_grouped_flops(const dat_conv_desc* d, int groups) {
+    if (!d || groups < 1) return 0.0;
+    return dat_conv3d_flops(d, d->Cin / groups, d->Cout);
+}
+
+int dat_conv3d_grouped_pack_weights(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, int groups, const float* w, void* packed) {
+    DAT_ENFORCE(ctx, d && w && packed, "conv3d_grouped_pack_weights: null argument");
+    const int rc = grouped_check(ctx, d, groups, "conv3d_grouped_pack_weights");
+    if (rc != DAT_OK) return rc;
+    const int ntap = d->KT * d->KH * d->KW, nck = slab_chunks(d->dtype), cp = cout_pad_of(d), cg = d->Cin / groups;
+    const size_t total = (size_t)ntap * nck * cp * (d->dtype == DAT_F32 ? 32 : 64);
+    const int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
+    if (d->dtype == DAT_F32)
+        hipLaunchKernelGGL(grouped_pack_kernel<DAT_F32>, dim3(blocks), dim3(256), 0, (hipStream_t)s, w, packed, d->Cout, cg, ntap, cp, nck, 0);
+    else
+        hipLaunchKernelGGL(grouped_pack_kernel<DAT_BF16>, dim3(blocks), dim3(256), 0, (hipStream_t)s, w, packed, d->Cout, cg, ntap, cp, nck,
+                           d->dtype == DAT_BF16X3 ? 1 : 0);
+    DAT_CHECK_LAUNCH(ctx, "grouped_pack");
+    return DAT_OK;
+}
+
+int dat_conv3d_grouped_fwd(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, int groups, const void* x, const void* w_packed,
+                           const float* scale, const float* bias, const void* residual, void* y, void* y_split) {
+    DAT_ENFORCE(ctx, d && x && w_packed && y, "conv3d_grouped_fwd: null argument");
+    const int rc0 = grouped_check(ctx, d, groups, "conv3d_grouped_fwd");
+    if (rc0 != DAT_OK) return rc0;
+    const bool x3 = d->dtype == DAT_BF16X3;
+    DAT_ENFORCE(ctx, d->T > 0 && d->frames > 0 && d->frames % d->T == 0, "conv3d_grouped_fwd: frames %d not a multiple of T %d", d->frames, d->T);
+    DAT_ENFORCE(ctx, d->out_cstride % 8 == 0 && d->out_cstride >= d->Cout, "conv3d_grouped_fwd: out_cstride %d must be a multiple of 8, >= Cout %d",
+                d->out_cstride, d->Cout);
+    DAT_ENFORCE(ctx, d->res_mode == 0 || residual, "conv3d_grouped_fwd: res_mode %d needs a residual pointer", d->res_mode);
+    DAT_ENFORCE(ctx, !y_split || (x3 && d->Cout == d->out_cstride), "conv3d_grouped_fwd: a split output needs DAT_BF16X3 and Cout == out_cstride (got %d / %d)",
+                d->Cout, d->out_cstride);
+    ConvParams p;
+    memset(&p, 0, sizeof(p));
+    p.x = (const char*)x; p.w = (const char*)w_packed; p.scale = scale; p.bias = bias;
+    p.res = (const char*)residual; p.y = (char*)y; p.y_split = (char*)y_split;
+    p.zeros = (const char*)ctx->zeros;
+    p.in_lo = d->in_tn > 0 ? d->in_t0 : 0;
+    p.in_hi = d->in_tn > 0 ? d->in_t0 + d->in_tn : d->T;
+    DAT_ENFORCE(ctx, p.in_lo >= 0 && p.in_hi <= d->T, "conv3d_grouped_fwd: non-zero input frames [%d, %d) outside T %d", p.in_lo, p.in_hi, d->T);
+    p.ot0 = d->out_tn > 0 ? d->out_t0 : 0;
+    p.otn = d->out_tn > 0 ? d->out_tn : d->T;
+    DAT_ENFORCE(ctx, p.ot0 >= 0 && p.ot0 + p.otn <= d->T, "conv3d_grouped_fwd: output frames [%d, %d) outside T %d", p.ot0, p.ot0 + p.otn, d->T);
+    p.frames = d->frames / d->T * p.otn; p.T = d->T; p.H = d->H; p.W = d->W;
+    p.Cin = x3 ? 2 * d->Cin : d->Cin;            // (x3: pixel pitch of the hi / lo split tensor)
+    p.x3 = x3;
+    dat_conv3d_out_shape(d, &p.Ho, &p.Wo);
+    DAT_ENFORCE(ctx, p.Ho > 0 && p.Wo > 0, "conv3d_grouped_fwd: empty output %dx%d", p.Ho, p.Wo);
+    p.Cout = d->Cout; p.out_cs = d->out_cstride; p.Cout_pad = cout_pad_of(d);
+    p.KT = d->KT; p.KH = 3; p.KW = 3; p.sh = p.sw = d->stride_h;
+    p.pt = d->pad_t; p.ph = 1; p.pw = 1; p.relu = d->relu; p.res_mode = d->res_mode;
+    grouped_tile(p.Ho, p.Wo, p.sh, &p.th_log2, &p.tw_log2);
+    const int th = 1 << p.th_log2, tw = 1 << p.tw_log2;
+    p.tile_w = tw;
+    p.tiles_h = (p.Ho + th - 1) / th;
+    p.tiles_w = (p.Wo + tw - 1) / tw;
+    p.psh = p.psw = p.sh;
+    p.rsh = p.rsw = 1;
+    p.PH = th + 2 / p.sh;
+    p.PW = tw + 2 / p.sw;
+    {   // tap table in stride-parity plane order: every plane is a dense (tile + halo / stride) patch
+        int n = 0;
+        for (int py = 0; py < p.sh; ++py)
+            for (int px = 0; px < p.sw; ++px) {
+                bool first = true;
+                for (int kh = py; kh < 3; kh += p.sh)
+                    for (int kw = px; kw < 3; kw += p.sw) {
+                        p.tab_tap[n] = kh * 3 + kw;
+                        p.tab_rowoff[n] = (kh / p.sh) * p.PW + (kw / p.sw);
+                        p.tab_dy[n] = (short)py;
+                        p.tab_dx[n] = (short)px;
+                        if (first) p.tab_new |= 1u << n;
+                        first = false;
+                        ++n;
+                    }
+            }
+        p.tab_n = n;
+    }
+    p.pw_magic = (unsigned)((0x100000000ull + (unsigned)p.PW - 1) / (unsigned)p.PW);     // (PW >= 2)
+    p.n_cchunks = slab_chunks(d->dtype);
+    p.ksplit = 1;
+    p.nblk_n = d->Cout / G_BN;
+    const long long nblocks = (long long)p.frames * p.tiles_h * p.tiles_w * p.nblk_n;
+    DAT_ENFORCE(ctx, nblocks > 0 && nblocks < (1ll << 31), "conv3d_grouped_fwd: grid of %lld blocks unsupported", nblocks);
+    DAT_ENFORCE(ctx, (long long)p.Ho * p.Wo * p.out_cs * 4 < (1ll << 31) && (long long)p.H * p.W * p.Cin * 4 < (1ll << 31),
+                "conv3d_grouped_fwd: one frame of %dx%dx%d exceeds the 2-GB range of the kernel's 32-bit offsets", p.H, p.W, p.Cin);
+    p.nblocks = (unsigned)nblocks;
+    p.ntiles = (unsigned)(nblocks / p.nblk_n);
+    size_t lds = ((size_t)p.PH * p.PW * PPITCH + 1023) & ~(size_t)1023;     // whole 1-KiB DMA pieces
+    if (lds < 4 * 32 * (64 * 4 + 16)) lds = 4 * 32 * (64 * 4 + 16);         // epilogue staging slices
+    DAT_ENFORCE(ctx, lds <= 160 * 1024, "conv3d_grouped_fwd: LDS patch of %zu bytes exceeds 160 KiB (tile %dx%d)", lds, th, tw);
+    hipStream_t st = (hipStream_t)s;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
+    if (ctx->prof_enabled && ctx->prof_n < ctx->prof_cap && hipStreamIsCapturing(st, &cap_st) == hipSuccess &&
+        cap_st == hipStreamCaptureStatusNone) {
+        e0 = ctx->prof_ev[2 * ctx->prof_n];
+        e1 = ctx->prof_ev[2 * ctx->prof_n + 1];
+        hipEventRecord(e0, st);
+    }
+#define DAT_GRP_LAUNCH(DT_, ODT_)                                                                      \
+    do {                                                                                               \
+        auto kern = conv3d_grouped_kernel<DT_, ODT_>;                                                  \
+        const int rc = dat_ensure_lds(ctx, (const void*)kern, 160 * 1024);                              \
+        if (rc != DAT_OK) return rc;                                                                   \
+        hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(NTHREADS), lds, st, p);                         \
+    } while (0)
+    if (x3) DAT_GRP_LAUNCH(DAT_BF16, DAT_F32);
+    else if (d->dtype == DAT_BF16) DAT_GRP_LAUNCH(DAT_BF16, DAT_BF16);
+    else DAT_GRP_LAUNCH(DAT_F32, DAT_F32);
+#undef DAT_GRP_LAUNCH
+    DAT_CHECK_LAUNCH(ctx, "conv3d_grouped");
+    if (e1) {
+        hipEventRecord(e1, st);
+        ctx->prof_flops[ctx->prof_n] = 2.0 * d->Cout * (d->Cin / groups) * d->KT * 9 * (double)p.frames * p.Ho * p.Wo;
+        ctx->prof_tag[ctx->prof_n] = 64 * 10000 + 2570 + d->dtype;     // ("257 positions": the grouped kernel)
+        ctx->prof_n++;
+    }
+    return DAT_OK;
+}
+
+}  // extern "C"

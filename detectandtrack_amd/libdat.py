@@ -111,6 +111,10 @@ _PROTOS = {
     'dat_conv3d_tune_plan': (_i, [_p, _i, _i]),
     'dat_conv3d_persistent_share': (_i, [_p, _i]),
     'dat_conv3d_flops': (_d, [C.POINTER(ConvDesc), _i, _i]),
+    'dat_conv3d_grouped_packed_weight_bytes': (C.c_size_t, [C.POINTER(ConvDesc), _i]),
+    'dat_conv3d_grouped_pack_weights': (_i, [_p, _p, C.POINTER(ConvDesc), _i, _p, _p]),
+    'dat_conv3d_grouped_fwd': (_i, [_p, _p, C.POINTER(ConvDesc), _i, _p, _p, _p, _p, _p, _p, _p]),
+    'dat_conv3d_grouped_flops': (_d, [C.POINTER(ConvDesc), _i]),
     'dat_stem_pack': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i]),
     'dat_stem_weights': (_i, [_p, _p, _p, _i, _p]),
     'dat_split_bf16x2': (_i, [_p, _p, _p, _p, _ll, _i]),

@@ -143,7 +143,9 @@ class DetectionModelHelper(object):
     # ---- convolutions --------------------------------------------------------------------------------
     def ConvNd(self, blob_in, blob_out, dim_in, dim_out, kernels, strides=None, pads=None, no_bias=0,
                weight_init=None, bias_init=None, group=1, dilations=1, weight=None, bias=None, **unused):
-        assert group == 1, 'grouped conv not on the hot path (RESNETS.NUM_GROUPS == 1 in every config)'
+        group = int(group)
+        assert group >= 1 and dim_in % group == 0 and dim_out % group == 0, \
+            'group count %d must divide dim_in %d and dim_out %d' % (group, dim_in, dim_out)
         if not isinstance(dilations, int):
             assert all(d == 1 for d in dilations), 'dilated conv unsupported (MODEL.DILATION == 1 in every config)'
         else:
@@ -154,20 +156,21 @@ class DetectionModelHelper(object):
         assert pads[:3] == pads[3:], 'symmetric pads expected'
         assert strides[0] == 1, 'temporal stride unsupported (VIDEO.TIME_STRIDE_ON, FPN3D.py:199-203)'
         blob_in, blob_out = str(blob_in), str(blob_out)
-        w = weight or self._param(blob_out + '_w', [dim_out, dim_in] + kernels,
+        w = weight or self._param(blob_out + '_w', [dim_out, dim_in // group] + kernels,
                                   weight_init or ('XavierFill', {}), 'w')
         b = None
         if not no_bias:
             b = bias or self._param(blob_out + '_b', [dim_out], bias_init or ('ConstantFill', {'value': 0.}), 'b')
+        grouped = {'group': group} if group > 1 else {}      # (recorded for grouped convs only: an ungrouped op is what it always was)
         return self.net.add(Op('Conv', [blob_in], [blob_out], w=w, b=b, scale=None, shift=None, dim_in=dim_in,
                                dim_out=dim_out, kernels=kernels, strides=strides[1:], pads=pads[:3], relu=False,
-                               residual=None, res_mode=0))
+                               residual=None, res_mode=0, **grouped))
 
     def Conv(self, blob_in, blob_out, dim_in, dim_out, kernel, stride=1, pad=0, no_bias=0, weight_init=None,
              bias_init=None, group=1, dilation=1, **kw):
         """2D conv (FPN.py:222-262, keypoint_rcnn_heads.py:61-66): recorded as a kT = 1 ConvNd; the parameter
         keeps the reference's 4-D shape [out, in, k, k]."""
-        w = kw.get('weight') or self._param(str(blob_out) + '_w', [dim_out, dim_in, kernel, kernel],
+        w = kw.get('weight') or self._param(str(blob_out) + '_w', [dim_out, dim_in // int(group), kernel, kernel],
                                              weight_init or ('XavierFill', {}), 'w')
         return self.ConvNd(blob_in, blob_out, dim_in, dim_out, [1, kernel, kernel], strides=[1, stride, stride],
                            pads=2 * [0, pad, pad], no_bias=no_bias, bias_init=bias_init, group=group,

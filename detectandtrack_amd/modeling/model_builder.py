@@ -45,6 +45,9 @@ def init_model(model_name, train, init_params=None):
 
 def create(model_name, train=False, init_params=None):
     """:52-61."""
+    if train and cfg.RESNETS.NUM_GROUPS > 1:
+        raise NotImplementedError('training a grouped (ResNeXt, RESNETS.NUM_GROUPS = %d) body needs the grouped data-gradient and '
+                                  'weight-gradient kernels, which do not exist: the grouped conv is forward only' % cfg.RESNETS.NUM_GROUPS)
     return get_func(model_name)(init_model(model_name, train, init_params))
 
 

@@ -160,15 +160,19 @@ def copy_frames(src, src_idx, dst, dst_idx):
 class ConvLayer(object):
     """A conv with packed weights + fused epilogue parameters, ready to launch.
 
-    w: fp32 [Cout, Cin, KT, KH, KW] (reference blob layout, CUDA tensor)
+    w: fp32 [Cout, Cin, KT, KH, KW] (reference blob layout, CUDA tensor); groups > 1: [Cout, Cin / groups, KT, KH, KW]
     scale/bias: fp32 [Cout] or None (AffineChannelNd / conv bias); padded to the stored Cout.
     """
 
     def __init__(self, w, scale=None, bias=None, stride=(1, 1), pads=(0, 0, 0), relu=False, dtype=BF16,
-                 cin_stride=None, dgrad_of=None, x3=False):
+                 cin_stride=None, dgrad_of=None, x3=False, groups=1):
         """dgrad_of = (w_fwd, scale_fwd): this layer is the DATA-GRADIENT conv of a forward conv with master weights w_fwd
         [CoutF, CinF, KT, KH, KW]; `w` is then ignored and the packed weights come straight from w_fwd (channels swapped, kernel
-        flipped, AffineChannelNd scale folded in: dat_conv3d_pack_weights_dgrad)."""
+        flipped, AffineChannelNd scale folded in: dat_conv3d_pack_weights_dgrad).
+        groups > 1: a grouped conv (ResNeXt `branch2b`) on the dat_conv3d_grouped_* entry points -- forward only, and only the shapes
+        that kernel has (anything else raises its DAT_ERR_UNSUPPORTED text: there is no dense fall-back)."""
+        self.groups = int(groups)
+        assert self.groups >= 1 and (self.groups == 1 or dgrad_of is None), 'grouped convs have no data-gradient kernel'
         if dgrad_of is not None:
             w_fwd = dgrad_of[0].contiguous().float()
             self.w_src, self.dgrad_scale = w_fwd, (None if dgrad_of[1] is None else dgrad_of[1].contiguous().float())
@@ -180,6 +184,7 @@ class ConvLayer(object):
             w = w.contiguous().float()
             self.w_src, self.dgrad_scale = w, None          # kept (no copy when `w` already was a contiguous fp32 master): repack()
             self.cout_real, self.cin_real, self.kt, self.kh, self.kw = [int(v) for v in w.shape]
+            self.cin_real *= self.groups
         self.is_dgrad = dgrad_of is not None
         self.dtype = dtype
         # x3 (cfg.HIP.DTYPE 'bf16x3'): fp32 activations, the conv itself on hi / lo bf16 splits of both operands -- three bf16 MFMAs per
@@ -207,7 +212,11 @@ class ConvLayer(object):
                 self.bias[:self.cout_real] = bias.float()
                 self.bias_src = bias
         d = self.desc(1, 1, 8, 8)
-        nbytes = L.lib().dat_conv3d_packed_weight_bytes(C.byref(d))
+        if self.groups > 1:
+            assert self.cin == self.cin_real == self.cout_real, 'grouped conv: Cin %d == Cout %d, unpadded' % (self.cin_real, self.cout_real)
+            nbytes = L.lib().dat_conv3d_grouped_packed_weight_bytes(C.byref(d), self.groups)
+        else:
+            nbytes = L.lib().dat_conv3d_packed_weight_bytes(C.byref(d))
         self.packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.repack(weights_only=True)
 
@@ -228,7 +237,9 @@ class ConvLayer(object):
     def repack(self, weights_only=False):
         """(Re-)derive the packed weights (and a padded bias copy) from the fp32 masters -- after an SGD update in place."""
         d = self.desc(1, 1, 8, 8)
-        if self.x3:
+        if self.groups > 1:
+            ctx().call('dat_conv3d_grouped_pack_weights', _stream(), C.byref(d), self.groups, _ptr(self.w_src), _ptr(self.packed))
+        elif self.x3:
             d.dtype, d.Cin = BF16, 3 * self.cin
             ctx().call('dat_conv3d_pack_weights', _stream(), C.byref(d), _ptr(self._x3_master()), self.cout_real, 3 * self.cin,
                        _ptr(self.packed))
@@ -262,7 +273,7 @@ class ConvLayer(object):
 
     def flops(self, frames, H, W):
         ho, wo = self.out_hw(H, W)
-        return 2.0 * self.cout_real * self.cin_real * self.kt * self.kh * self.kw * frames * ho * wo
+        return 2.0 * self.cout_real * (self.cin_real // self.groups) * self.kt * self.kh * self.kw * frames * ho * wo
 
     def hbm_bytes(self, frames, H, W, oframes=None, res_mode=0):
         """Algorithmic HBM bytes of one launch: input + packed weights + output (+ residual), each touched once."""
@@ -273,7 +284,7 @@ class ConvLayer(object):
         in_pos = H * W
         if self.kh == 1 and self.kw == 1:        # a strided 1x1 conv touches only the sampled positions of its input
             in_pos = ho * wo
-        b = in_frames * in_pos * self.cin * es + self.kt * self.kh * self.kw * self.cout * self.cin * es
+        b = in_frames * in_pos * self.cin * es + self.kt * self.kh * self.kw * self.cout * (self.cin // self.groups) * es
         b += oframes * ho * wo * self.cstride * es
         if res_mode == 1:
             b += oframes * ho * wo * self.cstride * es
@@ -299,6 +310,18 @@ class ConvLayer(object):
             # (RPN head -> proposal kernels, cls_score / bbox_pred -> softmax / box decode, the deconv -> kps_finalize) -- no fill launch
             alloc = torch.zeros if (self.cstride != self.cout and zero_pad) else torch.empty
             out = alloc((oframes, ho, wo, self.cstride), dtype=x.dtype, device=x.device)
+        if self.groups > 1:
+            assert res_mode in (0, 1) and addend is None
+            xin, ysplit = x, None
+            if self.x3:
+                xin = x_split if x_split is not None else split_bf16x2(x)
+                if want_split:
+                    ysplit = torch.empty(tuple(out.shape[:-1]) + (2 * self.cstride,), dtype=torch.bfloat16, device=out.device)
+            ctx().call('dat_conv3d_grouped_fwd', _stream(), C.byref(d), self.groups, _ptr(xin), _ptr(self.packed), _ptr(self.scale),
+                       _ptr(self.bias), _ptr(residual), _ptr(out), _ptr(ysplit))
+            if self.x3:
+                out._split = ysplit
+            return out
         if res_mode == 4:       # out = residual > 0 ? conv + addend : 0 (training: dat_conv3d_fwd_sum_mask; `addend` may be `out`)
             assert not self.x3 and addend is not None and residual is not None
             assert addend.shape == out.shape == residual.shape and addend.dtype == out.dtype == residual.dtype

@@ -453,7 +453,7 @@ class Executor(object):
             scale = ws.dev_param(a['scale']) if a['scale'] else None
             bias = ws.dev_param(a['shift']) if a['shift'] else (ws.dev_param(a['b']) if a['b'] else None)
             return ops.ConvLayer(w, scale, bias, stride=a['strides'], pads=a['pads'], relu=a['relu'], dtype=dt,
-                                 cin_stride=xin.t.shape[3], x3=_x3(self.ws))
+                                 cin_stride=xin.t.shape[3], x3=_x3(self.ws), groups=a.get('group', 1))
         layer = self._layer(i, build)
         res = ws.blobs[a['residual']].t if a['residual'] else None
         if xin.tsel is not None:    # lazy SliceKeyFrame: a kT = 1 conv computes output frame k of every clip from input frame k

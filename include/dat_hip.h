@@ -158,6 +158,25 @@ int dat_conv3d_fwd_x3(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, const 
 /* algorithmic FLOPs of one launch: 2*Cout*Cin*KT*KH*KW*frames*Ho*Wo */
 double dat_conv3d_flops(const dat_conv_desc* d, int Cin_real, int Cout_real);
 
+/* ---- grouped forward conv: ConvNd(group = G) + AffineChannelNd + Sum + Relu (ResNeXt `branch2b`, ResNet3D.py:141) ---------- */
+/* The dense entry points above with `groups` next to the descriptor (dat_conv_desc itself is unchanged): d->Cin == d->Cout == C, a
+ * multiple of 64, in `groups` groups of cg = C / groups channels; output channel co reads input channels [(co / cg) * cg, + cg).
+ * Supported: cg in {4, 8, 16, 32, 64} (a group never straddles a 64-channel slab), kernels 1x3x3 and 3x3x3 with "same" padding,
+ * spatial stride 1 or 2 (both axes), res_mode 0 | 1, dtypes DAT_F32 | DAT_BF16 | DAT_BF16X3.  Anything else returns
+ * DAT_ERR_UNSUPPORTED with a dat_last_error() text: there is no dense fall-back.  The block of output channels [64 s, 64 s + 64) reads
+ * only the input channels of slab s, against a packed 64 x 64 x taps weight image per slab that is block-diagonal inside it. */
+/* bytes of the packed weights: [KT*3*3][slab chunks: 1 bf16 | 2 fp32 | 3 bf16x3][Cout_pad][128 B] */
+size_t dat_conv3d_grouped_packed_weight_bytes(const dat_conv_desc* d, int groups);
+/* w: fp32 [Cout, Cin / groups, KT, KH, KW] (Caffe2's grouped filter layout).  DAT_BF16X3: the [W_hi | W_lo | W_hi] split is made here. */
+int dat_conv3d_grouped_pack_weights(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, int groups, const float* w, void* packed);
+/* y = act( conv_G(x, w)*scale[c] + bias[c] + residual ), arguments as dat_conv3d_fwd.  DAT_BF16X3: x = the hi / lo split tensor
+ * (dat_split_bf16x2), y / residual fp32, and y_split (may be NULL; needs Cout == out_cstride) receives the split of y as in
+ * dat_conv3d_fwd_x3; y_split must be NULL for the other dtypes. */
+int dat_conv3d_grouped_fwd(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, int groups, const void* x, const void* w_packed,
+                           const float* scale, const float* bias, const void* residual, void* y, void* y_split);
+/* algorithmic FLOPs of one launch: 2*Cout*(Cin/groups)*KT*KH*KW*frames*Ho*Wo */
+double dat_conv3d_grouped_flops(const dat_conv_desc* d, int groups);
+
 /* ---- stem: conv1 [1,7,7]/s[1,2,2] input packing (ResNet3D.py:258-262) ---------------------- */
 /* data NC(T)HW fp32 [N,3,T,H,W] -> packed [N*T, Ho+3, Wo, 64]:
  *   packed[f, r, ow, dkh*32 + kw*3 + c] = data[n, c, t, 2r-3+dkh, 2ow-3+kw] (0 outside), so that
