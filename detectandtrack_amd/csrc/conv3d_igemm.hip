@@ -87,11 +87,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
 
     // ---- XCD-aware block -> (channel block, tile) map (bijective for any grid size) ----
     unsigned bid = blockIdx.x;
-    if (!(p.ablate & 16)) {
-        const unsigned nx = 8, q = p.nblocks / nx, r = p.nblocks % nx;
-        const unsigned xcd = bid % nx, k = bid / nx;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    if (!(p.ablate & 16)) bid = xcd_block_map(bid, p.nblocks);
     int split, nb;
     unsigned tile;
     if (p.order) {   // weight-stationary order: all tiles of one (cout block, split) before the next one
@@ -426,19 +422,15 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
 #undef P_COMMIT
 #undef P_DMA
 
-    // ---- epilogue: affine/bias + residual + relu, staged through LDS so that HBM sees whole 128-B+ runs ----
-    // The MFMA result layout gives a lane 4 channels of ONE position (register r -> channel (r&3) + 8*(r>>2) + 4*(lane>>5)),
-    // i.e. 8-byte pieces 512+ bytes apart: written directly, every store instruction touched 32-64 different lines and a
-    // 256x128 tile took ~47k cycles (1x1 convs spent 80 % of their time here).  Each wave now transposes 32 positions x
-    // WN channels at a time through its own LDS slice (fp32, pitch WN*4+16 B: conflict-free b128 writes) and reads it
-    // back position-major, 16 B of output per lane, so one store instruction covers 4-8 complete position rows.
+    // ---- epilogue: affine/bias + residual + relu, staged through LDS so that HBM sees whole 128-B+ runs; one store instruction covers
+    // 4-8 complete position rows.  The scheme and its steps are conv_epilogue.h's; they are kept inline here because the helpers cost
+    // this kernel SGPR spills.  It shares the block map, the pitch and the split store ----
     static_assert(WN == 64, "epilogue staging assumes 64 channels per wave");
-    constexpr int EPITCH = WN * 4 + 16;
     constexpr int CPL = 16 / OES;                 // channels per lane in the store phase (8 bf16 / 4 fp32)
     constexpr int LPP = WN / CPL;                // lanes per position (8 / 16)
     constexpr int PPI = 64 / LPP;                // positions per store instruction (8 / 4)
     __syncthreads();                             // every wave is done with the patch
-    char* est = smem + wave * (32 * EPITCH);
+    char* est = smem + wave * (32 * EPI_PITCH);
     const int sl_c = (lane % LPP) * CPL;         // this lane's first channel inside the wave's 64
     const int sl_p = lane / LPP;
     const int cbase = n0 + wave_n * WN;
@@ -491,7 +483,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
         for (int i = 0; i < MT; ++i)
 #pragma unroll
             for (int g = 0; g < 4; ++g)
-                *(float4*)(est + (lane & 31) * EPITCH + (i * 32 + g * 8 + khalf * 4) * 4) =
+                *(float4*)(est + (lane & 31) * EPI_PITCH + (i * 32 + g * 8 + khalf * 4) * 4) =
                     make_float4(acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1], acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
         __builtin_amdgcn_wave_barrier();
         // phase 2: position-major read back, fused epilogue, 16-byte stores
@@ -501,7 +493,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
             float v[CPL];
 #pragma unroll
             for (int e4 = 0; e4 < CPL / 4; ++e4) {
-                const float4 t = *(const float4*)(est + pl * EPITCH + (sl_c + e4 * 4) * 4);
+                const float4 t = *(const float4*)(est + pl * EPI_PITCH + (sl_c + e4 * 4) * 4);
                 v[e4 * 4 + 0] = t.x; v[e4 * 4 + 1] = t.y; v[e4 * 4 + 2] = t.z; v[e4 * 4 + 3] = t.w;
             }
             const int pos = wave_p * WP + j * 32 + pl;
@@ -576,7 +568,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
                 for (int e = 0; e < CPL; ++e) v[e] = fmaxf(v[e], 0.f);
             }
             char* yp = ybase + (lpos * (unsigned)p.out_cs + (unsigned)c_st) * (unsigned)OES;
-            if (ODT == DAT_BF16) {
+            if (ODT == DAT_BF16) {   // (its own store: rows that are only 8-byte aligned and the channel tail go out in 8-byte pieces)
                 uint32_t o[CPL / 2];
 #pragma unroll
                 for (int e2 = 0; e2 < CPL / 2; ++e2) o[e2] = f2bf2(v[2 * e2], v[2 * e2 + 1]);
@@ -588,16 +580,9 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
                 }
             } else {
                 *(float4*)yp = make_float4(v[0], v[1], v[2], v[3]);
-                if (ODT == DAT_F32 && DT == DAT_BF16 && p.y_split) {
-                    // the same values as hi / lo bf16 halves for the next bf16x3 conv (bit-identical to dat_split_bf16x2 of the stored y):
-                    // 64-channel chunk q of the pixel: line 2q = hi, line 2q + 1 = lo; this lane's 4 channels = 8 bytes in each line
-                    const uint32_t h0 = f2bf2(v[0], v[1]), h1 = f2bf2(v[2], v[3]);
-                    const uint32_t l0 = f2bf2(v[0] - __uint_as_float(h0 << 16), v[1] - __uint_as_float(h0 & 0xffff0000u));
-                    const uint32_t l1 = f2bf2(v[2] - __uint_as_float(h1 << 16), v[3] - __uint_as_float(h1 & 0xffff0000u));
-                    char* sp = p.y_split + ((tile_pos + lpos) * (size_t)(2 * p.out_cs) + (size_t)((c_st >> 6) * 128 + (c_st & 63))) * 2;
-                    *(uint2*)sp = make_uint2(h0, h1);
-                    *(uint2*)(sp + 128) = make_uint2(l0, l1);
-                }
+                // bf16x3: 64-channel chunk q of the pixel: line 2q = hi, line 2q + 1 = lo; this lane's 4 channels = 8 bytes in each line
+                if (ODT == DAT_F32 && DT == DAT_BF16 && p.y_split)
+                    split_hi_lo_store(p.y_split + ((tile_pos + lpos) * (size_t)(2 * p.out_cs) + (size_t)((c_st >> 6) * 128 + (c_st & 63))) * 2, v);
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -674,14 +659,8 @@ __global__ void splitk_finish_kernel(const float* __restrict__ part, int ksplit,
             *(uint2*)(y + (opos * out_cs + c) * 2) = o;
         } else {
             *(float4*)(y + (opos * out_cs + c) * 4) = make_float4(v[0], v[1], v[2], v[3]);
-            if (y_split) {   // (bf16x3 mode: the hi / lo split of the same values, see the conv kernel's epilogue)
-                const uint32_t h0 = f2bf2(v[0], v[1]), h1 = f2bf2(v[2], v[3]);
-                const uint32_t l0 = f2bf2(v[0] - __uint_as_float(h0 << 16), v[1] - __uint_as_float(h0 & 0xffff0000u));
-                const uint32_t l1 = f2bf2(v[2] - __uint_as_float(h1 << 16), v[3] - __uint_as_float(h1 & 0xffff0000u));
-                char* sp = y_split + (opos * (size_t)(2 * out_cs) + (size_t)((c >> 6) * 128 + (c & 63))) * 2;
-                *(uint2*)sp = make_uint2(h0, h1);
-                *(uint2*)(sp + 128) = make_uint2(l0, l1);
-            }
+            // (bf16x3 mode: the hi / lo split of the same values, as in the conv kernel's epilogue)
+            if (y_split) split_hi_lo_store(y_split + (opos * (size_t)(2 * out_cs) + (size_t)((c >> 6) * 128 + (c & 63))) * 2, v);
         }
     }
 }
@@ -701,9 +680,9 @@ static long long linear_tiles(const dat_ctx* ctx, const dat_conv_desc* d, const 
     return (d->KT > 1 ? (long long)p.frames : 1) * ((per + bpv - 1) / bpv);
 }
 
-struct TileChoice {
-    int th_log2, tw_log2;
-};
+}  // namespace
+
+namespace dat_conv {
 
 // pick the 2^a x 2^b tile (a+b = log2(BP)) that wastes the fewest output positions, tie -> squarer patch
 TileChoice choose_tile(int Ho, int Wo, int bp_log2, int sh, int sw, int KH, int KW) {
@@ -728,6 +707,42 @@ TileChoice choose_tile(int Ho, int Wo, int bp_log2, int sh, int sw, int KH, int 
     }
     return best;
 }
+
+// tap table in stride-parity plane order: every plane is a dense (tile + halo / stride) patch whose rows are read consecutively
+void conv_build_tap_table(ConvParams& p) {
+    int n = 0;
+    p.tab_new = 0;
+    for (int py = 0; py < p.sh && py < p.KH; ++py)
+        for (int px = 0; px < p.sw && px < p.KW; ++px) {
+            bool first = true;
+            for (int kh = py; kh < p.KH; kh += p.sh)
+                for (int kw = px; kw < p.KW; kw += p.sw) {
+                    p.tab_tap[n] = kh * p.KW + kw;
+                    p.tab_rowoff[n] = (kh / p.sh) * p.PW + (kw / p.sw);
+                    p.tab_dy[n] = (short)py;
+                    p.tab_dx[n] = (short)px;
+                    if (first) p.tab_new |= 1u << n;
+                    first = false;
+                    ++n;
+                }
+        }
+    p.tab_n = n;
+}
+
+int conv_set_frame_window(dat_ctx* ctx, const dat_conv_desc* d, ConvParams& p, const char* who) {
+    p.in_lo = d->in_tn > 0 ? d->in_t0 : 0;
+    p.in_hi = d->in_tn > 0 ? d->in_t0 + d->in_tn : d->T;
+    DAT_ENFORCE(ctx, p.in_lo >= 0 && p.in_hi <= d->T, "%s: non-zero input frames [%d, %d) outside T %d", who, p.in_lo, p.in_hi, d->T);
+    p.ot0 = d->out_tn > 0 ? d->out_t0 : 0;
+    p.otn = d->out_tn > 0 ? d->out_tn : d->T;
+    DAT_ENFORCE(ctx, p.ot0 >= 0 && p.ot0 + p.otn <= d->T, "%s: output frames [%d, %d) outside T %d", who, p.ot0, p.ot0 + p.otn, d->T);
+    p.frames = d->frames / d->T * p.otn;
+    return DAT_OK;
+}
+
+}  // namespace dat_conv
+
+namespace {
 
 template <int DT, int BN, int BP, int WAVES_N, int NTAP, int ODT>
 int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ksplit, bool linear = false) {
@@ -790,27 +805,11 @@ int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ks
             p.tab_rowoff[i] = (i / p.KW) * p.PW + i % p.KW;
             p.tab_dy[i] = p.tab_dx[i] = 0;
         }
-    } else {   // tap table in stride-parity plane order
-        int n = 0;
-        p.tab_new = 0;
+    } else {
         DAT_ENFORCE(ctx, p.KH * p.KW <= 32, "conv3d: %dx%d spatial kernel exceeds the 32-entry tap table", p.KH, p.KW);
-        for (int py = 0; py < p.sh && py < p.KH; ++py)
-            for (int px = 0; px < p.sw && px < p.KW; ++px) {
-                bool first = true;
-                for (int kh = py; kh < p.KH; kh += p.sh)
-                    for (int kw = px; kw < p.KW; kw += p.sw) {
-                        p.tab_tap[n] = kh * p.KW + kw;
-                        p.tab_rowoff[n] = (kh / p.sh) * p.PW + (kw / p.sw);
-                        p.tab_dy[n] = (short)py;
-                        p.tab_dx[n] = (short)px;
-                        if (first) p.tab_new |= 1u << n;
-                        first = false;
-                        ++n;
-                    }
-            }
-        p.tab_n = n;
+        conv_build_tap_table(p);
     }
-    p.pw_magic = p.PW == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)p.PW - 1) / (unsigned)p.PW);
+    p.pw_magic = conv_pw_magic(p.PW);
     p.n_cchunks = p.x3 ? p.Cin / Mma<DT>::CK / 2 * 3 : p.Cin / Mma<DT>::CK;   // bf16x3: [hi | hi | lo] against [W_hi | W_lo | W_hi]
     p.ablate = ctx->dbg_ablate;
     p.nblk_n = p.Cout_pad / BN;
@@ -841,7 +840,7 @@ int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ks
     // sibling cout block no longer finds the patch in L2, and patch misses are waited for while weight misses are not.  Kept as a switch.
     p.order = ctx->dbg_order > 0;
     size_t lds = ((size_t)p.PH * p.PW * PPITCH + 1023) & ~(size_t)1023;     // whole 1-KiB DMA pieces
-    if (lds < 4 * 32 * (64 * 4 + 16)) lds = 4 * 32 * (64 * 4 + 16);         // epilogue staging slices
+    if (lds < EPI_SLICES_BYTES) lds = EPI_SLICES_BYTES;                     // epilogue staging slices
     DAT_ENFORCE(ctx, lds <= 160 * 1024, "conv3d: LDS patch of %zu bytes exceeds 160 KiB (tile %dx%d, stride %dx%d)", lds,
                 th, tw, p.sh, p.sw);
     auto kern = conv3d_igemm_kernel<DT, BN, BP, WAVES_N, 1, NTAP, ODT>;
@@ -954,14 +953,11 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
     p.res = (const char*)residual; p.res2 = (const char*)addend; p.y = (char*)y; p.y_split = (char*)y_split;
     p.zeros = (const char*)ctx->zeros;
     p.clk = ctx->prof_enabled ? (unsigned long long*)((char*)ctx->zeros + 256) : nullptr;
-    p.in_lo = d->in_tn > 0 ? d->in_t0 : 0;
-    p.in_hi = d->in_tn > 0 ? d->in_t0 + d->in_tn : d->T;
-    DAT_ENFORCE(ctx, p.in_lo >= 0 && p.in_hi <= d->T, "conv3d_fwd: non-zero input frames [%d, %d) outside T %d", p.in_lo, p.in_hi, d->T);
-    p.ot0 = d->out_tn > 0 ? d->out_t0 : 0;
-    p.otn = d->out_tn > 0 ? d->out_tn : d->T;
-    DAT_ENFORCE(ctx, p.ot0 >= 0 && p.ot0 + p.otn <= d->T, "conv3d_fwd: output frames [%d, %d) outside T %d", p.ot0,
-                p.ot0 + p.otn, d->T);
-    p.frames = d->frames / d->T * p.otn; p.T = d->T; p.H = d->H; p.W = d->W; p.Cin = x3 ? 2 * d->Cin : d->Cin;   // (x3: pixel pitch of the hi / lo split tensor)
+    {
+        const int rcw = conv_set_frame_window(ctx, d, p, "conv3d_fwd");
+        if (rcw != DAT_OK) return rcw;
+    }
+    p.T = d->T; p.H = d->H; p.W = d->W; p.Cin = x3 ? 2 * d->Cin : d->Cin;   // (x3: pixel pitch of the hi / lo split tensor)
     p.x3 = x3;
     dat_conv3d_out_shape(d, &p.Ho, &p.Wo);
     DAT_ENFORCE(ctx, p.Ho > 0 && p.Wo > 0, "conv3d_fwd: empty output %dx%d", p.Ho, p.Wo);
@@ -1020,16 +1016,7 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
     }
     const bool big = bp == 256;
     int tag = (small_n ? 64 : 128) * 10000 + bp * 10 + d->dtype;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    // (no event pairs inside a stream capture: an event recorded there becomes a graph node, and timing it later fails with
-    //  hipErrorInvalidHandle -- a sticky error the host framework then reports at an unrelated call)
-    hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
-    if (ctx->prof_enabled && ctx->prof_n < ctx->prof_cap && hipStreamIsCapturing(st, &cap_st) == hipSuccess &&
-        cap_st == hipStreamCaptureStatusNone) {
-        e0 = ctx->prof_ev[2 * ctx->prof_n];
-        e1 = ctx->prof_ev[2 * ctx->prof_n + 1];
-        hipEventRecord(e0, st);
-    }
+    ProfBracket prof(ctx, st);
     int rc;
     // big-tile kernel: one block per CU at a time, so the grid has to fill the chip several times and evenly (FPN P2: 2016 blocks on
     // 256 CUs = 7.9 rounds; P3's 528 blocks would run 3 rounds for 2.06 of work: 0.45 ms against 0.34 ms with the generic kernel)
@@ -1087,12 +1074,7 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
         else rc = d->dtype == DAT_BF16 ? DAT_CONV_LAUNCH(DAT_BF16, 128, 2, DAT_BF16) : DAT_CONV_LAUNCH(DAT_F32, 128, 2, DAT_F32);
 #undef DAT_CONV_LAUNCH
     }
-    if (e1) {
-        hipEventRecord(e1, st);
-        ctx->prof_flops[ctx->prof_n] = 2.0 * d->Cout * d->Cin * d->KT * d->KH * d->KW * (double)p.frames * p.Ho * p.Wo;
-        ctx->prof_tag[ctx->prof_n] = tag;
-        ctx->prof_n++;
-    }
+    prof.end(2.0 * d->Cout * d->Cin * d->KT * d->KH * d->KW * (double)p.frames * p.Ho * p.Wo, tag);
     return rc;
 }
 

@@ -1,5 +1,5 @@
-// Grouped forward 3D convolution (ResNeXt `branch2b`: kT x 3 x 3, C -> C in G groups of cg = C / G channels) for gfx950, with the fused
-// epilogue of the dense kernel (affine scale / bias, residual Sum, ReLU).  DESIGN.md section 3.8.
+// Grouped forward 3D convolution (ResNeXt `branch2b`: kT x 3 x 3, C -> C in G groups of cg = C / G channels) for gfx950, with the shared
+// fused epilogue (conv_epilogue.h: affine scale / bias, residual Sum, ReLU).  DESIGN.md section 3.8.
 //
 // The slab rule: an activation row in LDS is one 128-byte line = 64 bf16 channels, and for cg | 64 no group straddles a 64-channel slab.
 // The layer is therefore C / 64 independent 64 -> 64 convs: the block that owns output channels [64 s, 64 s + 64) stages ONLY the
@@ -8,10 +8,11 @@
 // elsewhere).  HBM traffic is the algorithmic minimum -- every input line is read by exactly one channel block per tile (plus halo),
 // the weights are C * 64 * taps elements instead of C * C * taps -- and the MFMA utilisation is cg / 64 by construction.
 //
-// The kernel keeps the dense implicit-GEMM kernel's machinery (conv3d_igemm.hip): LDS-DMA patch staging of tile + halo per (kt, chunk,
-// stride-parity plane), the ((row >> 1) & 7) XOR swizzle of the 16-byte slots, weights in MFMA A-fragment order straight from global
-// memory into registers, the XCD-aware block map and the LDS-transposed epilogue.  One variant: 64 channels x 256 positions per block,
-// every wave 64 channels x 64 positions, the table-driven tap loop (stride 1: one plane of 9 taps; stride 2: four parity planes).
+// The main loop is the dense implicit-GEMM kernel's table-driven one (conv3d_igemm.hip): LDS-DMA patch staging of tile + halo per (kt,
+// chunk, stride-parity plane), the ((row >> 1) & 7) XOR swizzle of the 16-byte slots, weights in MFMA A-fragment order straight from
+// global memory into registers.  The block map and the LDS-transposed epilogue are the helpers of conv_epilogue.h, the tile, tap table
+// and frame windows those of conv_internal.h.  One variant: 64 channels x 256 positions per block, every wave 64 channels x 64
+// positions (stride 1: one plane of 9 taps; stride 2: four parity planes).
 #include "conv_internal.h"
 
 using namespace dat_conv;
@@ -46,12 +47,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3d_grouped_kernel(const ConvP
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     // ---- XCD-aware block -> (slab, tile) map (bijective for any grid size): the slabs of one tile and neighbouring tiles share an XCD
-    unsigned bid = blockIdx.x;
-    {
-        const unsigned nx = 8, q = p.nblocks / nx, r = p.nblocks % nx;
-        const unsigned xcd = bid % nx, k = bid / nx;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    const unsigned bid = xcd_block_map(blockIdx.x, p.nblocks);
     const int slab = bid % p.nblk_n;
     unsigned tile = bid / p.nblk_n;
     const int fc = tile % p.otn;             // frame index fastest: the temporal re-reads of neighbouring output frames meet in the XCD's L2
@@ -139,7 +135,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3d_grouped_kernel(const ConvP
                     if (it < npatch_items) {
                         const int row = it >> 3;
                         const int slot = (it ^ (row >> 1)) & 7;
-                        const int prow = (int)__umulhi((unsigned)row, p.pw_magic), pcol = row - prow * p.PW;
+                        const int prow = (int)__umulhi((unsigned)row, p.pw_magic), pcol = row - prow * p.PW;   // (PW >= 2: pw_magic != 0)
                         const int ih = py0 + prow * p.psh, iw = px0 + pcol * p.psw;
                         const char* src = p.zeros;
                         if (ih >= 0 && ih < p.H && iw >= 0 && iw < p.W)
@@ -198,19 +194,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3d_grouped_kernel(const ConvP
     }
 #undef WD_PTR
 
-    // ---- epilogue: affine/bias + residual + relu, transposed through LDS so that HBM sees whole 16-byte channel runs per lane ----
-    // (the dense kernel's: MFMA register r of a lane = channel (r&3) + 8*(r>>2) + 4*(lane>>5) of ONE position; each wave transposes
-    //  32 positions x 64 channels at a time through its own fp32 slice, pitch 64*4+16 B)
-    constexpr int EPITCH = WN * 4 + 16;
+    // ---- epilogue (conv_epilogue.h): the dense kernel's without split-K, channel tail (Cout is a multiple of 64) and masking modes;
+    // the residual row is loaded where it is added ----
     constexpr int CPL = 16 / OES;                 // channels per lane in the store phase (8 bf16 / 4 fp32)
     constexpr int LPP = WN / CPL;                // lanes per position (8 / 16)
     constexpr int PPI = 64 / LPP;                // positions per store instruction (8 / 4)
-    constexpr int NQ = 32 / PPI;
     __syncthreads();                             // every wave is done with the patch
-    char* est = smem + wave * (32 * EPITCH);
-    const int sl_c = (lane % LPP) * CPL;
-    const int sl_p = lane / LPP;
-    const int c_st = n0 + sl_c;                  // (< Cout: Cout is a multiple of 64)
+    char* est = smem + wave * (32 * EPI_PITCH);
+    const int sl_c = (lane % LPP) * CPL, sl_p = lane / LPP;
+    const int c_st = n0 + sl_c;
     float sc[CPL], bi[CPL];
 #pragma unroll
     for (int e = 0; e < CPL; ++e) {
@@ -224,64 +216,25 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3d_grouped_kernel(const ConvP
 #pragma unroll
     for (int j = 0; j < PT; ++j) {
 #pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *(float4*)(est + (lane & 31) * EPITCH + (i * 32 + g * 8 + khalf * 4) * 4) =
-                    make_float4(acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1], acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
+        for (int i = 0; i < MT; ++i) epi_stage(est, lane & 31, khalf, i, acc[i][j]);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) {
+        for (int q = 0; q < 32 / PPI; ++q) {
             const int pl = q * PPI + sl_p;
             float v[CPL];
-#pragma unroll
-            for (int e4 = 0; e4 < CPL / 4; ++e4) {
-                const float4 t4 = *(const float4*)(est + pl * EPITCH + (sl_c + e4 * 4) * 4);
-                v[e4 * 4 + 0] = t4.x; v[e4 * 4 + 1] = t4.y; v[e4 * 4 + 2] = t4.z; v[e4 * 4 + 3] = t4.w;
-            }
+            epi_load(est, pl, sl_c, v);
             const int pos = wave * WP + j * 32 + pl;
             const int ohl = pos >> p.tw_log2, owl = pos & (TW - 1);
             if (oh0 + ohl >= p.Ho || ow0 + owl >= p.Wo) continue;
-            const unsigned off = ((unsigned)(ohl * p.Wo + owl) * (unsigned)p.out_cs + (unsigned)c_st) * (unsigned)OES;
-#pragma unroll
-            for (int e = 0; e < CPL; ++e) v[e] = v[e] * sc[e] + bi[e];
-            if (p.res_mode) {
-                const uint4 r = *(const uint4*)(rbase + off);
-                if (ODT == DAT_BF16) {
-                    const uint32_t ru[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-                    for (int e2 = 0; e2 < CPL / 2; ++e2) {
-                        v[2 * e2] += bf2f((uint16_t)(ru[e2 % 4] & 0xffff));
-                        v[2 * e2 + 1] += bf2f((uint16_t)(ru[e2 % 4] >> 16));
-                    }
-                } else {
-                    v[0] += __uint_as_float(r.x); v[1] += __uint_as_float(r.y);
-                    v[2] += __uint_as_float(r.z); v[3] += __uint_as_float(r.w);
-                }
-            }
-            if (p.relu) {
-#pragma unroll
-                for (int e = 0; e < CPL; ++e) v[e] = fmaxf(v[e], 0.f);
-            }
-            char* yp = ybase + off;
-            if (ODT == DAT_BF16) {
-                uint32_t o[CPL / 2];
-#pragma unroll
-                for (int e2 = 0; e2 < CPL / 2; ++e2) o[e2] = f2bf2(v[2 * e2], v[2 * e2 + 1]);
-                *(uint4*)yp = make_uint4(o[0], o[1 % (CPL / 2)], o[2 % (CPL / 2)], o[3 % (CPL / 2)]);
-            } else {
-                *(float4*)yp = make_float4(v[0], v[1], v[2], v[3]);
-                if (DT == DAT_BF16 && p.y_split) {
-                    // bf16x3: the same values as hi / lo bf16 halves for the next conv (bit-identical to dat_split_bf16x2 of the stored y):
-                    // 64-channel chunk q of the pixel: line 2q = hi, line 2q + 1 = lo; this lane's 4 channels = 8 bytes in each line
-                    const uint32_t h0 = f2bf2(v[0], v[1]), h1 = f2bf2(v[2], v[3]);
-                    const uint32_t l0 = f2bf2(v[0] - __uint_as_float(h0 << 16), v[1] - __uint_as_float(h0 & 0xffff0000u));
-                    const uint32_t l1 = f2bf2(v[2] - __uint_as_float(h1 << 16), v[3] - __uint_as_float(h1 & 0xffff0000u));
-                    char* sp = p.y_split + ((tile_pos + (size_t)(ohl * p.Wo + owl)) * (size_t)(2 * p.out_cs) + (size_t)((c_st >> 6) * 128 + (c_st & 63))) * 2;
-                    *(uint2*)sp = make_uint2(h0, h1);
-                    *(uint2*)(sp + 128) = make_uint2(l0, l1);
-                }
-            }
+            const unsigned lpos = (unsigned)(ohl * p.Wo + owl);
+            const unsigned off = (lpos * (unsigned)p.out_cs + (unsigned)c_st) * (unsigned)OES;
+            epi_affine(v, sc, bi);
+            if (p.res_mode) epi_residual<ODT>(v, *(const uint4*)(rbase + off), 1);
+            epi_relu(v, p.relu);
+            epi_store<ODT>(ybase + off, v);
+            // bf16x3: 64-channel chunk q of the pixel: line 2q = hi, line 2q + 1 = lo; this lane's 4 channels = 8 bytes in each line
+            if (ODT == DAT_F32 && DT == DAT_BF16 && p.y_split)
+                split_hi_lo_store(p.y_split + ((tile_pos + lpos) * (size_t)(2 * p.out_cs) + (size_t)((c_st >> 6) * 128 + (c_st & 63))) * 2, v);
         }
         __builtin_amdgcn_wave_barrier();
     }
@@ -339,19 +292,6 @@ int grouped_check(dat_ctx* ctx, const dat_conv_desc* d, int groups, const char* 
     return DAT_OK;
 }
 
-// the 2^a x 2^b tile (a + b = log2 positions) that wastes the fewest output positions, tie -> smaller halo (the dense kernel's rule)
-void grouped_tile(int Ho, int Wo, int s, int* th_log2, int* tw_log2) {
-    double best = 1e30;
-    for (int a = 0; a <= G_BP_LOG2; ++a) {
-        const int b = G_BP_LOG2 - a;
-        const long long th = 1 << a, tw = 1 << b;
-        const double waste = (double)(cdiv_ll(Ho, th) * cdiv_ll(Wo, tw) * th * tw) / ((double)Ho * Wo);
-        const double halo = (double)((th + 2 / s) * (tw + 2 / s)) / (double)(th * tw);
-        const double cost = waste * (1.0 + 0.15 * (halo - 1.0)) * (tw < 32 ? 1.06 : 1.0);
-        if (cost < best - 1e-9) { best = cost; *th_log2 = a; *tw_log2 = b; }
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -399,13 +339,9 @@ int dat_conv3d_grouped_fwd(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, i
     p.x = (const char*)x; p.w = (const char*)w_packed; p.scale = scale; p.bias = bias;
     p.res = (const char*)residual; p.y = (char*)y; p.y_split = (char*)y_split;
     p.zeros = (const char*)ctx->zeros;
-    p.in_lo = d->in_tn > 0 ? d->in_t0 : 0;
-    p.in_hi = d->in_tn > 0 ? d->in_t0 + d->in_tn : d->T;
-    DAT_ENFORCE(ctx, p.in_lo >= 0 && p.in_hi <= d->T, "conv3d_grouped_fwd: non-zero input frames [%d, %d) outside T %d", p.in_lo, p.in_hi, d->T);
-    p.ot0 = d->out_tn > 0 ? d->out_t0 : 0;
-    p.otn = d->out_tn > 0 ? d->out_tn : d->T;
-    DAT_ENFORCE(ctx, p.ot0 >= 0 && p.ot0 + p.otn <= d->T, "conv3d_grouped_fwd: output frames [%d, %d) outside T %d", p.ot0, p.ot0 + p.otn, d->T);
-    p.frames = d->frames / d->T * p.otn; p.T = d->T; p.H = d->H; p.W = d->W;
+    const int rcw = conv_set_frame_window(ctx, d, p, "conv3d_grouped_fwd");
+    if (rcw != DAT_OK) return rcw;
+    p.T = d->T; p.H = d->H; p.W = d->W;
     p.Cin = x3 ? 2 * d->Cin : d->Cin;            // (x3: pixel pitch of the hi / lo split tensor)
     p.x3 = x3;
     dat_conv3d_out_shape(d, &p.Ho, &p.Wo);
@@ -413,7 +349,8 @@ int dat_conv3d_grouped_fwd(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, i
     p.Cout = d->Cout; p.out_cs = d->out_cstride; p.Cout_pad = cout_pad_of(d);
     p.KT = d->KT; p.KH = 3; p.KW = 3; p.sh = p.sw = d->stride_h;
     p.pt = d->pad_t; p.ph = 1; p.pw = 1; p.relu = d->relu; p.res_mode = d->res_mode;
-    grouped_tile(p.Ho, p.Wo, p.sh, &p.th_log2, &p.tw_log2);
+    const TileChoice tc = choose_tile(p.Ho, p.Wo, G_BP_LOG2, p.sh, p.sw, 3, 3);
+    p.th_log2 = tc.th_log2; p.tw_log2 = tc.tw_log2;
     const int th = 1 << p.th_log2, tw = 1 << p.tw_log2;
     p.tile_w = tw;
     p.tiles_h = (p.Ho + th - 1) / th;
@@ -422,25 +359,8 @@ int dat_conv3d_grouped_fwd(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, i
     p.rsh = p.rsw = 1;
     p.PH = th + 2 / p.sh;
     p.PW = tw + 2 / p.sw;
-    {   // tap table in stride-parity plane order: every plane is a dense (tile + halo / stride) patch
-        int n = 0;
-        for (int py = 0; py < p.sh; ++py)
-            for (int px = 0; px < p.sw; ++px) {
-                bool first = true;
-                for (int kh = py; kh < 3; kh += p.sh)
-                    for (int kw = px; kw < 3; kw += p.sw) {
-                        p.tab_tap[n] = kh * 3 + kw;
-                        p.tab_rowoff[n] = (kh / p.sh) * p.PW + (kw / p.sw);
-                        p.tab_dy[n] = (short)py;
-                        p.tab_dx[n] = (short)px;
-                        if (first) p.tab_new |= 1u << n;
-                        first = false;
-                        ++n;
-                    }
-            }
-        p.tab_n = n;
-    }
-    p.pw_magic = (unsigned)((0x100000000ull + (unsigned)p.PW - 1) / (unsigned)p.PW);     // (PW >= 2)
+    conv_build_tap_table(p);
+    p.pw_magic = conv_pw_magic(p.PW);
     p.n_cchunks = slab_chunks(d->dtype);
     p.ksplit = 1;
     p.nblk_n = d->Cout / G_BN;
@@ -451,17 +371,10 @@ int dat_conv3d_grouped_fwd(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, i
     p.nblocks = (unsigned)nblocks;
     p.ntiles = (unsigned)(nblocks / p.nblk_n);
     size_t lds = ((size_t)p.PH * p.PW * PPITCH + 1023) & ~(size_t)1023;     // whole 1-KiB DMA pieces
-    if (lds < 4 * 32 * (64 * 4 + 16)) lds = 4 * 32 * (64 * 4 + 16);         // epilogue staging slices
+    if (lds < EPI_SLICES_BYTES) lds = EPI_SLICES_BYTES;                     // epilogue staging slices
     DAT_ENFORCE(ctx, lds <= 160 * 1024, "conv3d_grouped_fwd: LDS patch of %zu bytes exceeds 160 KiB (tile %dx%d)", lds, th, tw);
     hipStream_t st = (hipStream_t)s;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
-    if (ctx->prof_enabled && ctx->prof_n < ctx->prof_cap && hipStreamIsCapturing(st, &cap_st) == hipSuccess &&
-        cap_st == hipStreamCaptureStatusNone) {
-        e0 = ctx->prof_ev[2 * ctx->prof_n];
-        e1 = ctx->prof_ev[2 * ctx->prof_n + 1];
-        hipEventRecord(e0, st);
-    }
+    ProfBracket prof(ctx, st);
 #define DAT_GRP_LAUNCH(DT_, ODT_)                                                                      \
     do {                                                                                               \
         auto kern = conv3d_grouped_kernel<DT_, ODT_>;                                                  \
@@ -474,12 +387,7 @@ int dat_conv3d_grouped_fwd(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, i
     else DAT_GRP_LAUNCH(DAT_F32, DAT_F32);
 #undef DAT_GRP_LAUNCH
     DAT_CHECK_LAUNCH(ctx, "conv3d_grouped");
-    if (e1) {
-        hipEventRecord(e1, st);
-        ctx->prof_flops[ctx->prof_n] = 2.0 * d->Cout * (d->Cin / groups) * d->KT * 9 * (double)p.frames * p.Ho * p.Wo;
-        ctx->prof_tag[ctx->prof_n] = 64 * 10000 + 2570 + d->dtype;     // ("257 positions": the grouped kernel)
-        ctx->prof_n++;
-    }
+    prof.end(2.0 * d->Cout * (d->Cin / groups) * d->KT * 9 * (double)p.frames * p.Ho * p.Wo, 64 * 10000 + 2570 + d->dtype);   // ("257 positions": the grouped kernel)
     return DAT_OK;
 }
 

@@ -1,5 +1,6 @@
-// Internal header of the conv translation units (conv3d_igemm.hip: the generic implicit-GEMM kernel, its plan and the dispatcher;
-// conv_special.hip: the weights-stationary and big-tile kernels; conv_pack.hip: weight packing).  Not part of the C ABI.
+// Internal header of the conv translation units (conv3d_igemm.hip: the generic implicit-GEMM kernel, its plan, the dispatcher and the
+// launch prologue helpers below; conv_special.hip: the weights-stationary, K-streaming and big-tile kernels; conv_grouped.hip: the grouped
+// kernel; conv_pack.hip: weight packing).  conv_epilogue.h, included below, holds the device pieces the kernels share.  Not part of the C ABI.
 #ifndef DAT_CONV_INTERNAL_H
 #define DAT_CONV_INTERNAL_H
 
@@ -98,6 +99,11 @@ __device__ __forceinline__ float res_combine(float v, float r, int mode) { retur
 // conv of the LAST reader of y finishes the sum and applies y's ReLU backward in one epilogue (dat_conv3d_fwd_sum_mask; training.py bwd_Conv)
 __device__ __forceinline__ float res_combine4(float v, float old, float m) { return m > 0.f ? v + old : 0.f; }
 
+}  // namespace dat_conv
+
+#include "conv_epilogue.h"
+
+namespace dat_conv __attribute__((visibility("hidden"))) {
 
 // compile-time index sequence for the hand-scheduled loops (`#pragma unroll` is refused for bodies of this size, and immediates /
 // register-ring slots need constant indices)
@@ -111,6 +117,43 @@ inline int cout_pad_of(const dat_conv_desc* d) {
     const int bn = d->Cout <= 64 ? 64 : 128;
     return (d->Cout + bn - 1) / bn * bn;
 }
+
+// ---- launch prologue shared by launch_conv and dat_conv3d_grouped_fwd (conv3d_igemm.hip) ----
+struct TileChoice {
+    int th_log2, tw_log2;
+};
+// the 2^a x 2^b output tile (a + b = bp_log2) that wastes the fewest output positions, tie -> squarer patch
+TileChoice choose_tile(int Ho, int Wo, int bp_log2, int sh, int sw, int KH, int KW);
+// spatial tap schedule in stride-parity plane order (tab_*, tab_new, tab_n) from KH / KW / sh / sw / PW; KH * KW <= 32
+void conv_build_tap_table(ConvParams& p);
+// ConvParams::pw_magic
+inline unsigned conv_pw_magic(int PW) { return PW == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)PW - 1) / (unsigned)PW); }
+// in_lo / in_hi / ot0 / otn / frames of `p` from the descriptor's frame windows; `who` names the entry point in the error text
+int conv_set_frame_window(dat_ctx* ctx, const dat_conv_desc* d, ConvParams& p, const char* who);
+
+// per-launch timing (dat_prof_enable): takes the context's next event pair and records the first one, unless the stream is being
+// captured -- an event recorded there becomes a graph node, and timing it later fails with hipErrorInvalidHandle, a sticky error the
+// host framework then reports at an unrelated call.  end() records the second event with the launch's flops and kernel tag.
+struct ProfBracket {
+    dat_ctx* ctx;
+    hipStream_t st;
+    hipEvent_t e1 = nullptr;
+    ProfBracket(dat_ctx* ctx_, hipStream_t st_) : ctx(ctx_), st(st_) {
+        hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
+        if (ctx->prof_enabled && ctx->prof_n < ctx->prof_cap && hipStreamIsCapturing(st, &cap_st) == hipSuccess &&
+            cap_st == hipStreamCaptureStatusNone) {
+            e1 = ctx->prof_ev[2 * ctx->prof_n + 1];
+            hipEventRecord(ctx->prof_ev[2 * ctx->prof_n], st);
+        }
+    }
+    void end(double flops, int tag) {
+        if (!e1) return;
+        hipEventRecord(e1, st);
+        ctx->prof_flops[ctx->prof_n] = flops;
+        ctx->prof_tag[ctx->prof_n] = tag;
+        ctx->prof_n++;
+    }
+};
 
 // conv_special.hip
 int ctx_num_cu(dat_ctx* ctx);

@@ -36,12 +36,11 @@ template <int TWL>
 __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv3x3_c64_ws_kernel(const Ws64Params p) {
     constexpr int TW = 1 << TWL, TH = 256 >> TWL, PW = TW + 2, PH = TH + 2;
     constexpr int NPIX = PH * PW, NPIECE = (NPIX * 8 + 63) / 64, PBYTES = NPIECE * 1024, UMAX = (NPIECE + 3) / 4;
-    constexpr int EPITCH = 64 * 4 + 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int khalf = lane >> 5, n = lane & 31;
-    char* const est = smem + 2 * PBYTES + wave * (32 * EPITCH);
+    char* const est = smem + 2 * PBYTES + wave * (32 * EPI_PITCH);
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -198,38 +197,20 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 1))
         for (int j = 0; j < 2; ++j) {
             if (p.res_mode && j == 0) res_fetch(1, rq[1]);
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *(float4*)(est + n * EPITCH + (i * 32 + g * 8 + khalf * 4) * 4) =
-                        make_float4(acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1], acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
+            for (int i = 0; i < 2; ++i) epi_stage(est, n, khalf, i, acc[i][j]);
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int pl = q * 8 + sl_p;
-                const float4 t0 = *(const float4*)(est + pl * EPITCH + sl_c * 4);
-                const float4 t1 = *(const float4*)(est + pl * EPITCH + sl_c * 4 + 16);
-                float v[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+                float v[8];
+                epi_load(est, pl, sl_c, v);
                 const int ohl = TWL == 5 ? 2 * wave + j : 4 * wave + 2 * j + (pl >> 4), owl = TWL == 5 ? pl : (pl & 15);
                 if (oh0 + ohl >= p.H || ow0 + owl >= p.W || (p.ablate & 4)) continue;
                 const unsigned lpos = (unsigned)(ohl * p.W + owl);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = v[e] * sc[e] + bi[e];
-                if (p.res_mode) {
-                    const uint4 r = rq[j][q];
-                    const uint32_t ru[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-                    for (int e2 = 0; e2 < 4; ++e2) {
-                        v[2 * e2] += bf2f((uint16_t)(ru[e2] & 0xffff));
-                        v[2 * e2 + 1] += bf2f((uint16_t)(ru[e2] >> 16));
-                    }
-                }
-                if (p.relu) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                }
-                *(uint4*)(ybase + (lpos * (unsigned)p.out_cs + (unsigned)sl_c) * 2u) =
-                    make_uint4(f2bf2(v[0], v[1]), f2bf2(v[2], v[3]), f2bf2(v[4], v[5]), f2bf2(v[6], v[7]));
+                epi_affine(v, sc, bi);
+                if (p.res_mode) epi_residual<DAT_BF16>(v, rq[j][q], 1);
+                epi_relu(v, p.relu);
+                epi_store<DAT_BF16>(ybase + (lpos * (unsigned)p.out_cs + (unsigned)sl_c) * 2u, v);
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -328,36 +309,19 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 1))
             for (int mb = 0; mb < 8; ++mb) Mma<DAT_BF16>::step(wa[mb][ks], bcur[ks], acc[mb]);
         // ---- epilogue: transpose through this wave's LDS slice, then two complete output rows per store instruction ----
 #pragma unroll
-        for (int mb = 0; mb < 8; ++mb)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *(float4*)(est + n * EPITCH + (mb * 32 + g * 8 + khalf * 4) * 4) =
-                    make_float4(acc[mb][g * 4 + 0], acc[mb][g * 4 + 1], acc[mb][g * 4 + 2], acc[mb][g * 4 + 3]);
+        for (int mb = 0; mb < 8; ++mb) epi_stage<EPITCH>(est, n, khalf, mb, acc[mb]);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
             const int pl = q * 2 + sl_p;
-            const float4 t0 = *(const float4*)(est + pl * EPITCH + sl_c * 4);
-            const float4 t1 = *(const float4*)(est + pl * EPITCH + sl_c * 4 + 16);
-            float v[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+            float v[8];
+            epi_load<8, EPITCH>(est, pl, sl_c, v);
             const unsigned pos = pos0 + (unsigned)pl;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = v[e] * sc[e] + bi[e];
-            if (p.res_mode) {
-                const uint32_t ru[4] = {rr[q].x, rr[q].y, rr[q].z, rr[q].w};
-#pragma unroll
-                for (int e2 = 0; e2 < 4; ++e2) {
-                    v[2 * e2] += bf2f((uint16_t)(ru[e2] & 0xffff));
-                    v[2 * e2 + 1] += bf2f((uint16_t)(ru[e2] >> 16));
-                }
-            }
-            if (p.relu) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-            }
+            epi_affine(v, sc, bi);
+            if (p.res_mode) epi_residual<DAT_BF16>(v, rr[q], 1);
+            epi_relu(v, p.relu);
             if (pos < (unsigned)p.npos)
-                *(uint4*)(p.y + (size_t)((pos * (unsigned)p.out_cs + (unsigned)sl_c) * 2u)) =
-                    make_uint4(f2bf2(v[0], v[1]), f2bf2(v[2], v[3]), f2bf2(v[4], v[5]), f2bf2(v[6], v[7]));
+                epi_store<DAT_BF16>(p.y + (size_t)((pos * (unsigned)p.out_cs + (unsigned)sl_c) * 2u), v);
         }
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -528,10 +492,7 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 1))
             for (int mb = 0; mb < MBW; ++mb) {
                 const int cl = (pass * MBW + mb) * 32 + sq * 8;    // this lane's 8 channels inside the part
                 const int c0 = c_part0 + cl;
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *(float4*)(est + n * EPITCH + (g * 8 + khalf * 4) * 4) =
-                        make_float4(acc[mb][g * 4 + 0], acc[mb][g * 4 + 1], acc[mb][g * 4 + 2], acc[mb][g * 4 + 3]);
+                epi_stage<EPITCH>(est, n, khalf, 0, acc[mb]);
                 __builtin_amdgcn_wave_barrier();
                 const float4 s0 = *(const float4*)(sbl + cl), s1 = *(const float4*)(sbl + cl + 4);
                 const float4 b0 = *(const float4*)(sbl + MBP * 32 + cl), b1 = *(const float4*)(sbl + MBP * 32 + cl + 4);
@@ -540,36 +501,15 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 1))
 #pragma unroll
                 for (int r = 0; r < 2; ++r) {
                     const int pl = r * 16 + spl;
-                    const float4 t0 = *(const float4*)(est + pl * EPITCH + sq * 32);
-                    const float4 t1 = *(const float4*)(est + pl * EPITCH + sq * 32 + 16);
-                    float v[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = v[e] * sc[e] + bi[e];
-                    if (m4) {
-                        const uint4 qa = rr[0][mb][r], qm = NPASS == 1 ? rm[NPASS == 1 ? mb : 0][r] : rr[NPASS - 1][mb][r];
-                        const uint32_t au[4] = {qa.x, qa.y, qa.z, qa.w}, mu[4] = {qm.x, qm.y, qm.z, qm.w};
-#pragma unroll
-                        for (int e2 = 0; e2 < 4; ++e2) {
-                            v[2 * e2] = res_combine4(v[2 * e2], bf2f((uint16_t)(au[e2] & 0xffff)), bf2f((uint16_t)(mu[e2] & 0xffff)));
-                            v[2 * e2 + 1] = res_combine4(v[2 * e2 + 1], bf2f((uint16_t)(au[e2] >> 16)), bf2f((uint16_t)(mu[e2] >> 16)));
-                        }
-                    } else if (p.res_mode) {            // modes 1 / 2: Sum (mode 3 layers stay on the generic kernel: dat_conv3d_fwd's dispatcher)
-                        const uint4 q = rr[pass][mb][r];
-                        const uint32_t ru[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                        for (int e2 = 0; e2 < 4; ++e2) {
-                            v[2 * e2] += bf2f((uint16_t)(ru[e2] & 0xffff));
-                            v[2 * e2 + 1] += bf2f((uint16_t)(ru[e2] >> 16));
-                        }
-                    }
-                    if (p.relu) {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                    }
+                    float v[8];
+                    epi_load<8, EPITCH>(est, pl, sq * 8, v);
+                    epi_affine(v, sc, bi);
+                    if (m4) epi_residual4<DAT_BF16>(v, rr[0][mb][r], NPASS == 1 ? rm[NPASS == 1 ? mb : 0][r] : rr[NPASS - 1][mb][r]);
+                    else if (p.res_mode) epi_residual<DAT_BF16>(v, rr[pass][mb][r], 1);   // modes 1 / 2: Sum (mode 3 layers stay on the generic kernel: dat_conv3d_fwd's dispatcher)
+                    epi_relu(v, p.relu);
                     if (live[r] && c0 < p.cout) {
                         const unsigned pos = pos0 + (unsigned)pl;
-                        *(uint4*)(p.y + ((size_t)pos * (unsigned)p.out_cs + (unsigned)c0) * 2u) =
-                            make_uint4(f2bf2(v[0], v[1]), f2bf2(v[2], v[3]), f2bf2(v[4], v[5]), f2bf2(v[6], v[7]));
+                        epi_store<DAT_BF16>(p.y + ((size_t)pos * (unsigned)p.out_cs + (unsigned)c0) * 2u, v);
                     }
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -614,7 +554,6 @@ constexpr int KS_THREADS = 512;
 constexpr int KS_XBYTES = 256 * 128, KS_WBYTES = 8 * 4 * 1024;      // one K chunk of the input tile / of the weights of a cout block
 
 __global__ __launch_bounds__(KS_THREADS) void conv1x1_ks_kernel(const PwKsParams p) {
-    constexpr int EPITCH = 64 * 4 + 16;                 // fp32 transpose row of one position: 64 channels + pad
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const xb = smem;                              // [3][256 rows x 128 B], XOR-swizzled 16-byte slots
     char* const wb = smem + 3 * KS_XBYTES;              // [2][8 row blocks][4 k-slices][64 lanes][16 B]
@@ -622,13 +561,9 @@ __global__ __launch_bounds__(KS_THREADS) void conv1x1_ks_kernel(const PwKsParams
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int khalf = lane >> 5, n = lane & 31;
     // block -> (position tile, cout block): the cout blocks of a tile read the same input rows, so they must share an L2 -- consecutive LOGICAL
-    // ids on one XCD (the bijection of conv3d_igemm_kernel; hardware block b runs on XCD b % 8), not consecutive hardware ids
+    // ids on one XCD (xcd_block_map; hardware block b runs on XCD b % 8), not consecutive hardware ids
     unsigned bid = blockIdx.x;
-    if (p.xcd) {
-        const unsigned nx = 8, q = gridDim.x / nx, r = gridDim.x % nx;
-        const unsigned xcd = bid % nx, k = bid / nx;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    if (p.xcd) bid = xcd_block_map(bid, gridDim.x);
     const int cb = bid % p.ncb;
     const unsigned pos0 = (bid / p.ncb) * 256u;
     const int wq = wave & 3, ph = wave >> 2;            // cout quarter (row blocks 2 wq, 2 wq + 1) / position half (tiles 4 ph .. 4 ph + 3)
@@ -719,7 +654,7 @@ __global__ __launch_bounds__(KS_THREADS) void conv1x1_ks_kernel(const PwKsParams
 #undef KS_DMA_W
 #undef KS_COMPUTE
     // ---- epilogue ----
-    char* const est = smem + wave * (32 * EPITCH);
+    char* const est = smem + wave * (32 * EPI_PITCH);
     const int sq = lane & 7, spl = lane >> 3;           // store phase: lane = 8 channels (sq) of one of 8 positions per round
     const int c0 = cb * 256 + wq * 64 + sq * 8;         // first of this lane's 8 output channels
     float sc[8], bi[8];                                 // channels past the stored Cout: 0 / 0 (their zero weight rows give zeros)
@@ -751,43 +686,22 @@ __global__ __launch_bounds__(KS_THREADS) void conv1x1_ks_kernel(const PwKsParams
             }
         }
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *(float4*)(est + n * EPITCH + (i * 32 + g * 8 + khalf * 4) * 4) =
-                    make_float4(acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1], acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
+        for (int i = 0; i < 2; ++i) epi_stage(est, n, khalf, i, acc[i][j]);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int pl = r * 8 + spl;
-            const float4 t0 = *(const float4*)(est + pl * EPITCH + sq * 32);
-            const float4 t1 = *(const float4*)(est + pl * EPITCH + sq * 32 + 16);
-            float v[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = v[e] * sc[e] + bi[e];
-            if (p.res_mode == 4) {                      // mode 4: SUM with the output's present contents, MASKED by the residual operand
-                const uint32_t ru[4] = {rr[r].x, rr[r].y, rr[r].z, rr[r].w}, au[4] = {ra[r].x, ra[r].y, ra[r].z, ra[r].w};
-#pragma unroll
-                for (int e2 = 0; e2 < 4; ++e2) {
-                    v[2 * e2] = res_combine4(v[2 * e2], bf2f((uint16_t)(au[e2] & 0xffff)), bf2f((uint16_t)(ru[e2] & 0xffff)));
-                    v[2 * e2 + 1] = res_combine4(v[2 * e2 + 1], bf2f((uint16_t)(au[e2] >> 16)), bf2f((uint16_t)(ru[e2] >> 16)));
-                }
-            } else if (p.res_mode) {                    // modes 1 / 2: Sum; mode 3: MASK by the forward input of the conv whose data gradient this is
-                const uint32_t ru[4] = {rr[r].x, rr[r].y, rr[r].z, rr[r].w};
-#pragma unroll
-                for (int e2 = 0; e2 < 4; ++e2) {
-                    v[2 * e2] = res_combine(v[2 * e2], bf2f((uint16_t)(ru[e2] & 0xffff)), p.res_mode);
-                    v[2 * e2 + 1] = res_combine(v[2 * e2 + 1], bf2f((uint16_t)(ru[e2] >> 16)), p.res_mode);
-                }
-            }
-            if (p.relu) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-            }
+            float v[8];
+            epi_load(est, pl, sq * 8, v);
+            epi_affine(v, sc, bi);
+            // mode 4: SUM with the output's present contents, MASKED by the residual operand; modes 1 / 2: Sum; mode 3: MASK by the forward
+            // input of the conv whose data gradient this is
+            if (p.res_mode == 4) epi_residual4<DAT_BF16>(v, ra[r], rr[r]);
+            else if (p.res_mode) epi_residual<DAT_BF16>(v, rr[r], p.res_mode);
+            epi_relu(v, p.relu);
             const unsigned pos = tile0 + (unsigned)pl;
             if (pos < p.npos && c0 < p.cout)
-                *(uint4*)(p.y + ((size_t)pos * (unsigned)p.out_cs + (unsigned)c0) * 2u) =
-                    make_uint4(f2bf2(v[0], v[1]), f2bf2(v[2], v[3]), f2bf2(v[4], v[5]), f2bf2(v[6], v[7]));
+                epi_store<DAT_BF16>(p.y + ((size_t)pos * (unsigned)p.out_cs + (unsigned)c0) * 2u, v);
         }
         __builtin_amdgcn_wave_barrier();
     }
@@ -825,7 +739,6 @@ __global__ __launch_bounds__(KS_THREADS) void conv_kt1x1_ks_kernel(const TkParam
     constexpr int NJ = NWQ;                             // 32-position tiles per wave (8 / NWQ position parts of 32 * NWQ positions)
     constexpr int WBYTES = CB / 32 * 4 * 1024;          // one K chunk of the weights of a cout block: 32 KB
     constexpr int WPIECES = CB / 64;                    // 1-KB weight pieces each wave copies per chunk
-    constexpr int EPITCH = 64 * 4 + 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const xb = smem;                              // [3][256 rows x 128 B], XOR-swizzled 16-byte slots
     char* const wb = smem + 3 * KS_XBYTES;              // [2][CB / 32 row blocks][4 k-slices][64 lanes][16 B]
@@ -833,11 +746,7 @@ __global__ __launch_bounds__(KS_THREADS) void conv_kt1x1_ks_kernel(const TkParam
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int khalf = lane >> 5, n = lane & 31;
     unsigned bid = blockIdx.x;
-    if (p.xcd) {
-        const unsigned nx = 8, q = gridDim.x / nx, r = gridDim.x % nx;
-        const unsigned xcd = bid % nx, k = bid / nx;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    if (p.xcd) bid = xcd_block_map(bid, gridDim.x);
     const int cb = bid % p.ncb;
     const unsigned pos0 = (bid / p.ncb) * 256u;
     const int wq = wave % NWQ, ph = wave / NWQ;         // cout quarter (row blocks 2 wq, 2 wq + 1) / position part (tiles NJ ph .. NJ ph + NJ - 1)
@@ -925,8 +834,8 @@ __global__ __launch_bounds__(KS_THREADS) void conv_kt1x1_ks_kernel(const TkParam
 #undef TK_DMA_X
 #undef TK_DMA_W
 #undef TK_COMPUTE
-    // ---- epilogue (conv1x1_ks_kernel's, modes 0 / 1) ----
-    char* const est = smem + wave * (32 * EPITCH);
+    // ---- epilogue (conv1x1_ks_kernel's decode and prefetch, modes 0 / 1) ----
+    char* const est = smem + wave * (32 * EPI_PITCH);
     const int sq = lane & 7, spl = lane >> 3;
     const int c0 = cb * CB + wq * 64 + sq * 8;
     float sc[8], bi[8];
@@ -950,36 +859,19 @@ __global__ __launch_bounds__(KS_THREADS) void conv_kt1x1_ks_kernel(const TkParam
             }
         }
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *(float4*)(est + n * EPITCH + (i * 32 + g * 8 + khalf * 4) * 4) =
-                    make_float4(acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1], acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
+        for (int i = 0; i < 2; ++i) epi_stage(est, n, khalf, i, acc[i][j]);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int pl = r * 8 + spl;
-            const float4 t0 = *(const float4*)(est + pl * EPITCH + sq * 32);
-            const float4 t1 = *(const float4*)(est + pl * EPITCH + sq * 32 + 16);
-            float v[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = v[e] * sc[e] + bi[e];
-            if (p.res_mode) {
-                const uint32_t ru[4] = {rr[r].x, rr[r].y, rr[r].z, rr[r].w};
-#pragma unroll
-                for (int e2 = 0; e2 < 4; ++e2) {
-                    v[2 * e2] = res_combine(v[2 * e2], bf2f((uint16_t)(ru[e2] & 0xffff)), 1);
-                    v[2 * e2 + 1] = res_combine(v[2 * e2 + 1], bf2f((uint16_t)(ru[e2] >> 16)), 1);
-                }
-            }
-            if (p.relu) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-            }
+            float v[8];
+            epi_load(est, pl, sq * 8, v);
+            epi_affine(v, sc, bi);
+            if (p.res_mode) epi_residual<DAT_BF16>(v, rr[r], 1);
+            epi_relu(v, p.relu);
             const unsigned pos = tile0 + (unsigned)pl;
             if (pos < p.npos && c0 < p.cout)
-                *(uint4*)(p.y + ((size_t)pos * (unsigned)p.out_cs + (unsigned)c0) * 2u) =
-                    make_uint4(f2bf2(v[0], v[1]), f2bf2(v[2], v[3]), f2bf2(v[4], v[5]), f2bf2(v[6], v[7]));
+                epi_store<DAT_BF16>(p.y + ((size_t)pos * (unsigned)p.out_cs + (unsigned)c0) * 2u, v);
         }
         __builtin_amdgcn_wave_barrier();
     }
@@ -1016,12 +908,7 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int khalf = lane >> 5, n = lane & 31;
 
     // ---- XCD-aware block -> (channel block, tile, frame) map, as in conv3d_igemm_kernel ----
-    unsigned bid = blockIdx.x;
-    {
-        const unsigned nx = 8, q = p.nblocks / nx, r = p.nblocks % nx;
-        const unsigned xcd = bid % nx, k = bid / nx;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    const unsigned bid = xcd_block_map(blockIdx.x, p.nblocks);
     const int nb = bid % p.nblk_n;
     unsigned tile = bid / p.nblk_n;
     const int fc = tile % p.otn; tile /= p.otn;
@@ -1173,7 +1060,9 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 1))
 #undef BT_DMA
 
     // ---- epilogue: per-wave LDS transpose of 32 positions x 64 channels at a time, affine + residual + ReLU, 16-byte stores ----
-    constexpr int EPITCH = 64 * 4 + 16;
+    // (the steps of conv_epilogue.h kept inline: this hand-scheduled kernel measured 0.6 % slower on the FPN P2 output conv with the helpers,
+    //  DESIGN.md section 3.9)
+    constexpr int EPITCH = EPI_PITCH;
     char* const est = smem + wave * (32 * EPITCH);             // (the patch buffers are free: the loop ended with a barrier)
     const int sl_c = (lane & 7) * 8, sl_p = lane >> 3;
     const size_t tile_pos = ((size_t)f * p.Ho + oh0) * p.Wo + ow0;
@@ -1524,7 +1413,7 @@ int launch_ws64(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
     DAT_ENFORCE(ctx, best_tiles > 0 && best_tiles < (1ll << 31), "conv3d: %lld tiles unsupported", best_tiles);
     p.ntiles = (int)best_tiles;
     const int npiece = ((th + 2) * (tw + 2) * 8 + 63) / 64;
-    const size_t lds = (size_t)2 * npiece * 1024 + 4 * 32 * (64 * 4 + 16);
+    const size_t lds = (size_t)2 * npiece * 1024 + EPI_SLICES_BYTES;
     const unsigned grid = (unsigned)std::min<long long>(best_tiles, persist_cus(ctx, 8));
     if (best_twl == 5) {
         if (dat_ensure_lds(ctx, (const void*)conv3x3_c64_ws_kernel<5>, 160 * 1024) != DAT_OK) return DAT_ERR_LAUNCH;
