@@ -281,11 +281,15 @@ def _build_defaults():
     # (model_builder.py:848-856).  False (default): a grouped ConvTranspose in Caffe2's filter layout (C_in, C_out / group, k, k) -- frame t
     # has its own [C, K, 4, 4] block.  True: what the pinned Caffe2 (b4e1588, Feb 2018: ConvTranspose has no `group` argument yet and brew
     # creates the full [T*C, T*K, 4, 4] filter) would execute -- the argument is dropped and the deconv is dense over T*C -> T*K channels
+    # TRAIN_GROUPED_CONV (opt-in, training): model_builder.create(train=True) accepts a grouped (ResNeXt, RESNETS.NUM_GROUPS > 1) body; its
+    # `branch2b` layers take the grouped data-gradient layer and wgrad_grouped_kernel.  False keeps the builder's
+    # NotImplementedError until the path has been measured at full size
     c.HIP = AttrDict({'DTYPE': 'bf16', 'KEYFRAME_DCE': False, 'DEVICE_KPS_DECODE': True, 'FRAME_TRUNK_CACHE': 0,
                       'DEVICE_BOX_RESULTS': True, 'FUSE_STEM_POOL': True, 'RCCL_DIRECT': False,
                       'PIPELINE_DEPTH': 4, 'CLIP_GRAPH': True, 'IMS_PER_FORWARD': 1, 'FUSE_RELU_BWD': True, 'FUSE_RELU_SUM_BWD': True, 'PERSISTENT_CU_SHARE': 50, 'DET_SPARE_ROWS': 4,
                       'DEFER_WGRAD_FINISH': True, 'MAX_GRAPHS_PER_SLOT': 6, 'PAD_TAIL_FORWARD': True,
-                      'OVERLAP_ALLREDUCE': True, 'WGRAD_PW_BATCH': 16, 'DEVICE_ROI_SAMPLING': True, 'DECONV_GROUP_IGNORED': False, 'STEM_FROM_UINT8': True})
+                      'OVERLAP_ALLREDUCE': True, 'WGRAD_PW_BATCH': 16, 'DEVICE_ROI_SAMPLING': True, 'DECONV_GROUP_IGNORED': False, 'STEM_FROM_UINT8': True,
+                      'TRAIN_GROUPED_CONV': False})
     return c
 
 

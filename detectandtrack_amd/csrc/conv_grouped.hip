@@ -1,5 +1,6 @@
-// Grouped forward 3D convolution (ResNeXt `branch2b`: kT x 3 x 3, C -> C in G groups of cg = C / G channels) for gfx950, with the shared
-// fused epilogue (conv_epilogue.h: affine scale / bias, residual Sum, ReLU).  DESIGN.md section 3.8.
+// Grouped 3D convolution (ResNeXt `branch2b`: kT x 3 x 3, C -> C in G groups of cg = C / G channels) for gfx950: the forward kernel with
+// the shared fused epilogue (conv_epilogue.h: affine scale / bias, residual Sum or mask, ReLU) -- which, with the weights of
+// dat_conv3d_grouped_pack_weights_dgrad, is also the data gradient -- and the weight-gradient kernel further down.  DESIGN.md section 3.8.
 //
 // The slab rule: an activation row in LDS is one 128-byte line = 64 bf16 channels, and for cg | 64 no group straddles a 64-channel slab.
 // The layer is therefore C / 64 independent 64 -> 64 convs: the block that owns output channels [64 s, 64 s + 64) stages ONLY the
@@ -30,7 +31,9 @@ constexpr int G_BP_LOG2 = 8;
 
 // ConvParams as the dense kernel reads them, with two fields re-read: n_cchunks = K chunks of ONE slab (bf16 1, fp32 2, bf16x3 3) and
 // nblk_n = slabs (C / 64).  ksplit is 1, lin_* / order / res2 / part are unused.
-template <int DT, int ODT>
+// MASK: the residual operand masks instead of adding (res_mode 3, the data-gradient layer of training: y = residual > 0 ? v : 0) -- an
+// instantiation of its own, so the inference instantiations keep their registers and their code.
+template <int DT, int ODT, bool MASK = false>
 __global__ __launch_bounds__(NTHREADS, 2) void conv3d_grouped_kernel(const ConvParams p) {
     constexpr int ES = ElemOf<DT>::size;
     constexpr int OES = ElemOf<ODT>::size;
@@ -229,7 +232,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3d_grouped_kernel(const ConvP
             const unsigned lpos = (unsigned)(ohl * p.Wo + owl);
             const unsigned off = (lpos * (unsigned)p.out_cs + (unsigned)c_st) * (unsigned)OES;
             epi_affine(v, sc, bi);
-            if (p.res_mode) epi_residual<ODT>(v, *(const uint4*)(rbase + off), 1);
+            if (MASK || p.res_mode) epi_residual<ODT>(v, *(const uint4*)(rbase + off), MASK ? 3 : 1);
             epi_relu(v, p.relu);
             epi_store<ODT>(ybase + off, v);
             // bf16x3: 64-channel chunk q of the pixel: line 2q = hi, line 2q + 1 = lo; this lane's 4 channels = 8 bytes in each line
@@ -244,8 +247,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3d_grouped_kernel(const ConvP
 // lane = k-half * 32 + row, 16-B slot (2 * k-slice + k-half) of the row's 128-B chunk -- whose row co holds, at the slab-local input
 // channels of its own group, w[co][0 .. cg); zeros elsewhere (the block-diagonal 64 x 64 image) and in the rows past C.
 // x3: three bf16 chunks [W_hi | W_lo | W_hi] per slab, met in the kernel by the input lines [hi | hi | lo].
+// dgrad: the weights of the DATA-GRADIENT conv straight from the forward master: row ci (an input channel of the forward conv) holds,
+// at the slab-local channels co of its own group, w[co][ci % cg][ntap - 1 - tap] * scale[co] -- the forward filter flipped over the
+// taps, transposed inside each group, the fused AffineChannelNd scale folded in (grouped counterpart of conv_pack.hip's dgrad mode).
 template <int DT>
-__global__ void grouped_pack_kernel(const float* __restrict__ w, void* __restrict__ out, int C, int cg, int ntap, int Cout_pad, int nck, int x3) {
+__global__ void grouped_pack_kernel(const float* __restrict__ w, void* __restrict__ out, int C, int cg, int ntap, int Cout_pad, int nck, int x3,
+                                    int dgrad, const float* __restrict__ scale) {
     constexpr int CK = Mma<DT>::CK, EPS = 16 / ElemOf<DT>::size;
     const size_t total = (size_t)ntap * nck * Cout_pad * CK;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -257,7 +264,14 @@ __global__ void grouped_pack_kernel(const float* __restrict__ w, void* __restric
         float v = 0.f;
         if (co < C) {
             const int cil = j - ((co & 63) / cg) * cg;    // ... inside the row's group
-            if (cil >= 0 && cil < cg) v = w[((size_t)co * cg + cil) * ntap + tap];
+            if (cil >= 0 && cil < cg) {
+                if (dgrad) {
+                    const int cof = (co / cg) * cg + cil;     // forward output channel: this row's group, slab-local column
+                    v = w[((size_t)cof * cg + co % cg) * ntap + (ntap - 1 - tap)] * (scale ? scale[cof] : 1.f);
+                } else {
+                    v = w[((size_t)co * cg + cil) * ntap + tap];
+                }
+            }
         }
         if (x3) {
             const float hi = bf2f(f2bf(v));
@@ -270,10 +284,162 @@ __global__ void grouped_pack_kernel(const float* __restrict__ w, void* __restric
     }
 }
 
+// ---- weight gradient: dW[co][cil][kt][kh][kw] = sum_p g[p][co] * x[p (+) tap][(co / cg) * cg + cil] ------------------------------------------
+// Per 64-channel slab a 64 x 64 x taps GEMM over the positions of which only the 64 / cg diagonal cg x cg blocks are kept.  The slab rule
+// of the forward kernel holds here too: a block (slab, kt, range of position chunks) stages ONLY the slab's lines of g and x -- one
+// 128-byte line per pixel in 16-bit, the 256 contiguous bytes of two 32-channel lines in fp32 -- by LDS-DMA, positions as LDS rows:
+//   * a chunk = one 8 x 8 patch of output positions of one frame: 64 g rows, and the (7 s + 3)^2 input positions around it (s = 1: 10 x 10,
+//     s = 2: 17 x 17) ONCE for all nine spatial taps; tap (kh, kw) of output (oy, ox) is patch row (s oy + kh) * PW + s ox + kw;
+//   * 16-bit: the fragments are transposing reads (ds_read_b64_tr_b16; every lane supplies its own row address, so the stride-2 rows two
+//     apart need no second layout) of rows swizzled as in wgrad_dma9_kernel -- 16-byte piece q of row r sits in slot q ^ 4 * bit1(r),
+//     applied on the source side of the DMA: four consecutive rows x 64 B cover all 64 banks (stride 2: rows two apart, two-way);
+//   * fp32 (the parity mode): plain ds_read_b32 operands of v_mfma_f32_32x32x2_f32, two positions per instruction;
+//   * wave w of the four: cg = 64 -> quadrant (w & 1, w >> 1) of the slab over all 64 positions; cg <= 32 -> only the two DIAGONAL 32 x 32
+//     quadrants hold kept blocks: quadrant w & 1 over positions [32 (w >> 1), + 32) of the chunk.  Nine accumulators (144 registers);
+//   * the partial sums are ADDED to Gt[tap][C][cg] with float atomics, kept elements only -- products outside the diagonal blocks have no
+//     address in that layout.
+// Temporal taps outside the clip are skipped per chunk.  Every loop is bounded by launch arguments.
+struct GWgradParams {
+    const char* g;
+    const char* x;
+    float* G;                 // [KT * 9][C][cg] fp32
+    const char* zeros;
+    int C, cg_log2, g_cs;
+    int T, H, W, Ho, Wo;
+    int KT, pt;
+    int nslab, ksplit, frames;
+    int tiles_h, tiles_w;     // 8 x 8 output patches per frame
+};
+
+typedef short gw_v4s __attribute__((ext_vector_type(4)));
+
+template <int DT, int S>
+__global__ __launch_bounds__(NTHREADS, 2) void wgrad_grouped_kernel(const GWgradParams p) {
+    constexpr int ES = ElemOf<DT>::size;
+    constexpr int ROWB = 64 * ES;                 // one slab of one pixel: 128 B (16-bit) | 256 B (fp32)
+    constexpr int SPR = ROWB / 16;                // 16-byte DMA slots per row
+    constexpr int PW = 7 * S + 3;                 // input patch edge
+    constexpr int PR = PW * PW;
+    constexpr int RPP = 1024 / ROWB;              // rows per 1-KiB DMA piece
+    constexpr int NROWS = (64 + PR + RPP - 1) / RPP * RPP;
+    constexpr int NPIECES = NROWS / RPP;
+    extern __shared__ __attribute__((aligned(1024))) char smem[];
+    typedef const __attribute__((address_space(1))) void* gptr_t;
+    typedef __attribute__((address_space(3))) void* lptr_t;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    unsigned bid = blockIdx.x;
+    const int kt = bid % p.KT; bid /= p.KT;
+    const int slab = bid % p.nslab;
+    const int split = bid / p.nslab;
+    const bool full = p.cg_log2 == 6;
+    const int qm = wave & 1, qn = full ? wave >> 1 : qm;
+    const int ks0 = full ? 0 : 2 * (wave >> 1), ks1 = full ? 4 : ks0 + 2;     // 16-position slices of the chunk
+    const unsigned per_frame = (unsigned)(p.tiles_h * p.tiles_w);
+    const unsigned nchunks = (unsigned)p.frames * per_frame;
+    const unsigned c_lo = (unsigned)((unsigned long long)nchunks * split / p.ksplit);
+    const unsigned c_hi = (unsigned)((unsigned long long)nchunks * (split + 1) / p.ksplit);
+    const int khalf = lane >> 5, l31 = lane & 31;
+
+    f32x16_t acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+
+    // 16-bit fragment addressing: lane 4 q + c of a 16-lane group supplies row q, columns 4 c .. 4 c + 3 of a 4-row x 16-channel block and
+    // receives channel (lane & 15) of the four rows.  Groups 0 / 1 = channels 0-15 / 16-31 of the quadrant, groups 2 / 3 the same of the
+    // next eight positions (the k-half of the MFMA); the second read, four positions on, completes the lane's eight k.
+    const int li = lane & 15, frow = li >> 2;
+    const int fcol = ((((lane >> 4) & 1) * 16 + (li & 3) * 4) * 2);            // byte column inside the quadrant's 64 B
+    char* const xs = smem + 64 * ROWB;
+    typedef __attribute__((address_space(3))) gw_v4s* lp_t;
+    auto tr4 = [&](const char* a) __attribute__((always_inline)) { return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)a)); };
+    auto frag16 = [&](const char* base, int row, int rstep, int colb) __attribute__((always_inline)) {
+        const int r1 = row + 4 * rstep;
+        const uint2 lo = tr4(base + row * ROWB + (colb ^ ((row & 2) << 5)));
+        const uint2 hi = tr4(base + r1 * ROWB + (colb ^ ((r1 & 2) << 5)));
+        return make_uint4(lo.x, lo.y, hi.x, hi.y);
+    };
+
+    bool any = false;
+    for (unsigned ch = c_lo; ch < c_hi; ++ch) {
+        const unsigned fr = ch / per_frame, tl = ch - fr * per_frame;
+        const int f = (int)fr;
+        const int clip = f / p.T, t = f - clip * p.T, ti = t + kt - p.pt;
+        if (ti < 0 || ti >= p.T) continue;                 // (block-uniform) the tap reads a frame outside the clip: zeros
+        const int ty = (int)(tl / (unsigned)p.tiles_w), tx = (int)tl - ty * p.tiles_w;
+        const int oy0 = ty * 8, ox0 = tx * 8;
+        const int iy0 = oy0 * S - 1, ix0 = ox0 * S - 1;
+        const char* const gfr = p.g + (size_t)f * p.Ho * p.Wo * p.g_cs * ES + (size_t)slab * ROWB;
+        const char* const xfr = p.x + (size_t)(clip * p.T + ti) * p.H * p.W * p.C * ES + (size_t)slab * ROWB;
+        any = true;
+        __syncthreads();                                   // every wave is done with the previous chunk's rows
+        for (int c = wave; c < NPIECES; c += 4) {
+            const int it = c * 64 + lane;
+            const int row = it / SPR;
+            int slot = it % SPR;
+            if (ES == 2) slot ^= ((row >> 1) & 1) << 2;    // the bank swizzle of the transposing reads, on the source side
+            const char* src = p.zeros;
+            if (row < 64) {
+                const int y = oy0 + (row >> 3), xq = ox0 + (row & 7);
+                if (y < p.Ho && xq < p.Wo) src = gfr + ((size_t)y * p.Wo + xq) * p.g_cs * ES + slot * 16;
+            } else if (row < 64 + PR) {
+                const int xr = row - 64, py = xr / PW, px = xr - py * PW;
+                const int y = iy0 + py, xq = ix0 + px;
+                if (y >= 0 && y < p.H && xq >= 0 && xq < p.W) src = xfr + ((size_t)y * p.W + xq) * p.C * ES + slot * 16;
+            }
+            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + c * 1024), 16, 0, 0);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        for (int ks = ks0; ks < ks1; ++ks) {
+            if (ES == 2) {
+                const int oy = 2 * ks + khalf;             // the eight k of this lane: output row oy, columns 0 .. 7
+                const uint4 a = frag16(smem, oy * 8 + frow, 1, qm * 64 + fcol);
+#pragma unroll
+                for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+                    for (int kw = 0; kw < 3; ++kw) {
+                        const uint4 b = frag16(xs, (S * oy + kh) * PW + S * frow + kw, S, qn * 64 + fcol);
+                        Mma<DT>::step(a, b, acc[kh * 3 + kw]);
+                    }
+            } else {
+#pragma unroll 2
+                for (int j = 0; j < 8; ++j) {
+                    const int pos = ks * 16 + 2 * j + khalf, oy = pos >> 3, ox = pos & 7;
+                    const float a = *(const float*)(smem + pos * ROWB + (qm * 32 + l31) * 4);
+#pragma unroll
+                    for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+                        for (int kw = 0; kw < 3; ++kw) {
+                            const float b = *(const float*)(xs + ((S * oy + kh) * PW + S * ox + kw) * ROWB + (qn * 32 + l31) * 4);
+                            acc[kh * 3 + kw] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[kh * 3 + kw], 0, 0, 0);
+                        }
+                }
+            }
+        }
+    }
+    if (!any) return;                                      // (an empty range, or every chunk outside the clip: nothing to add)
+    // ---- kept elements only: row co of the quadrant against column ci of the SAME group ----
+    const int cis = qn * 32 + l31;                         // slab-local input channel of this lane
+    const int cg = 1 << p.cg_log2;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        float* const Gt = p.G + ((size_t)(kt * 9 + t) * p.C + (size_t)slab * 64) * cg;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int cos = qm * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+            if ((cos >> p.cg_log2) == (cis >> p.cg_log2)) atomicAdd(Gt + (size_t)cos * cg + (cis & (cg - 1)), acc[t][r]);
+        }
+    }
+}
+
 inline int slab_chunks(int dtype) { return dtype == DAT_BF16X3 ? 3 : dtype == DAT_F32 ? 2 : 1; }
 
 // what every grouped entry point accepts (anything else is DAT_ERR_UNSUPPORTED: there is no dense fall-back)
-int grouped_check(dat_ctx* ctx, const dat_conv_desc* d, int groups, const char* who) {
+// max_res_mode: the highest residual mode the entry point has (forward: 3 = mask, for DAT_F32 / DAT_BF16; every other one: 0 or 1)
+int grouped_check(dat_ctx* ctx, const dat_conv_desc* d, int groups, const char* who, int max_res_mode = 1) {
     DAT_ENFORCE(ctx, d, "%s: null descriptor", who);
     DAT_GRP_UNSUPPORTED(ctx, d->dtype == DAT_F32 || d->dtype == DAT_BF16 || d->dtype == DAT_BF16X3, "%s: bad dtype %d", who, d->dtype);
     DAT_GRP_UNSUPPORTED(ctx, d->dtype != DAT_BF16X3 || DAT_H16_FORMAT == 0,
@@ -288,7 +454,9 @@ int grouped_check(dat_ctx* ctx, const dat_conv_desc* d, int groups, const char* 
                         d->pad_t, d->pad_h, d->pad_w);
     DAT_GRP_UNSUPPORTED(ctx, d->stride_h == d->stride_w && (d->stride_h == 1 || d->stride_h == 2), "%s: stride %dx%d (supported: 1, 2)", who,
                         d->stride_h, d->stride_w);
-    DAT_GRP_UNSUPPORTED(ctx, d->res_mode == 0 || d->res_mode == 1, "%s: res_mode %d (supported: 0, 1)", who, d->res_mode);
+    DAT_GRP_UNSUPPORTED(ctx, d->res_mode == 0 || d->res_mode == 1 || (d->res_mode == 3 && max_res_mode >= 3 && d->dtype != DAT_BF16X3),
+                        "%s: res_mode %d (supported: 0, 1%s)", who, d->res_mode,
+                        max_res_mode >= 3 ? "; 3 = mask for DAT_F32 / DAT_BF16; 4 = sum + mask has no grouped instantiation" : "");
     return DAT_OK;
 }
 
@@ -314,18 +482,117 @@ int dat_conv3d_grouped_pack_weights(dat_ctx* ctx, dat_stream s, const dat_conv_d
     const size_t total = (size_t)ntap * nck * cp * (d->dtype == DAT_F32 ? 32 : 64);
     const int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
     if (d->dtype == DAT_F32)
-        hipLaunchKernelGGL(grouped_pack_kernel<DAT_F32>, dim3(blocks), dim3(256), 0, (hipStream_t)s, w, packed, d->Cout, cg, ntap, cp, nck, 0);
+        hipLaunchKernelGGL(grouped_pack_kernel<DAT_F32>, dim3(blocks), dim3(256), 0, (hipStream_t)s, w, packed, d->Cout, cg, ntap, cp, nck, 0, 0,
+                           (const float*)nullptr);
     else
         hipLaunchKernelGGL(grouped_pack_kernel<DAT_BF16>, dim3(blocks), dim3(256), 0, (hipStream_t)s, w, packed, d->Cout, cg, ntap, cp, nck,
-                           d->dtype == DAT_BF16X3 ? 1 : 0);
+                           d->dtype == DAT_BF16X3 ? 1 : 0, 0, (const float*)nullptr);
     DAT_CHECK_LAUNCH(ctx, "grouped_pack");
     return DAT_OK;
+}
+
+int dat_conv3d_grouped_pack_weights_dgrad(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, int groups, const float* w_fwd,
+                                          const float* scale_fwd, void* packed) {
+    DAT_ENFORCE(ctx, d && w_fwd && packed, "conv3d_grouped_pack_weights_dgrad: null argument");
+    const int rc = grouped_check(ctx, d, groups, "conv3d_grouped_pack_weights_dgrad", 3);
+    if (rc != DAT_OK) return rc;
+    DAT_GRP_UNSUPPORTED(ctx, d->dtype != DAT_BF16X3, "conv3d_grouped_pack_weights_dgrad: DAT_BF16X3 is an inference mode (no data-gradient pack)");
+    DAT_GRP_UNSUPPORTED(ctx, d->stride_h == 1, "conv3d_grouped_pack_weights_dgrad: the data-gradient conv has stride 1 (a stride-2 layer goes "
+                        "through dat_zero_insert2x first), got %d", d->stride_h);
+    const int ntap = d->KT * d->KH * d->KW, nck = slab_chunks(d->dtype), cp = cout_pad_of(d), cg = d->Cin / groups;
+    const size_t total = (size_t)ntap * nck * cp * (d->dtype == DAT_F32 ? 32 : 64);
+    const int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
+    if (d->dtype == DAT_F32)
+        hipLaunchKernelGGL(grouped_pack_kernel<DAT_F32>, dim3(blocks), dim3(256), 0, (hipStream_t)s, w_fwd, packed, d->Cout, cg, ntap, cp, nck, 0, 1,
+                           scale_fwd);
+    else
+        hipLaunchKernelGGL(grouped_pack_kernel<DAT_BF16>, dim3(blocks), dim3(256), 0, (hipStream_t)s, w_fwd, packed, d->Cout, cg, ntap, cp, nck, 0, 1,
+                           scale_fwd);
+    DAT_CHECK_LAUNCH(ctx, "grouped_pack_dgrad");
+    return DAT_OK;
+}
+
+// shared by the two weight-gradient entry points: checks + the accumulate launch
+static int grouped_wgrad_launch(dat_ctx* ctx, hipStream_t st, const dat_conv_desc* d, int groups, const void* x, const void* g, int g_cstride,
+                                float* Gt, const char* who) {
+    DAT_ENFORCE(ctx, d && x && g && Gt, "%s: null argument", who);
+    const int rc = grouped_check(ctx, d, groups, who, 0);
+    if (rc != DAT_OK) return rc;
+    DAT_GRP_UNSUPPORTED(ctx, d->dtype != DAT_BF16X3, "%s: DAT_BF16X3 is an inference mode (no weight gradient)", who);
+    DAT_GRP_UNSUPPORTED(ctx, d->res_mode == 0, "%s: res_mode %d (a weight gradient has no residual)", who, d->res_mode);
+    DAT_ENFORCE(ctx, d->T > 0 && d->frames > 0 && d->frames % d->T == 0, "%s: frames %d not a multiple of T %d", who, d->frames, d->T);
+    DAT_ENFORCE(ctx, g_cstride % 8 == 0 && g_cstride >= d->Cout, "%s: g_cstride %d must be a multiple of 8, >= Cout %d", who, g_cstride, d->Cout);
+    GWgradParams q;
+    memset(&q, 0, sizeof(q));
+    q.g = (const char*)g; q.x = (const char*)x; q.G = Gt; q.zeros = (const char*)ctx->zeros;
+    q.C = d->Cin; q.g_cs = g_cstride;
+    const int cg = d->Cin / groups;
+    while ((1 << q.cg_log2) < cg) ++q.cg_log2;
+    q.T = d->T; q.H = d->H; q.W = d->W;
+    dat_conv3d_out_shape(d, &q.Ho, &q.Wo);
+    DAT_ENFORCE(ctx, q.Ho > 0 && q.Wo > 0, "%s: empty output %dx%d", who, q.Ho, q.Wo);
+    q.KT = d->KT; q.pt = d->pad_t;
+    q.nslab = d->Cin / G_BN; q.frames = d->frames;
+    q.tiles_h = (q.Ho + 7) / 8; q.tiles_w = (q.Wo + 7) / 8;
+    // (d->out_t0 / out_tn: g is zero outside that window by contract -- its chunks add zeros; the whole clip is reduced)
+    const long long nchunks = (long long)d->frames * q.tiles_h * q.tiles_w;
+    const long long tiles = (long long)q.nslab * d->KT;
+    DAT_ENFORCE(ctx, nchunks < (1ll << 31), "%s: %lld position chunks unsupported", who, nchunks);
+    // K split: about two blocks per CU, at least four chunks per block (every block ends in 9 x 64 x cg float atomics)
+    long long ks = (2ll * ctx_num_cu(ctx) + tiles - 1) / tiles;
+    if (ks > nchunks / 4) ks = nchunks / 4;
+    if (ks < 1) ks = 1;
+    q.ksplit = (int)ks;
+    const int s2 = d->stride_h == 2, f32 = d->dtype == DAT_F32;
+    const int pw = 7 * d->stride_h + 3, rowb = f32 ? 256 : 128, rpp = 1024 / rowb;
+    const int lds = (64 + pw * pw + rpp - 1) / rpp * rpp * rowb;
+    const unsigned nblocks = (unsigned)(tiles * ks);
+    ProfBracket prof(ctx, st);
+#define DAT_GW_LAUNCH(DT_, S_)                                                              \
+    do {                                                                                    \
+        auto kern = wgrad_grouped_kernel<DT_, S_>;                                          \
+        const int rcl = dat_ensure_lds(ctx, (const void*)kern, 160 * 1024);                 \
+        if (rcl != DAT_OK) return rcl;                                                      \
+        hipLaunchKernelGGL(kern, dim3(nblocks), dim3(NTHREADS), lds, st, q);                \
+    } while (0)
+    if (f32 && s2) DAT_GW_LAUNCH(DAT_F32, 2);
+    else if (f32) DAT_GW_LAUNCH(DAT_F32, 1);
+    else if (s2) DAT_GW_LAUNCH(DAT_BF16, 2);
+    else DAT_GW_LAUNCH(DAT_BF16, 1);
+#undef DAT_GW_LAUNCH
+    DAT_CHECK_LAUNCH(ctx, "wgrad_grouped");
+    prof.end(2.0 * d->Cout * cg * d->KT * 9 * (double)d->frames * q.Ho * q.Wo, 64 * 10000 + 2580 + d->dtype);   // ("258": the grouped weight gradient)
+    return DAT_OK;
+}
+
+size_t dat_conv3d_grouped_wgrad_workspace_bytes(const dat_conv_desc* d, int groups) {
+    if (!d || groups < 1 || d->Cout < 1) return 0;
+    return (size_t)d->KT * d->KH * d->KW * d->Cout * (d->Cin / groups) * sizeof(float);
+}
+
+int dat_conv3d_grouped_wgrad_acc(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, int groups, const void* x, const void* g, int g_cstride,
+                                 float* Gt) {
+    return grouped_wgrad_launch(ctx, (hipStream_t)s, d, groups, x, g, g_cstride, Gt, "conv3d_grouped_wgrad_acc");
+}
+
+int dat_conv3d_grouped_wgrad(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, int groups, const void* x, const void* g, int g_cstride,
+                             const float* scale, void* workspace, float* dW) {
+    DAT_ENFORCE(ctx, d && workspace && dW, "conv3d_grouped_wgrad: null argument");
+    const int rc0 = grouped_check(ctx, d, groups, "conv3d_grouped_wgrad", 0);     // (before the memset: nothing is launched for an unsupported call)
+    if (rc0 != DAT_OK) return rc0;
+    DAT_GRP_UNSUPPORTED(ctx, d->dtype != DAT_BF16X3, "conv3d_grouped_wgrad: DAT_BF16X3 is an inference mode (no weight gradient)");
+    hipStream_t st = (hipStream_t)s;
+    if (hipMemsetAsync(workspace, 0, dat_conv3d_grouped_wgrad_workspace_bytes(d, groups), st) != hipSuccess)
+        DAT_FAIL(ctx, DAT_ERR_LAUNCH, "conv3d_grouped_wgrad: memset failed");
+    const int rc = grouped_wgrad_launch(ctx, st, d, groups, x, g, g_cstride, (float*)workspace, "conv3d_grouped_wgrad");
+    if (rc != DAT_OK) return rc;
+    return launch_wgrad_finish(ctx, st, (const float*)workspace, scale, dW, d->Cout, d->Cin / groups, d->KT * 9);
 }
 
 int dat_conv3d_grouped_fwd(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, int groups, const void* x, const void* w_packed,
                            const float* scale, const float* bias, const void* residual, void* y, void* y_split) {
     DAT_ENFORCE(ctx, d && x && w_packed && y, "conv3d_grouped_fwd: null argument");
-    const int rc0 = grouped_check(ctx, d, groups, "conv3d_grouped_fwd");
+    const int rc0 = grouped_check(ctx, d, groups, "conv3d_grouped_fwd", 3);
     if (rc0 != DAT_OK) return rc0;
     const bool x3 = d->dtype == DAT_BF16X3;
     DAT_ENFORCE(ctx, d->T > 0 && d->frames > 0 && d->frames % d->T == 0, "conv3d_grouped_fwd: frames %d not a multiple of T %d", d->frames, d->T);
@@ -375,16 +642,18 @@ int dat_conv3d_grouped_fwd(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, i
     DAT_ENFORCE(ctx, lds <= 160 * 1024, "conv3d_grouped_fwd: LDS patch of %zu bytes exceeds 160 KiB (tile %dx%d)", lds, th, tw);
     hipStream_t st = (hipStream_t)s;
     ProfBracket prof(ctx, st);
-#define DAT_GRP_LAUNCH(DT_, ODT_)                                                                      \
+#define DAT_GRP_LAUNCH(DT_, ODT_, MASK_)                                                               \
     do {                                                                                               \
-        auto kern = conv3d_grouped_kernel<DT_, ODT_>;                                                  \
+        auto kern = conv3d_grouped_kernel<DT_, ODT_, MASK_>;                                           \
         const int rc = dat_ensure_lds(ctx, (const void*)kern, 160 * 1024);                              \
         if (rc != DAT_OK) return rc;                                                                   \
         hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(NTHREADS), lds, st, p);                         \
     } while (0)
-    if (x3) DAT_GRP_LAUNCH(DAT_BF16, DAT_F32);
-    else if (d->dtype == DAT_BF16) DAT_GRP_LAUNCH(DAT_BF16, DAT_BF16);
-    else DAT_GRP_LAUNCH(DAT_F32, DAT_F32);
+    if (x3) DAT_GRP_LAUNCH(DAT_BF16, DAT_F32, false);
+    else if (d->res_mode == 3 && d->dtype == DAT_BF16) DAT_GRP_LAUNCH(DAT_BF16, DAT_BF16, true);
+    else if (d->res_mode == 3) DAT_GRP_LAUNCH(DAT_F32, DAT_F32, true);
+    else if (d->dtype == DAT_BF16) DAT_GRP_LAUNCH(DAT_BF16, DAT_BF16, false);
+    else DAT_GRP_LAUNCH(DAT_F32, DAT_F32, false);
 #undef DAT_GRP_LAUNCH
     DAT_CHECK_LAUNCH(ctx, "conv3d_grouped");
     prof.end(2.0 * d->Cout * (d->Cin / groups) * d->KT * 9 * (double)p.frames * p.Ho * p.Wo, 64 * 10000 + 2570 + d->dtype);   // ("257 positions": the grouped kernel)

@@ -171,6 +171,9 @@ bool bt_eligible(const dat_ctx* ctx, const dat_conv_desc* d);
 int bt_tile_twl(const ConvParams& p, long long* nblocks);
 int launch_bt(dat_ctx* ctx, hipStream_t st, ConvParams& p);
 
+// train_ops.hip: dW[co][ci][tap] = scale[co] * Gt[tap][co][ci] (wgrad_finish_kernel; scale NULL = 1)
+int launch_wgrad_finish(dat_ctx* ctx, hipStream_t st, const float* Gt, const float* scale, float* dW, int Cout, int Cin, int ntaps);
+
 }  // namespace dat_conv
 
 #endif

@@ -14,12 +14,10 @@
 // of input channels, 128-byte K slices, XOR-swizzled LDS tiles, v_mfma_f32_32x32x16_bf16 / 32x32x2_f32).  bf16 rows
 // need 4-byte alignment, so a second copy of every plane shifted by one element serves the odd offsets (Wq is even).
 // Split-K over q across blocks; fp32 partial tiles are accumulated into G with atomics (G is tiny: Cout*Cin*taps).
-#include "dat_common.h"
+#include "conv_internal.h"      // dat_conv::ctx_num_cu (conv_special.hip), dat_conv::launch_wgrad_finish (defined below)
 
 #include <utility>
 #include <vector>
-
-namespace dat_conv { int ctx_num_cu(dat_ctx* ctx); }      // conv_special.hip: compute units of the device
 
 namespace {
 
@@ -1209,6 +1207,14 @@ static inline int grid_for(long long n, int block) {
 }
 
 }  // namespace
+
+// the finish pass for the grouped weight gradient of conv_grouped.hip (declared in conv_internal.h, hidden like the rest of dat_conv)
+int dat_conv::launch_wgrad_finish(dat_ctx* ctx, hipStream_t st, const float* Gt, const float* scale, float* dW, int Cout, int Cin, int ntaps) {
+    const long long n = (long long)Cout * Cin * ntaps;
+    hipLaunchKernelGGL(wgrad_finish_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, Gt, scale, dW, Cout, Cin, ntaps);
+    DAT_CHECK_LAUNCH(ctx, "wgrad_finish");
+    return DAT_OK;
+}
 
 extern "C" {
 

@@ -115,6 +115,10 @@ _PROTOS = {
     'dat_conv3d_grouped_pack_weights': (_i, [_p, _p, C.POINTER(ConvDesc), _i, _p, _p]),
     'dat_conv3d_grouped_fwd': (_i, [_p, _p, C.POINTER(ConvDesc), _i, _p, _p, _p, _p, _p, _p, _p]),
     'dat_conv3d_grouped_flops': (_d, [C.POINTER(ConvDesc), _i]),
+    'dat_conv3d_grouped_pack_weights_dgrad': (_i, [_p, _p, C.POINTER(ConvDesc), _i, _p, _p, _p]),
+    'dat_conv3d_grouped_wgrad_workspace_bytes': (C.c_size_t, [C.POINTER(ConvDesc), _i]),
+    'dat_conv3d_grouped_wgrad_acc': (_i, [_p, _p, C.POINTER(ConvDesc), _i, _p, _p, _i, _p]),
+    'dat_conv3d_grouped_wgrad': (_i, [_p, _p, C.POINTER(ConvDesc), _i, _p, _p, _i, _p, _p, _p]),
     'dat_stem_pack': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i]),
     'dat_stem_weights': (_i, [_p, _p, _p, _i, _p]),
     'dat_split_bf16x2': (_i, [_p, _p, _p, _p, _ll, _i]),

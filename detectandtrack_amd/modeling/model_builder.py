@@ -45,9 +45,10 @@ def init_model(model_name, train, init_params=None):
 
 def create(model_name, train=False, init_params=None):
     """:52-61."""
-    if train and cfg.RESNETS.NUM_GROUPS > 1:
+    if train and cfg.RESNETS.NUM_GROUPS > 1 and not cfg.HIP.get('TRAIN_GROUPED_CONV', False):
         raise NotImplementedError('training a grouped (ResNeXt, RESNETS.NUM_GROUPS = %d) body needs the grouped data-gradient and '
-                                  'weight-gradient kernels, which do not exist: the grouped conv is forward only' % cfg.RESNETS.NUM_GROUPS)
+                                  'weight-gradient kernels, which are opt-in until they have been measured at full size: set '
+                                  'cfg.HIP.TRAIN_GROUPED_CONV = True' % cfg.RESNETS.NUM_GROUPS)
     return get_func(model_name)(init_model(model_name, train, init_params))
 
 

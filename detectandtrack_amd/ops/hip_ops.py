@@ -169,14 +169,15 @@ class ConvLayer(object):
         """dgrad_of = (w_fwd, scale_fwd): this layer is the DATA-GRADIENT conv of a forward conv with master weights w_fwd
         [CoutF, CinF, KT, KH, KW]; `w` is then ignored and the packed weights come straight from w_fwd (channels swapped, kernel
         flipped, AffineChannelNd scale folded in: dat_conv3d_pack_weights_dgrad).
-        groups > 1: a grouped conv (ResNeXt `branch2b`) on the dat_conv3d_grouped_* entry points -- forward only, and only the shapes
-        that kernel has (anything else raises its DAT_ERR_UNSUPPORTED text: there is no dense fall-back)."""
+        groups > 1: a grouped conv (ResNeXt `branch2b`) on the dat_conv3d_grouped_* entry points, only the shapes that kernel has
+        (anything else raises its DAT_ERR_UNSUPPORTED text: there is no dense fall-back).  With dgrad_of its data gradient -- again a
+        grouped conv, packed by dat_conv3d_grouped_pack_weights_dgrad from w_fwd [C, C / groups, KT, KH, KW]."""
         self.groups = int(groups)
-        assert self.groups >= 1 and (self.groups == 1 or dgrad_of is None), 'grouped convs have no data-gradient kernel'
+        assert self.groups >= 1
         if dgrad_of is not None:
             w_fwd = dgrad_of[0].contiguous().float()
             self.w_src, self.dgrad_scale = w_fwd, (None if dgrad_of[1] is None else dgrad_of[1].contiguous().float())
-            coutf, cinf = int(w_fwd.shape[0]), int(w_fwd.shape[1])
+            coutf, cinf = int(w_fwd.shape[0]), int(w_fwd.shape[1]) * self.groups
             self.cout_real, self.cin_real = cinf, coutf
             self.kt, self.kh, self.kw = [int(v) for v in w_fwd.shape[2:]]
             w = w_fwd
@@ -237,7 +238,10 @@ class ConvLayer(object):
     def repack(self, weights_only=False):
         """(Re-)derive the packed weights (and a padded bias copy) from the fp32 masters -- after an SGD update in place."""
         d = self.desc(1, 1, 8, 8)
-        if self.groups > 1:
+        if self.groups > 1 and self.is_dgrad:
+            ctx().call('dat_conv3d_grouped_pack_weights_dgrad', _stream(), C.byref(d), self.groups, _ptr(self.w_src),
+                       _ptr(self.dgrad_scale), _ptr(self.packed))
+        elif self.groups > 1:
             ctx().call('dat_conv3d_grouped_pack_weights', _stream(), C.byref(d), self.groups, _ptr(self.w_src), _ptr(self.packed))
         elif self.x3:
             d.dtype, d.Cin = BF16, 3 * self.cin
@@ -311,7 +315,7 @@ class ConvLayer(object):
             alloc = torch.zeros if (self.cstride != self.cout and zero_pad) else torch.empty
             out = alloc((oframes, ho, wo, self.cstride), dtype=x.dtype, device=x.device)
         if self.groups > 1:
-            assert res_mode in (0, 1) and addend is None
+            # (res_mode 3 = mask: the data-gradient layer; 4 = sum + mask has no grouped instantiation: the library refuses it)
             xin, ysplit = x, None
             if self.x3:
                 xin = x_split if x_split is not None else split_bf16x2(x)
@@ -362,9 +366,13 @@ class ConvGrad(object):
       weight(x, g) -> G = dL/d(z) / scale-free weight gradient;  dL/dw = scale*G,  dL/dscale[c] = <w[c], G[c]>.
     """
 
-    def __init__(self, w, scale, stride, pads, dtype, x_cstride, g_cstride):
+    def __init__(self, w, scale, stride, pads, dtype, x_cstride, g_cstride, groups=1):
+        """groups > 1: a grouped conv (`w` fp32 [C, C / groups, KT, KH, KW]) on dat_conv3d_grouped_wgrad* and the grouped data-gradient
+        layer; `cin` is the full C."""
         self.w = w.contiguous().float()
         self.cout, self.cin, self.kt, self.kh, self.kw = [int(v) for v in self.w.shape]
+        self.groups = int(groups)
+        self.cin *= self.groups
         self.scale = None if scale is None else scale.float()
         self.stride, self.pads, self.dtype = tuple(stride), tuple(pads), dtype
         self.x_cstride, self.g_cstride = x_cstride, g_cstride
@@ -390,13 +398,21 @@ class ConvGrad(object):
         d = self._fwd_desc(frames, T, H, W)
         if g_frames is not None and frames == T:      # g is zero outside frames [t0, t0 + n) of the (single) clip
             d.out_t0, d.out_tn = int(g_frames[0]), int(g_frames[1])
-        nbytes = L.lib().dat_conv3d_wgrad_workspace_bytes(C.byref(d), self.cin, self.cout)
+        if self.groups > 1:
+            nbytes = L.lib().dat_conv3d_grouped_wgrad_workspace_bytes(C.byref(d), self.groups)
+        else:
+            nbytes = L.lib().dat_conv3d_wgrad_workspace_bytes(C.byref(d), self.cin, self.cout)
         wsb = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         if out is not None:
             assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == self.w.numel()
         dW = out if out is not None else torch.empty(self.w.shape, dtype=torch.float32, device=x.device)
-        ctx().call('dat_conv3d_wgrad', _stream(), C.byref(d), _ptr(x), _ptr(g), self.g_cstride, self.cin, self.cout,
-                   _ptr(self.scale), _ptr(wsb), _ptr(dW))
+        if self.groups > 1:
+            assert x.is_contiguous() and g.is_contiguous()
+            ctx().call('dat_conv3d_grouped_wgrad', _stream(), C.byref(d), self.groups, _ptr(x), _ptr(g), self.g_cstride,
+                       _ptr(self.scale), _ptr(wsb), _ptr(dW))
+        else:
+            ctx().call('dat_conv3d_wgrad', _stream(), C.byref(d), _ptr(x), _ptr(g), self.g_cstride, self.cin, self.cout,
+                       _ptr(self.scale), _ptr(wsb), _ptr(dW))
         if self.scale is None or not want_dscale:
             return dW, None
         # dL/dscale[c] = <w[c], G[c]> with G = dW / scale (the reference's AffineChannelNd has no such gradient; test hook)
@@ -412,6 +428,11 @@ class ConvGrad(object):
         d = self._fwd_desc(frames, T, H, W)
         if g_frames is not None and frames == T:
             d.out_t0, d.out_tn = int(g_frames[0]), int(g_frames[1])
+        if self.groups > 1:       # Gt[tap][C][C / groups]: the elements outside the diagonal blocks do not exist
+            assert gt.dtype == torch.float32 and gt.is_contiguous() and gt.numel() == self.w.numel()
+            assert x.is_contiguous() and g.is_contiguous()
+            ctx().call('dat_conv3d_grouped_wgrad_acc', _stream(), C.byref(d), self.groups, _ptr(x), _ptr(g), self.g_cstride, _ptr(gt))
+            return True
         if not L.lib().dat_conv3d_wgrad_acc_supported(ctx().h, C.byref(d), self.g_cstride):
             return False
         assert gt.dtype == torch.float32 and gt.is_contiguous() and gt.numel() == self.w.numel()
@@ -421,6 +442,8 @@ class ConvGrad(object):
     def weight_acc_job(self, x, g, T, gt, g_frames=None):
         """The arguments of `weight_acc` as a job for `wgrad_acc_batch` (None when the layer does not take the direct kernels).  The job holds
         references to x / g / gt: they stay alive (and must stay unmodified) until the batch has been enqueued."""
+        if self.groups > 1:         # grouped layers are never queued into the pointwise batch
+            return None
         frames, H, W, _ = x.shape
         d = self._fwd_desc(frames, T, H, W)
         if g_frames is not None and frames == T:
@@ -433,7 +456,7 @@ class ConvGrad(object):
 
     @property
     def pointwise(self):
-        return self.kt == 1 and self.kh == 1 and self.kw == 1 and tuple(self.pads) == (0, 0, 0)
+        return self.groups == 1 and self.kt == 1 and self.kh == 1 and self.kw == 1 and tuple(self.pads) == (0, 0, 0)
 
     def data(self, g, T, H, W, accumulate_into=None, g_frames=None, mask=None, inplace=True):
         """g [frames,Ho,Wo,g_cstride] -> dL/dx [frames,H,W,round64(Cin)] (added to `accumulate_into` when given).  mask: the conv's
@@ -444,7 +467,7 @@ class ConvGrad(object):
             # flipped / transposed / scale-folded weights are packed straight from the forward master (no ATen flip, mul, copy)
             pads = (self.kt - 1 - self.pads[0], self.kh - 1 - self.pads[1], self.kw - 1 - self.pads[2])
             self._data_layer = ConvLayer(None, None, None, stride=(1, 1), pads=pads, relu=False, dtype=self.dtype,
-                                         cin_stride=self.g_cstride, dgrad_of=(self.w, self.scale))
+                                         cin_stride=self.g_cstride, dgrad_of=(self.w, self.scale), groups=self.groups)
         frames, Ho, Wo, cs = g.shape
         Hz, Wz = H - self.kh + 1 + 2 * self.pads[1], W - self.kw + 1 + 2 * self.pads[2]
         if self.stride[0] == 2 or (Hz, Wz) != (Ho, Wo):

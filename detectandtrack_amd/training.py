@@ -389,7 +389,7 @@ class TrainExecutor(Executor):
             w5 = self._master(a['w'])
             w5 = w5 if w5.dim() == 5 else w5.unsqueeze(2)
             scale = self._master(a['scale']) if a['scale'] else None
-            return ops.ConvGrad(w5, scale, a['strides'], a['pads'], y.dt, xin.t.shape[3], g.shape[3])
+            return ops.ConvGrad(w5, scale, a['strides'], a['pads'], y.dt, xin.t.shape[3], g.shape[3], groups=a.get('group', 1))
         cg = self._conv_grad(i, build)
         if self._trainable(a['w']):
             gfr = (lo - ilo, n) if xin.N == 1 else None
@@ -439,7 +439,8 @@ class TrainExecutor(Executor):
             # ... and when this conv is the LAST of the blob's readers to contribute (a residual block's output: read by the next block's
             # first conv and by its shortcut), the same epilogue applies the ReLU backward of the blob's producer to the finished sum
             # (dat_conv3d_fwd_sum_mask, round 6): that producer's elementwise mask pass (three passes over the block output) goes
-            if (into is not None and cfg.HIP.get('FUSE_RELU_BWD', True) and cfg.HIP.get('FUSE_RELU_SUM_BWD', True) and _SUM_FUSE_ENV and prod is not None and
+            # (grouped layers have no sum + mask instantiation; a `branch2b` input has one reader, so the case does not arise for them)
+            if (into is not None and cg.groups == 1 and cfg.HIP.get('FUSE_RELU_BWD', True) and cfg.HIP.get('FUSE_RELU_SUM_BWD', True) and _SUM_FUSE_ENV and prod is not None and
                     prod.type == 'Conv' and isinstance(prod.args, dict) and prod.args.get('relu') and
                     self._readers.get(op.inputs[0], 0) == 2 and self._ncontrib.get(op.inputs[0], 0) == 1 and
                     xin.keyframe is None and not xin.t2c and x_win.is_contiguous() and tuple(x_win.shape) == tuple(into.shape) and
@@ -1073,10 +1074,13 @@ class Trainer(object):
                 continue
             ptr = src.data_ptr()
             if ptr in self._train_ptrs:
-                if isinstance(layer, ops.ConvLayer):
-                    todo.append(layer)
-                elif layer._data_layer is not None:
-                    todo.append(layer._data_layer)
+                lay = layer if isinstance(layer, ops.ConvLayer) else layer._data_layer
+                if lay is None:
+                    continue
+                if lay.groups > 1:      # the grouped packed layout is not the batch's: one small launch per image (forward, data gradient)
+                    lay.repack(weights_only=True)
+                else:
+                    todo.append(lay)
             elif ptr not in all_ptrs:
                 del ws._layers[key]
         if todo:

@@ -162,7 +162,7 @@ double dat_conv3d_flops(const dat_conv_desc* d, int Cin_real, int Cout_real);
 /* The dense entry points above with `groups` next to the descriptor (dat_conv_desc itself is unchanged): d->Cin == d->Cout == C, a
  * multiple of 64, in `groups` groups of cg = C / groups channels; output channel co reads input channels [(co / cg) * cg, + cg).
  * Supported: cg in {4, 8, 16, 32, 64} (a group never straddles a 64-channel slab), kernels 1x3x3 and 3x3x3 with "same" padding,
- * spatial stride 1 or 2 (both axes), res_mode 0 | 1, dtypes DAT_F32 | DAT_BF16 | DAT_BF16X3.  Anything else returns
+ * spatial stride 1 or 2 (both axes), res_mode 0 | 1 (| 3 for DAT_F32 / DAT_BF16), dtypes DAT_F32 | DAT_BF16 | DAT_BF16X3.  Anything else returns
  * DAT_ERR_UNSUPPORTED with a dat_last_error() text: there is no dense fall-back.  The block of output channels [64 s, 64 s + 64) reads
  * only the input channels of slab s, against a packed 64 x 64 x taps weight image per slab that is block-diagonal inside it. */
 /* bytes of the packed weights: [KT*3*3][slab chunks: 1 bf16 | 2 fp32 | 3 bf16x3][Cout_pad][128 B] */
@@ -176,6 +176,26 @@ int dat_conv3d_grouped_fwd(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, i
                            const float* scale, const float* bias, const void* residual, void* y, void* y_split);
 /* algorithmic FLOPs of one launch: 2*Cout*(Cin/groups)*KT*KH*KW*frames*Ho*Wo */
 double dat_conv3d_grouped_flops(const dat_conv_desc* d, int groups);
+
+/* ---- grouped conv, backward (training of ResNeXt bodies; DAT_F32 | DAT_BF16, DAT_BF16X3 is DAT_ERR_UNSUPPORTED) ------------------ */
+/* Data gradient: with Cin == Cout and groups that never straddle a slab it is again a grouped stride-1 conv -- dat_conv3d_grouped_fwd
+ * over the gradient (a stride-2 layer: over its dat_zero_insert2x image) with the weights packed here.  d describes THAT conv (stride 1,
+ * pads K - 1 - pad); w_fwd: the forward master fp32 [C, C / groups, KT, 3, 3]; scale_fwd: the forward AffineChannelNd scale [C] or NULL.
+ * Packs W'[ci][co_local][ntap - 1 - tap] = w_fwd[co][ci_local][tap] * scale_fwd[co] in the grouped packed layout, in one pass.
+ * dat_conv3d_grouped_fwd takes res_mode 3 (y = residual > 0 ? v : 0, the fused ReLU backward of the conv's input blob) for such a
+ * layer; res_mode 4 stays DAT_ERR_UNSUPPORTED. */
+int dat_conv3d_grouped_pack_weights_dgrad(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, int groups, const float* w_fwd,
+                                          const float* scale_fwd, void* packed);
+/* Weight gradient.  d: the FORWARD descriptor (d->Cin = channel stride of x = C); x [frames, H, W, C], g [frames, Ho, Wo, g_cstride]
+ * (zero outside d->out_t0 / out_tn when that window is set).  dat_conv3d_grouped_wgrad_acc ADDS the unscaled gradient into the
+ * caller's zeroed fp32 accumulator Gt[tap][C][C / groups] (float atomics; elements outside the diagonal blocks do not exist);
+ * dat_wgrad_finish_batch finishes it with Cout = C, Cin = C / groups.  dat_conv3d_grouped_wgrad is the immediate form: it overwrites
+ * dW [C, C / groups, KT, 3, 3] with scale[co] * gradient (scale may be NULL); workspace: dat_conv3d_grouped_wgrad_workspace_bytes(). */
+size_t dat_conv3d_grouped_wgrad_workspace_bytes(const dat_conv_desc* d, int groups);
+int dat_conv3d_grouped_wgrad_acc(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, int groups, const void* x, const void* g, int g_cstride,
+                                 float* Gt);
+int dat_conv3d_grouped_wgrad(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, int groups, const void* x, const void* g, int g_cstride,
+                             const float* scale, void* workspace, float* dW);
 
 /* ---- stem: conv1 [1,7,7]/s[1,2,2] input packing (ResNet3D.py:258-262) ---------------------- */
 /* data NC(T)HW fp32 [N,3,T,H,W] -> packed [N*T, Ho+3, Wo, 64]:
