@@ -2,7 +2,7 @@
 
 The 16-bit format belongs to the loaded library, so the format-generic kernel tests run again in ONE child process started with
 DAT_H16=fp16: tests/test_gpu_kernels.py, tests/test_gpu_fp16_edges.py, tests/test_gpu_infer_kernels.py, tests/test_gpu_wgrad.py (the
-weight-gradient kernels) and the persistent-kernel test of tests/test_gpu_model.py.
+weight-gradient kernels), tests/test_gpu_temporal_windows.py (the conv frame windows) and the persistent-kernel test of tests/test_gpu_model.py.
 The parent reads the child's JUnit report: no failure or error, every skip is a bf16-only test, and one test per kernel family (plus
 the NMS and proposal goldens) is among the passed -- so that a collection mistake cannot pass for a green run.  The child is never
 retried."""
@@ -17,12 +17,14 @@ import pytest
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_FILES = ['tests/test_gpu_kernels.py', 'tests/test_gpu_fp16_edges.py', 'tests/test_gpu_infer_kernels.py', 'tests/test_gpu_wgrad.py',
+               'tests/test_gpu_temporal_windows.py',
                'tests/test_gpu_model.py::test_persistent_kernel_cu_share_does_not_change_results']
 
 K = 'tests.test_gpu_kernels::'
 E = 'tests.test_gpu_fp16_edges::'
 I = 'tests.test_gpu_infer_kernels::'
 G = 'tests.test_gpu_wgrad::'
+W = 'tests.test_gpu_temporal_windows::'
 MUST_PASS = [
     K + 'test_layout_roundtrip[1]',
     K + 'test_conv3d[3x3x3-bf16]',                                   # generic kernel + the split-K finish
@@ -73,6 +75,9 @@ MUST_PASS = [
     G + 'test_cq_pack_and_wgrad_gemm_kernel_bf16_under_direct_0[64to128_k333_s2_n1t4_9x11_win2+2]',
     G + 'test_wgrad_finish_batch_kernel_transposes_scales_and_accumulates[0]',
     G + 'test_results_on_maps_wider_than_one_column_are_bit_identical_to_the_recorded_ones',
+    W + 'test_short_clips[short_t1-outall-inall-affine_res_relu]',              # generic kernel, a split-K slice with an empty patch range
+    W + 'test_temporal_k311_windows[k311-outall-in1+2-affine_res_relu]',        # windowed kT x 1 x 1: the one-tap variant
+    W + 'test_big_tile_windows[big_tile-outall-in1+1-none]',                    # big-tile kernel, a frame without a valid tap
 ]
 
 
