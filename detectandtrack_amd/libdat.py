@@ -162,6 +162,11 @@ _PROTOS = {
     'dat_wgrad_finish_batch': (_i, [_p, _p, _p, _i, C.c_longlong]),
     'dat_conv3d_wgrad_acc_batch': (_i, [_p, _p, C.POINTER(WgradJob), _i]),
     'dat_relu_bias_bwd': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, C.c_longlong, _i, _i, _i]),
+    'dat_bn_workspace_bytes': (C.c_size_t, [_i, _ll, _i]),
+    'dat_bn_stats': (_i, [_p, _p, _i, _p, _ll, _i, _i, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, C.c_size_t]),
+    'dat_bn_apply': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _ll, _i, _i, _i]),
+    'dat_bn_bwd_reduce': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _ll, _ll, _ll, _i, _i, _i, _p, _p, _p, _p, C.c_size_t]),
+    'dat_bn_bwd_apply': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _ll, _ll, _ll, _i, _i]),
     'dat_zero_insert2x': (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i]),
     'dat_upsample2x_bwd': (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i]),
     'dat_sgd_momentum': (_i, [_p, _p, _p, _p, _p, C.c_longlong, _f, _f, _f, _i]),

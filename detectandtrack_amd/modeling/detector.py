@@ -73,10 +73,12 @@ class Net(object):
         # fold "conv + shortcut" / "lateral + upsampled top-down" into the conv epilogue
         for x, y in ((a, b), (b, a)):
             pa = self.producer(x)
-            if pa is not None and pa.type == 'Conv' and not pa.args['relu'] and pa.args['residual'] is None \
+            if pa is not None and pa.type in ('Conv', 'SpatialBN') and not pa.args['relu'] and pa.args['residual'] is None \
                     and not self.consumers(x, pa):
                 py = self.producer(y)
                 res, mode = y, 1
+                # (a SpatialBN producer takes a same-shape residual only: the FPN lateral convs carry a bias, never an affine / BN)
+                assert pa.type == 'Conv' or py is None or py.type != 'UpsampleNearest2x', 'SpatialBN + upsampled top-down Sum'
                 if py is not None and py.type == 'UpsampleNearest2x':
                     res, mode = py.inputs[0], 2
                     if not self.consumers(y, py):
@@ -119,6 +121,7 @@ class DetectionModelHelper(object):
         self.param_specs = {}
         self.weights = []
         self.biases = []
+        self.computed_params = []       # SpatialBN running statistics (`_rm`, `_riv`): saved and loaded, never trained
         self.do_not_update_params = []
         self.losses = []
         self.metrics = []
@@ -129,15 +132,16 @@ class DetectionModelHelper(object):
         if name not in self.param_specs:
             self.param_specs[name] = dict(shape=tuple(int(s) for s in shape), init=init)
             self.params.append(name)
-            (self.weights if kind == 'w' else self.biases).append(name)
+            {'w': self.weights, 'b': self.biases, 'c': self.computed_params}[kind].append(name)
         else:
             assert self.param_specs[name]['shape'] == tuple(int(s) for s in shape), name
         return name
 
     def TrainableParams(self, gpu_id=-1):
         """Params that receive gradients: everything except AffineChannel scale/bias (gradient op has no
-        dscale/dbias, affine_channel_nd_op.cc:29-37) and do_not_update params (detector.py:57-65)."""
-        frozen = set(self.do_not_update_params)
+        dscale/dbias, affine_channel_nd_op.cc:29-37), do_not_update params (detector.py:57-65) and the computed parameters of
+        SpatialBN (running mean / variance)."""
+        frozen = set(self.do_not_update_params) | set(self.computed_params)
         return [p for p in self.params if p not in frozen and not self.param_specs[p].get('affine')]
 
     # ---- convolutions --------------------------------------------------------------------------------
@@ -185,20 +189,47 @@ class DetectionModelHelper(object):
     def AffineChannelNd(self, blob_in, blob_out, dim_out, share_with=None, inplace=False):
         """detector.py:89-108.  Folded into the producing conv's epilogue when possible."""
         if cfg.MODEL.USE_BN:
-            raise NotImplementedError('SpatialBN path (MODEL.USE_BN) is not used by any shipped config')
+            return self.SpatialBNLayer(blob_in, blob_out, dim_out, share_with, inplace)
         blob_in = str(blob_in)
         prefix = str(blob_out) if share_with is None else share_with
         s = self._param(prefix + '_s', [dim_out], ('ConstantFill', {'value': 1.}), 'w')
         b = self._param(prefix + '_b', [dim_out], ('ConstantFill', {'value': 0.}), 'b')
         self.param_specs[s]['affine'] = self.param_specs[b]['affine'] = True
-        out = blob_in if inplace else str(blob_out)
+        return self._record_affine(blob_in, blob_in if inplace else str(blob_out), s, b)
+
+    def _record_affine(self, blob_in, out, s, b, **bn):
+        """y = x * s + b, folded into the producing conv's epilogue when possible.  bn: the running statistics of a test-mode
+        SpatialBN (rm, riv, eps) -- the executor then hands the layer s / sqrt(riv + eps) and b - rm * s / sqrt(riv + eps)."""
         prod = self.net.producer(blob_in)
         if prod is not None and prod.type == 'Conv' and prod.args['scale'] is None and prod.args['b'] is None \
                 and not prod.args['relu'] and not self.net.consumers(blob_in, prod):
             prod.args['scale'], prod.args['shift'] = s, b
+            prod.args.update(bn)
             prod.outputs = [out]
             return out
-        return self.net.add(Op('AffineChannel', [blob_in], [out], scale=s, shift=b))
+        return self.net.add(Op('AffineChannel', [blob_in], [out], scale=s, shift=b, **bn))
+
+    def SpatialBNLayer(self, blob_in, blob_out, dim_out, share_with=None, inplace=False):
+        """detector.py:111-124: Caffe2 SpatialBN in place of every AffineChannel[Nd] (MODEL.USE_BN).  Parameters `<blob>_s` (a weight),
+        `<blob>_b` (a bias), and the computed `<blob>_rm` / `<blob>_riv` (running mean / running VARIANCE, utils/net.py:225-233).
+        Test mode is the affine graph with the folded pair; training mode records a `SpatialBN` op behind the unfused conv."""
+        if share_with is not None:
+            raise NotImplementedError('Handle that')
+        blob_in, prefix = str(blob_in), str(blob_out)
+        is_test = True if cfg.MODEL.USE_BN_TESTMODE_ONLY else not self.train
+        s = self._param(prefix + '_s', [dim_out], ('ConstantFill', {'value': 1.}), 'w')
+        b = self._param(prefix + '_b', [dim_out], ('ConstantFill', {'value': 0.}), 'b')
+        rm = self._param(prefix + '_rm', [dim_out], ('ConstantFill', {'value': 0.}), 'c')
+        riv = self._param(prefix + '_riv', [dim_out], ('ConstantFill', {'value': 1.}), 'c')
+        self.param_specs[s]['bn'] = self.param_specs[b]['bn'] = True
+        eps = float(cfg.MODEL.BN_EPSILON)
+        if is_test:
+            # the fused conv epilogue has no scale / bias gradient: frozen, like the affine it stands for
+            self.param_specs[s]['affine'] = self.param_specs[b]['affine'] = True
+            return self._record_affine(blob_in, blob_in if inplace else prefix, s, b, rm=rm, riv=riv, eps=eps)
+        # (training mode keeps its input for the backward: never in place -- the reference's "Not supporting inplace yet")
+        return self.net.add(Op('SpatialBN', [blob_in], [prefix], scale=s, bias=b, rm=rm, riv=riv, eps=eps,
+                               momentum=float(cfg.MODEL.BN_MOMENTUM), relu=False, residual=None))
 
     AffineChannel = AffineChannelNd
 
@@ -219,7 +250,7 @@ class DetectionModelHelper(object):
     def Relu(self, blob_in, blob_out):
         blob_in, blob_out = str(blob_in), str(blob_out)
         prod = self.net.producer(blob_in)
-        if prod is not None and prod.type in ('Conv', 'FC') and not prod.args['relu'] \
+        if prod is not None and prod.type in ('Conv', 'FC', 'SpatialBN') and not prod.args['relu'] \
                 and not self.net.consumers(blob_in, prod):
             prod.args['relu'] = True
             prod.outputs = [blob_out]

@@ -690,6 +690,63 @@ def relu_bias_bwd(dy, y, dtype, C_real, relu=True, dy2=None, dbias=None):
     return g
 
 
+# ---- SpatialBN (MODEL.USE_BN): blobs [.., cs] NDHWC, statistics fp32 [cs] with zeros in the padding channels ------------------------
+def _bn_ws(dtype, rows, cs, device):
+    n = int(L._lib.dat_bn_workspace_bytes(dtype, C.c_longlong(rows), cs))
+    assert n > 0, 'SpatialBN: %d rows at channel stride %d' % (rows, cs)
+    return torch.empty(n, dtype=torch.uint8, device=device), n
+
+
+def bn_stats(z, dtype, C_real, scale, bias, eps, momentum, rm=None, riv=None):
+    """Batch statistics of z over all its positions -> fp32 [4, cs]: saved mean, rstd, and the pair a = scale * rstd,
+    b' = bias - mean * a that bn_apply reads; the running statistics rm / riv (fp32 [C]) are updated in place."""
+    cs = z.shape[-1]
+    rows = z.numel() // cs
+    assert z.is_contiguous() and all(t is None or (t.dtype == torch.float32 and t.is_contiguous()) for t in (scale, bias, rm, riv))
+    st = torch.empty((4, cs), dtype=torch.float32, device=z.device)
+    ws, n = _bn_ws(dtype, max(rows, 1), cs, z.device)
+    ctx().call('dat_bn_stats', _stream(), dtype, _ptr(z), C.c_longlong(rows), C_real, cs, _ptr(scale), _ptr(bias), C.c_float(eps),
+               C.c_float(momentum), _ptr(rm), _ptr(riv), _ptr(st[0]), _ptr(st[1]), _ptr(st[2]), _ptr(st[3]), _ptr(ws), C.c_size_t(n))
+    return st
+
+
+def bn_apply(z, dtype, C_real, a, b, relu=False, residual=None, out=None):
+    """y = act(z * a[c] + b[c] (+ residual)); out may be z (in place: only when z is not needed again) or the residual."""
+    cs = z.shape[-1]
+    assert z.is_contiguous() and (residual is None or (residual.shape == z.shape and residual.is_contiguous()))
+    y = torch.empty_like(z) if out is None else out
+    ctx().call('dat_bn_apply', _stream(), dtype, _ptr(z), _ptr(residual), _ptr(y), _ptr(a), _ptr(b), C.c_longlong(z.numel() // cs),
+               C_real, cs, int(relu))
+    return y
+
+
+def bn_bwd_reduce(dy, y, z, dtype, C_real, mean, rstd, frame_lo=0, relu=False, dbeta=None, dgamma=None, inplace=False):
+    """dy: the gradient of frames [frame_lo, frame_lo + dy.shape[0]) of the blob z ([frames, H, W, cs]; y = the op's output, read for
+    the ReLU mask).  -> (g = dy * [y > 0], sums fp32 [2, cs] = sum g, sum g * xhat); dbeta / dgamma (fp32 [C]) ACCUMULATE the sums."""
+    cs = z.shape[-1]
+    per = z.numel() // cs // z.shape[0]
+    assert dy.is_contiguous() and z.is_contiguous() and dy.shape[1:] == z.shape[1:] and (y is None or y.is_contiguous())
+    g = dy if inplace else torch.empty_like(dy)
+    sums = torch.empty((2, cs), dtype=torch.float32, device=z.device)
+    nrows = dy.shape[0] * per
+    ws, n = _bn_ws(dtype, nrows, cs, z.device)
+    ctx().call('dat_bn_bwd_reduce', _stream(), dtype, _ptr(dy), _ptr(y) if relu else None, _ptr(z), _ptr(g), _ptr(mean), _ptr(rstd),
+               C.c_longlong(z.shape[0] * per), C.c_longlong(frame_lo * per), C.c_longlong(nrows), C_real, cs, int(relu), _ptr(sums),
+               _ptr(dbeta), _ptr(dgamma), _ptr(ws), C.c_size_t(n))
+    return g, sums
+
+
+def bn_bwd_apply(g, z, dtype, C_real, mean, rstd, a, sums, frame_lo=0):
+    """dz for EVERY frame of the blob z: a * (g - db / M - xhat * ds / M), g = 0 outside its frame window."""
+    cs = z.shape[-1]
+    per = z.numel() // cs // z.shape[0]
+    assert g.is_contiguous() and z.is_contiguous()
+    dz = torch.empty_like(z)
+    ctx().call('dat_bn_bwd_apply', _stream(), dtype, _ptr(g), _ptr(z), _ptr(dz), _ptr(mean), _ptr(rstd), _ptr(a), _ptr(sums),
+               C.c_longlong(z.shape[0] * per), C.c_longlong(frame_lo * per), C.c_longlong(g.shape[0] * per), C_real, cs)
+    return dz
+
+
 def upsample2x_bwd(g, dtype, dtop=None):
     frames, H2, W2, cs = g.shape
     acc = dtop is not None

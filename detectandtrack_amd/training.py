@@ -388,7 +388,7 @@ class TrainExecutor(Executor):
         def build():
             w5 = self._master(a['w'])
             w5 = w5 if w5.dim() == 5 else w5.unsqueeze(2)
-            scale = self._master(a['scale']) if a['scale'] else None
+            scale = ws.affine_pair(a)[0]        # (a test-mode SpatialBN: the folded scale)
             return ops.ConvGrad(w5, scale, a['strides'], a['pads'], y.dt, xin.t.shape[3], g.shape[3], groups=a.get('group', 1))
         cg = self._conv_grad(i, build)
         if self._trainable(a['w']):
@@ -453,6 +453,35 @@ class TrainExecutor(Executor):
                 self._ncontrib[op.inputs[0]] = self._ncontrib.get(op.inputs[0], 0) + 1
                 if held or mask is not None:
                     self.grads[op.inputs[0]] = [(dx, ilo, mask is not None)]
+
+    def bwd_SpatialBN(self, i, op):
+        """g = dy masked by the fused ReLU (also the residual's gradient), db = sum g, ds = sum g * xhat, and
+        dz = s * rstd * (g - db / M - xhat * ds / M) over ALL frames of the input: the batch statistics couple every position of a
+        channel, so a frame-window gradient does not stay a window here (outside it g = 0, dz is not)."""
+        ws, a = self.ws, op.args
+        out = op.outputs[0]
+        y = ws.blobs[out]
+        dy, lo = self._take_grad(out, y.dt)
+        assert not self._last_masked, 'a ReLU-masked gradient reached a SpatialBN (the mask fusions of bwd_Conv are for Conv producers)'
+        self._last_masked = False
+        if dy is None:
+            return
+        z, st = y.bn
+        assert lo == 0 and dy.shape[0] == z.shape[0] or y.N == 1, 'frame-window gradients assume one clip per forward'
+        dev = {}
+        for key in ('bias', 'scale'):
+            name = a[key]
+            if self._trainable(name):       # the kernel ACCUMULATES: straight into the (zeroed) arena view when there is one
+                dev[key] = self.arena[name] if (self.arena is not None and name in self.arena) else \
+                    torch.zeros(y.C, dtype=torch.float32, device=ws.device)
+        g, sums = ops.bn_bwd_reduce(dy if dy.is_contiguous() else dy.contiguous(), y.t, z, y.dt, y.C, st[0], st[1], frame_lo=lo,
+                                    relu=bool(a['relu']), dbeta=dev.get('bias'), dgamma=dev.get('scale'))
+        for key, t in dev.items():
+            self._pgrad(a[key], t)
+        if a['residual']:
+            self._add_grad(a['residual'], g, lo)
+        if op.inputs[0] not in self.no_grad:
+            self._add_grad(op.inputs[0], ops.bn_bwd_apply(g, z, y.dt, y.C, st[0], st[1], st[2], sums, frame_lo=lo), 0)
 
     def _bwd_rpn_head(self, i):
         ws = self.ws
@@ -768,6 +797,9 @@ def no_grad_blobs(net):
     return ng
 
 
+_PARAM_KEYS = {'SpatialBN': ('scale', 'bias')}     # op type -> the args that name its trainable parameters (default: w, b)
+
+
 def param_ready_index(net, fused=None):
     """For every parameter blob a net's ops reference (`w`, `b`): the SMALLEST index of an op that uses it.  The backward pass runs
     the ops from the last to the first, so the parameter's gradient is final once the op of that index has been differentiated
@@ -777,7 +809,7 @@ def param_ready_index(net, fused=None):
     pos = {id(op): i for i, op in enumerate(net.ops)}
     for i, op in enumerate(net.ops):
         a = op.args if isinstance(op.args, dict) else {}
-        for key in ('w', 'b'):
+        for key in _PARAM_KEYS.get(op.type, ('w', 'b')):
             n = a.get(key)
             if isinstance(n, str) and n:
                 idx[n] = min(idx.get(n, i), i)
@@ -794,7 +826,7 @@ def param_ready_index(net, fused=None):
     users = {}
     for i, op in enumerate(net.ops):
         a = op.args if isinstance(op.args, dict) else {}
-        for key in ('w', 'b'):
+        for key in _PARAM_KEYS.get(op.type, ('w', 'b')):
             n = a.get(key)
             if isinstance(n, str) and n:
                 users.setdefault(n, []).append(op)

@@ -58,6 +58,8 @@ def synthetic_params(model, seed=3):
     activations stay O(1..10) through the stack —, affine bias N(0, 0.1), conv/FC biases N(0, 0.05); the bilinear
     up-sampling kernel is the fixed one of detector.py:356-372."""
     rs = np.random.RandomState(seed)
+    rs_stats = np.random.RandomState(seed + 1009)       # (the running statistics draw from their own stream: every other parameter
+                                                        #  is what the same model gets without MODEL.USE_BN)
     trans = cfg.RESNETS.TRANS_FUNC
     last_bn = ('_branch2c_bn_s',) if trans.startswith('bottleneck') else ('_branch2b_bn_s', '_branch2b_temporal_bn_s')
     linear = ('fpn_', 'rpn_cls', 'rpn_bbox', 'cls_score', 'bbox_pred', 'kps_score')
@@ -67,7 +69,10 @@ def synthetic_params(model, seed=3):
         shape = spec['shape']
         if spec['init'][0] == 'BilinearFill':
             out[name] = _fill('BilinearFill', spec['init'][1], shape, rs)
-        elif spec.get('affine'):
+        elif name in getattr(model, 'computed_params', ()):
+            # SpatialBN running mean: small, non-zero; running variance in (0.5, 1.5) -- a test must not pass on the identities 0 / 1
+            out[name] = (rs_stats.randn(*shape) * 0.1 if name.endswith('_rm') else rs_stats.uniform(0.5, 1.5, shape)).astype(np.float32)
+        elif spec.get('affine') or spec.get('bn'):
             if name.endswith('_s'):
                 lo, hi = (0.2, 0.4) if name.endswith(last_bn) else (0.5, 1.0)   # (the (2+1)D bodies: their last affine is `_temporal_bn`)
                 out[name] = rs.uniform(lo, hi, shape).astype(np.float32)
@@ -85,6 +90,14 @@ def synthetic_params(model, seed=3):
                 w = w / 64.0
             out[name] = w.astype(np.float32)
     return out
+
+
+def fold_bn(s, b, rm, riv, eps):
+    """Test-mode SpatialBN as the affine pair of the conv epilogue: a = s / sqrt(riv + eps), b' = b - rm * a, in fp32 in exactly this
+    order (`riv` is a running VARIANCE despite its name, reference :225-233)."""
+    s, b, rm, riv = (np.asarray(v, dtype=np.float32) for v in (s, b, rm, riv))
+    a = s / np.sqrt(riv + np.float32(eps))
+    return a.astype(np.float32), (b - rm * a).astype(np.float32)
 
 
 # ---- inflation (:95-161) ---------------------------------------------------------------------------------------------------
@@ -181,6 +194,10 @@ def initialize_from_weights_file(model, ws, weights_file, momentum=None):
             m = np.asarray(src[src_name + '_momentum'], dtype=np.float32)
             if tuple(m.shape) == shape:
                 momentum[name] = m
+    # (:225-233) every SpatialBN running statistic of the file, whether or not this model lists it: "needed to test the scratch trained models"
+    for src_name in sorted(src):
+        if src_name.endswith(('_rm', '_riv')) and src_name not in model.params:
+            ws.set_param(src_name, np.asarray(src[src_name], dtype=np.float32))
     if kept:
         logger.info('%d parameters not taken from %s (kept as initialised): %s', len(kept), weights_file, ' '.join(kept))
     return kept
@@ -189,6 +206,9 @@ def initialize_from_weights_file(model, ws, weights_file, momentum=None):
 def save_model_to_weights_file(weights_file, model, ws, momentum=None):
     """:252-294: parameters, their `<param>_momentum` blobs (when given: name -> array) and the cfg yaml."""
     blobs = {name: np.asarray(ws.params[name]) for name in model.params}
+    for name in ws.params:          # (:284-292) the SpatialBN running statistics of the workspace, also those this model does not list
+        if name.endswith(('_rm', '_riv')) and name not in blobs:
+            blobs[name] = np.asarray(ws.params[name])
     for name, m in (momentum or {}).items():
         blobs[name + '_momentum'] = np.asarray(m, dtype=np.float32)
     cfg_yaml = yaml.safe_dump(_plain(cfg))

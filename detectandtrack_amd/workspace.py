@@ -22,7 +22,7 @@ logger = logging.getLogger(__name__)
 class Blob(object):
     """A device blob.  kind: 'fmap' [N*T,H,W,Cs] | 'rows' [1,1,R,Cs] (FC activations) | 'mat' fp32 tensor |
     'rois' fp32 [cap, cols] + device count."""
-    __slots__ = ('t', 'kind', 'N', 'T', 'C', 'dt', 'five_d', 'count', 'sigmoid_of', 'host', 'keyframe', 't2c', 'split', 'tsel')
+    __slots__ = ('t', 'kind', 'N', 'T', 'C', 'dt', 'five_d', 'count', 'sigmoid_of', 'host', 'keyframe', 't2c', 'split', 'tsel', 'bn')
 
     def __init__(self, t, kind, N=1, T=1, C=0, dt=0, five_d=False, count=None):
         self.t, self.kind, self.N, self.T, self.C, self.dt = t, kind, N, T, C, dt
@@ -35,6 +35,7 @@ class Blob(object):
                                 # the reading conv / RoIAlign address that frame themselves)
         self.t2c = False        # time moved into channels (detector.py:480-491): still stored as T frames of C channels
         self.keyframe = None    # set when only this frame of a T-frame blob was computed (cfg.HIP.KEYFRAME_DCE)
+        self.bn = None          # output of a training-mode SpatialBN: (its input tensor z, fp32 [4, cs] = mean, rstd, a, b') for the backward
 
 
 class Workspace(object):
@@ -104,6 +105,7 @@ class Workspace(object):
     _READER_KEYS = ('slice_lazy', 'pad_unread', 'conv_reader')
 
     def CreateNet(self, net):
+        check_bn_sees_every_frame(net)
         self.nets[net.name] = net
         # a new net may read a blob that so far only pad-blind / frame-addressing ops read: the cached reader scans (lazy SliceKeyFrame,
         # skipped zero fill of the padding channels, epilogue-written bf16x3 splits) are re-derived on the next forward.  `_layers` is
@@ -166,9 +168,30 @@ class Workspace(object):
 
     def params_from_device(self, names=None):
         """Copy the device fp32 masters (updated in place by training) back into the host parameter dict (checkpoints)."""
+        stats = False
         for n in (names if names is not None else list(self._dev_params)):
             if n in self._dev_params:
                 self.params[n] = self._dev_params[n].cpu().numpy()
+                stats = stats or n.endswith(('_rm', '_riv'))
+        if stats:
+            # running statistics moved (training-mode SpatialBN updates them on the device): layers of a test-mode graph on this
+            # workspace hold the pair folded from the old ones
+            self._layers.clear()
+            self.param_epoch = getattr(self, 'param_epoch', 0) + 1
+
+    def affine_pair(self, a):
+        """(scale, bias) device tensors of a conv's fused affine (`a` = the op's args), or (None, None).  For a test-mode SpatialBN
+        (the op also names rm / riv / eps) the pair folded on the host from the parameters as they are now."""
+        if not a.get('scale'):
+            return None, None
+        if not a.get('rm'):
+            return self.dev_param(a['scale']), self.dev_param(a['shift'])
+        key = ('bnfold', a['scale'])
+        if key not in self._layers:     # (set_param clears `_layers`: re-folded whenever a parameter is set)
+            from detectandtrack_amd.utils.net import fold_bn
+            sc, sh = fold_bn(self.params[a['scale']], self.params[a['shift']], self.params[a['rm']], self.params[a['riv']], a['eps'])
+            self._layers[key] = tuple(torch.from_numpy(v).to(self.device) for v in (sc, sh))
+        return self._layers[key]
 
 
 def blob_as_matrix(b):
@@ -203,6 +226,15 @@ def _valid_rows(b, arr):
         assert seg * len(cnt) == arr.shape[0], (arr.shape, len(cnt))
         return np.concatenate([arr[i * seg:i * seg + int(c)] for i, c in enumerate(cnt)], axis=0)
     return arr[:_count(b)]
+
+
+def check_bn_sees_every_frame(net):
+    """A training-mode SpatialBN normalises with the statistics of ALL frames of its input: it cannot run in a forward that computes
+    a subset of the frames."""
+    if (cfg.HIP.KEYFRAME_DCE or int(cfg.HIP.FRAME_TRUNK_CACHE) > 0) and any(op.type == 'SpatialBN' for op in net.ops):
+        raise ValueError('net %r holds training-mode SpatialBN ops (MODEL.USE_BN), whose batch statistics need every frame of their '
+                         'input: not combinable with HIP.KEYFRAME_DCE / HIP.FRAME_TRUNK_CACHE, which compute a subset of the frames'
+                         % (net.name,))
 
 
 def _mode(ws=None):
@@ -245,6 +277,7 @@ class Executor(object):
     _TSEL_AWARE = frozenset(['Conv', 'RoIFeatureTransform'])    # handlers that understand Blob.tsel
 
     def __init__(self, ws, net):
+        check_bn_sees_every_frame(net)
         self.ws, self.net = ws, net
         self.pending_rpn = []
         self.has_collect = any(op.type == 'CollectAndDistributeFpnRpnProposals' for op in net.ops)
@@ -450,8 +483,8 @@ class Executor(object):
 
         def build():
             w = _w5d(ws.dev_param(a['w']))
-            scale = ws.dev_param(a['scale']) if a['scale'] else None
-            bias = ws.dev_param(a['shift']) if a['shift'] else (ws.dev_param(a['b']) if a['b'] else None)
+            scale, shift = ws.affine_pair(a)
+            bias = shift if a['shift'] else (ws.dev_param(a['b']) if a['b'] else None)
             return ops.ConvLayer(w, scale, bias, stride=a['strides'], pads=a['pads'], relu=a['relu'], dtype=dt,
                                  cin_stride=xin.t.shape[3], x3=_x3(self.ws), groups=a.get('group', 1))
         layer = self._layer(i, build)
@@ -550,8 +583,8 @@ class Executor(object):
             n, _, t, h, w = data.shape
 
         def build():
-            scale = ws.dev_param(a['scale']) if a['scale'] else None
-            bias = ws.dev_param(a['shift']) if a['shift'] else (ws.dev_param(a['b']) if a['b'] else None)
+            scale, shift = ws.affine_pair(a)
+            bias = shift if a['shift'] else (ws.dev_param(a['b']) if a['b'] else None)
             return ops.StemConv(_w5d(ws.dev_param(a['w'])), scale, bias, dt, relu=a['relu'])
         layer = self._layer(i, build)
         # (the fused stem kernel is not a conv3d_igemm launch: it is not part of the bench's per-launch conv log)
@@ -634,6 +667,21 @@ class Executor(object):
             head = Blob(y, 'fmap', xin.N, xin.T, A + do.args['dim_out'], dt, xin.five_d)
         ws.blobs[lo.outputs[0] + '+' + do.outputs[0]] = head
         ws.blobs['_rpnhead_for_%d' % gi] = head
+
+    def op_SpatialBN(self, i, op):
+        """Training-mode SpatialBN (+ fused residual / ReLU): batch statistics over every position of the input, running statistics
+        updated in place on the device masters, then one normalise pass.  The output keeps (z, mean / rstd / a / b') for the backward."""
+        ws, a = self.ws, op.args
+        x = ws.blobs[op.inputs[0]]
+        assert x.kind == 'fmap' and x.keyframe is None and not x.t2c, (op, x.kind)
+        assert x.count is None, 'SpatialBN over a row-counted blob (per-RoI head) is not supported'
+        st = ops.bn_stats(x.t, x.dt, x.C, ws.dev_param(a['scale']), ws.dev_param(a['bias']), a['eps'], a['momentum'],
+                          ws.dev_param(a['rm']), ws.dev_param(a['riv']))
+        res = ws.blobs[a['residual']].t if a['residual'] else None
+        y = ops.bn_apply(x.t, x.dt, x.C, st[2], st[3], relu=a['relu'], residual=res)
+        b = Blob(y, 'fmap', x.N, x.T, x.C, x.dt, x.five_d)
+        b.bn = (x.t, st)
+        ws.blobs[op.outputs[0]] = b
 
     def op_MaxPool(self, i, op):
         x = self.ws.blobs[op.inputs[0]]

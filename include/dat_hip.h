@@ -550,6 +550,34 @@ int dat_softmax_ce_rows(dat_ctx* ctx, dat_stream s, int dtype, const void* logit
 int dat_sgd_momentum(dat_ctx* ctx, dat_stream s, float* w, float* v, const float* grad, long long n, float lr, float momentum,
                      float weight_decay, int is_bias);
 
+/* ---- SpatialBN (MODEL.USE_BN) ------------------------------------------------------------------------
+ * Caffe2's SpatialBN (cuDNN engine semantics, restated: its source is not part of the reference tree) on NDHWC blobs
+ * [rows][cstride]: cstride % 64 == 0, real channels [0, C), fp32 or the build's 16-bit format; every statistic and sum is fp32.
+ * Every kernel writes zeros to the padding channels [C, cstride) of what it writes and uses no float atomics (same input, same bits).
+ * `ws`: caller-owned scratch of dat_bn_workspace_bytes(dtype, rows, cstride) bytes (per-block partial rows); mean / rstd / a / bprime
+ * hold cstride floats, sums 2 * cstride, scale / bias / rm / riv / dbeta / dgamma C floats. */
+size_t dat_bn_workspace_bytes(int dtype, long long rows, int cstride);
+/* Batch statistics of z over all rows: mean and the biased variance per channel (per-block (count, mean, M2) partials merged with
+ * Chan's formula), then  mean, rstd = 1 / sqrt(var + eps),  a = scale * rstd,  bprime = bias - mean * a,  and in place
+ * rm = momentum * rm + (1 - momentum) * mean,  riv = momentum * riv + (1 - momentum) * var * rows / (rows - 1)   (rm / riv may be NULL).
+ * rows < 2 is DAT_ERR_ARG. */
+int dat_bn_stats(dat_ctx* ctx, dat_stream s, int dtype, const void* z, long long rows, int C, int cstride, const float* scale,
+                 const float* bias, float eps, float momentum, float* rm, float* riv, float* mean, float* rstd, float* a, float* bprime,
+                 void* ws, size_t ws_bytes);
+/* y = act(z * a[c] + bprime[c] (+ residual)), act = ReLU when relu.  y may alias z and / or residual (NULL: none). */
+int dat_bn_apply(dat_ctx* ctx, dat_stream s, int dtype, const void* z, const void* residual, void* y, const float* a, const float* bprime,
+                 long long rows, int C, int cstride, int relu);
+/* dy, g: the rows [row_lo, row_lo + nrows) of a blob of `rows` rows (a frame window of the gradient); y (the op's output; NULL without
+ * relu) and z: the WHOLE blob.  g = dy * [y > 0] (g may alias dy);  sums[c] = sum g,  sums[cstride + c] = sum g * xhat with
+ * xhat = (z - mean) * rstd, over the window;  dbeta[c] += sums[c], dgamma[c] += sums[cstride + c] (either may be NULL). */
+int dat_bn_bwd_reduce(dat_ctx* ctx, dat_stream s, int dtype, const void* dy, const void* y, const void* z, void* g, const float* mean,
+                      const float* rstd, long long rows, long long row_lo, long long nrows, int C, int cstride, int relu, float* sums,
+                      float* dbeta, float* dgamma, void* ws, size_t ws_bytes);
+/* dz = a * (g - sums[c] / rows - xhat * sums[cstride + c] / rows) for EVERY row of the blob; g (rows [row_lo, row_lo + nrows)) counts
+ * as zero outside its window -- dz does not vanish there. */
+int dat_bn_bwd_apply(dat_ctx* ctx, dat_stream s, int dtype, const void* g, const void* z, void* dz, const float* mean, const float* rstd,
+                     const float* a, const float* sums, long long rows, long long row_lo, long long nrows, int C, int cstride);
+
 /* ---- training input pipeline: RPN anchor labelling, device half -------------------------------------
  * Replaces the O(anchors x gts) part of reference lib/roi_data/rpn.py:283-312: the straddle filter (:283-291), the Cython
  * IoU lib/utils/cython_bbox.pyx:16-57 averaged over the tube's frames (lib/utils/boxes.py:60-69), anchor->gt max / first
