@@ -480,20 +480,24 @@ class ConvGrad(object):
             gz = g
         lay = self._data_layer
         in_t = g_frames if (g_frames is not None and frames == T) else None   # zero frames of g: their temporal taps are skipped
+        # a forward conv without "same" temporal padding (pad_t = 0 under kT = 3: the windowed / (2+1)D form) has the data-gradient padding
+        # kT - 1 - pad_t != (kT - 1) / 2, which the library takes only with an explicit output-frame window: here all T frames
+        out_t = (0, T) if 2 * lay.pads[0] + 1 != self.kt else None
         if accumulate_into is not None and mask is not None:
             # the LAST contribution to the gradient of x = relu(...): sum into `accumulate_into` and apply the ReLU backward of x's producer in the
             # same epilogue (res_mode 4: out = x > 0 ? conv + out : 0, in place)
             # (inplace=False: into a new tensor -- a queued weight-gradient job still reads `accumulate_into`)
             assert mask.is_contiguous() and mask.dtype == gz.dtype and mask.shape == accumulate_into.shape
-            return lay(gz, T=T, residual=mask, res_mode=4, addend=accumulate_into, out=accumulate_into if inplace else None, in_t=in_t)
+            return lay(gz, T=T, residual=mask, res_mode=4, addend=accumulate_into, out=accumulate_into if inplace else None, in_t=in_t,
+                       out_t=out_t)
         if accumulate_into is not None:
             # inplace=False: the sum goes to a NEW tensor (`accumulate_into` is read as the residual and left untouched -- somebody else,
             # a queued weight-gradient job, still needs its present contents)
-            return lay(gz, T=T, residual=accumulate_into, res_mode=1, out=accumulate_into if inplace else None, in_t=in_t)
+            return lay(gz, T=T, residual=accumulate_into, res_mode=1, out=accumulate_into if inplace else None, in_t=in_t, out_t=out_t)
         if mask is not None:
             assert mask.is_contiguous() and mask.dtype == gz.dtype
-            return lay(gz, T=T, residual=mask, res_mode=3, in_t=in_t)
-        return lay(gz, T=T, in_t=in_t)
+            return lay(gz, T=T, residual=mask, res_mode=3, in_t=in_t, out_t=out_t)
+        return lay(gz, T=T, in_t=in_t, out_t=out_t)
 
 
 class BucketAllReduce(object):

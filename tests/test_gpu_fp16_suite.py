@@ -2,7 +2,8 @@
 
 The 16-bit format belongs to the loaded library, so the format-generic kernel tests run again in ONE child process started with
 DAT_H16=fp16: tests/test_gpu_kernels.py, tests/test_gpu_fp16_edges.py, tests/test_gpu_infer_kernels.py, tests/test_gpu_wgrad.py (the
-weight-gradient kernels), tests/test_gpu_temporal_windows.py (the conv frame windows) and the persistent-kernel test of tests/test_gpu_model.py.
+weight-gradient kernels), tests/test_gpu_temporal_windows.py (the conv frame windows), tests/test_gpu_weight_pack.py and tests/test_gpu_dgrad.py (the weight
+packers and the dense data gradient) and the persistent-kernel test of tests/test_gpu_model.py.
 The parent reads the child's JUnit report: no failure or error, every skip is a bf16-only test, and one test per kernel family (plus
 the NMS and proposal goldens) is among the passed -- so that a collection mistake cannot pass for a green run.  The child is never
 retried."""
@@ -17,7 +18,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_FILES = ['tests/test_gpu_kernels.py', 'tests/test_gpu_fp16_edges.py', 'tests/test_gpu_infer_kernels.py', 'tests/test_gpu_wgrad.py',
-               'tests/test_gpu_temporal_windows.py',
+               'tests/test_gpu_temporal_windows.py', 'tests/test_gpu_weight_pack.py', 'tests/test_gpu_dgrad.py',
                'tests/test_gpu_model.py::test_persistent_kernel_cu_share_does_not_change_results']
 
 K = 'tests.test_gpu_kernels::'
@@ -25,6 +26,8 @@ E = 'tests.test_gpu_fp16_edges::'
 I = 'tests.test_gpu_infer_kernels::'
 G = 'tests.test_gpu_wgrad::'
 W = 'tests.test_gpu_temporal_windows::'
+P = 'tests.test_gpu_weight_pack::'
+D = 'tests.test_gpu_dgrad::'
 MUST_PASS = [
     K + 'test_layout_roundtrip[1]',
     K + 'test_conv3d[3x3x3-bf16]',                                   # generic kernel + the split-K finish
@@ -78,6 +81,13 @@ MUST_PASS = [
     W + 'test_short_clips[short_t1-outall-inall-affine_res_relu]',              # generic kernel, a split-K slice with an empty patch range
     W + 'test_temporal_k311_windows[k311-outall-in1+2-affine_res_relu]',        # windowed kT x 1 x 1: the one-tap variant
     W + 'test_big_tile_windows[big_tile-outall-in1+1-none]',                    # big-tile kernel, a frame without a valid tap
+    P + 'test_per_layer_packer_is_bit_equal_to_the_expected_image[72x130x3x3x3-dgrad-16]',   # data-gradient packer, ragged, fp16 rounding
+    P + 'test_batched_packer_is_bit_equal_to_the_expected_images[16]',
+    D + 'test_generic_64_wide_table_driven[k333_same-16]',                     # data gradient: generic 3 x 3 x 3 ...
+    D + 'test_generic_64_wide_table_driven[k333_pad_t0-16]',                   # ... and with the T padding 2
+    D + 'test_k_streaming_1x1',
+    D + 'test_zero_insertion_3x3x3_stride2[k333_s2_13x16]',
+    D + 'test_weights_in_lds_1x1',
 ]
 
 

@@ -81,6 +81,12 @@ def test_conv_backward_matches_autograd(ops, case, dtype_name):
     got = _from_ndhwc(dx, N, cin, T)
     err = (got - xr.grad).abs().max() / max(xr.grad.abs().max(), 1e-6)
     assert err < (2e-4 if dtype_name == 'fp32' else 3e-2), 'dx rel err %.3e' % err
+    if dtype_name == 'fp32':
+        # every element against float64 (tests/numerics.py): fp32 operands, fp32 accumulation, one fp32 rounding of w * scale in the packer
+        x64, w64, s64, gy64 = x.double(), w.double(), scale.double().view(1, -1, 1, 1, 1), gy.double()
+        dgrad = lambda a, b: torch.nn.grad.conv3d_input(x.shape, a, b, stride=(1, st, st), padding=pads)
+        abs_dx = dgrad(w64.abs(), (gy64 * s64).abs())
+        nm.assert_elementwise(got, dgrad(w64, gy64 * s64), abs_dx, nm.conv_k(cout, k), 'fp32', 'dx', extra=nm.unit_roundoff('fp32') * abs_dx)
     if dtype_name == 'bf16':
         # per-element bounds against float64 (tests/numerics.py): dW is stored in fp32 after a reduction over every output position
         x64, w64, s64, gy64 = x.double(), w.double(), scale.double().view(1, -1, 1, 1, 1), gy.double()
