@@ -284,12 +284,16 @@ def _build_defaults():
     # TRAIN_GROUPED_CONV (opt-in, training): model_builder.create(train=True) accepts a grouped (ResNeXt, RESNETS.NUM_GROUPS > 1) body; its
     # `branch2b` layers take the grouped data-gradient layer and wgrad_grouped_kernel.  False keeps the builder's
     # NotImplementedError until the path has been measured at full size
+    # USE_GN (opt-in): every AffineChannel[Nd] of the body becomes a GroupNorm layer (csrc/group_norm.hip) behind the
+    # unfused conv, in training AND test graphs -- statistics per clip over T x H x W x the group's channels, no running statistics, trainable
+    # scale / bias.  GN_NUM_GROUPS: a layer of C channels gets the largest divisor of C that is <= this many groups (modeling/detector.py
+    # gn_groups).  GN_EPSILON: added to the variance.  Not combinable with MODEL.USE_BN, HIP.KEYFRAME_DCE or HIP.FRAME_TRUNK_CACHE
     c.HIP = AttrDict({'DTYPE': 'bf16', 'KEYFRAME_DCE': False, 'DEVICE_KPS_DECODE': True, 'FRAME_TRUNK_CACHE': 0,
                       'DEVICE_BOX_RESULTS': True, 'FUSE_STEM_POOL': True, 'RCCL_DIRECT': False,
                       'PIPELINE_DEPTH': 4, 'CLIP_GRAPH': True, 'IMS_PER_FORWARD': 1, 'FUSE_RELU_BWD': True, 'FUSE_RELU_SUM_BWD': True, 'PERSISTENT_CU_SHARE': 50, 'DET_SPARE_ROWS': 4,
                       'DEFER_WGRAD_FINISH': True, 'MAX_GRAPHS_PER_SLOT': 6, 'PAD_TAIL_FORWARD': True,
                       'OVERLAP_ALLREDUCE': True, 'WGRAD_PW_BATCH': 16, 'DEVICE_ROI_SAMPLING': True, 'DECONV_GROUP_IGNORED': False, 'STEM_FROM_UINT8': True,
-                      'TRAIN_GROUPED_CONV': False})
+                      'TRAIN_GROUPED_CONV': False, 'USE_GN': False, 'GN_NUM_GROUPS': 32, 'GN_EPSILON': 1e-5})
     return c
 
 

@@ -167,6 +167,11 @@ _PROTOS = {
     'dat_bn_apply': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _ll, _i, _i, _i]),
     'dat_bn_bwd_reduce': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _ll, _ll, _ll, _i, _i, _i, _p, _p, _p, _p, C.c_size_t]),
     'dat_bn_bwd_apply': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _ll, _ll, _ll, _i, _i]),
+    'dat_gn_workspace_bytes': (C.c_size_t, [_i, _i, _ll, _i]),
+    'dat_gn_stats': (_i, [_p, _p, _i, _p, _i, _ll, _i, _i, _i, _p, _p, _f, _p, _p, _p, _p, _p, C.c_size_t]),
+    'dat_gn_apply': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _ll, _i, _i, _i]),
+    'dat_gn_bwd_reduce': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _ll, _ll, _ll, _i, _i, _i, _i, _p, _p, _p, _p, _p, C.c_size_t]),
+    'dat_gn_bwd_apply': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _ll, _ll, _ll, _i, _i]),
     'dat_zero_insert2x': (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i]),
     'dat_upsample2x_bwd': (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i]),
     'dat_sgd_momentum': (_i, [_p, _p, _p, _p, _p, C.c_longlong, _f, _f, _f, _i]),

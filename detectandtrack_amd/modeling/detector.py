@@ -73,12 +73,13 @@ class Net(object):
         # fold "conv + shortcut" / "lateral + upsampled top-down" into the conv epilogue
         for x, y in ((a, b), (b, a)):
             pa = self.producer(x)
-            if pa is not None and pa.type in ('Conv', 'SpatialBN') and not pa.args['relu'] and pa.args['residual'] is None \
+            if pa is not None and pa.type in ('Conv',) + _NORM_OPS and not pa.args['relu'] and pa.args['residual'] is None \
                     and not self.consumers(x, pa):
                 py = self.producer(y)
                 res, mode = y, 1
-                # (a SpatialBN producer takes a same-shape residual only: the FPN lateral convs carry a bias, never an affine / BN)
-                assert pa.type == 'Conv' or py is None or py.type != 'UpsampleNearest2x', 'SpatialBN + upsampled top-down Sum'
+                # (a SpatialBN / GroupNorm producer takes a same-shape residual only: the FPN lateral convs carry a bias, never an
+                #  affine / BN / GN)
+                assert pa.type == 'Conv' or py is None or py.type != 'UpsampleNearest2x', pa.type + ' + upsampled top-down Sum'
                 if py is not None and py.type == 'UpsampleNearest2x':
                     res, mode = py.inputs[0], 2
                     if not self.consumers(y, py):
@@ -104,6 +105,17 @@ class Net(object):
 
     def BlobIsDefined(self, blob):
         return self.producer(str(blob)) is not None
+
+
+_NORM_OPS = ('SpatialBN', 'GroupNorm')      # normalisation ops behind an unfused conv: Sum (same shape) and Relu fold into them
+
+
+def gn_groups(channels, max_groups):
+    """Group count of a GroupNorm layer: the largest divisor of `channels` that is <= `max_groups` (HIP.GN_NUM_GROUPS).  The standard
+    widths keep max_groups = 32; the (2+1)D mid planes get 144 -> 24, 230 -> 23, 921 -> 3."""
+    channels, max_groups = int(channels), int(max_groups)
+    assert channels >= 1 and max_groups >= 1, (channels, max_groups)
+    return max(g for g in range(1, min(channels, max_groups) + 1) if channels % g == 0)
 
 
 class DetectionModelHelper(object):
@@ -188,8 +200,12 @@ class DetectionModelHelper(object):
 
     def AffineChannelNd(self, blob_in, blob_out, dim_out, share_with=None, inplace=False):
         """detector.py:89-108.  Folded into the producing conv's epilogue when possible."""
+        if cfg.HIP.USE_GN and cfg.MODEL.USE_BN:
+            raise ValueError('HIP.USE_GN and MODEL.USE_BN both replace every AffineChannel[Nd]: set one of them')
         if cfg.MODEL.USE_BN:
             return self.SpatialBNLayer(blob_in, blob_out, dim_out, share_with, inplace)
+        if cfg.HIP.USE_GN:
+            return self.GroupNormLayer(blob_in, blob_out, dim_out, share_with, inplace)
         blob_in = str(blob_in)
         prefix = str(blob_out) if share_with is None else share_with
         s = self._param(prefix + '_s', [dim_out], ('ConstantFill', {'value': 1.}), 'w')
@@ -231,6 +247,20 @@ class DetectionModelHelper(object):
         return self.net.add(Op('SpatialBN', [blob_in], [prefix], scale=s, bias=b, rm=rm, riv=riv, eps=eps,
                                momentum=float(cfg.MODEL.BN_MOMENTUM), relu=False, residual=None))
 
+    def GroupNormLayer(self, blob_in, blob_out, dim_out, share_with=None, inplace=False):
+        """GroupNorm in place of every AffineChannel[Nd] (HIP.USE_GN; not in the reference): statistics per clip and group, so the op is
+        the same in training and test graphs and has no computed parameters.  `<blob>_s` (a weight, init 1) and `<blob>_b` (a bias,
+        init 0) train.  Recorded behind the unfused conv; `Sum` and `Relu` fold into it as they fold into a SpatialBN."""
+        if share_with is not None:
+            raise NotImplementedError('Handle that')
+        blob_in, prefix = str(blob_in), str(blob_out)
+        s = self._param(prefix + '_s', [dim_out], ('ConstantFill', {'value': 1.}), 'w')
+        b = self._param(prefix + '_b', [dim_out], ('ConstantFill', {'value': 0.}), 'b')
+        self.param_specs[s]['gn'] = self.param_specs[b]['gn'] = True
+        # (keeps its input for the backward, and the statistics pass reads it before the apply pass writes: never in place)
+        return self.net.add(Op('GroupNorm', [blob_in], [prefix], scale=s, bias=b, groups=gn_groups(dim_out, cfg.HIP.GN_NUM_GROUPS),
+                               eps=float(cfg.HIP.GN_EPSILON), relu=False, residual=None))
+
     AffineChannel = AffineChannelNd
 
     def ConvAffineNd(self, blob_in, prefix, dim_in, dim_out, kernels, strides, pads, group=1, dilations=1,
@@ -250,7 +280,7 @@ class DetectionModelHelper(object):
     def Relu(self, blob_in, blob_out):
         blob_in, blob_out = str(blob_in), str(blob_out)
         prod = self.net.producer(blob_in)
-        if prod is not None and prod.type in ('Conv', 'FC', 'SpatialBN') and not prod.args['relu'] \
+        if prod is not None and prod.type in ('Conv', 'FC') + _NORM_OPS and not prod.args['relu'] \
                 and not self.net.consumers(blob_in, prod):
             prod.args['relu'] = True
             prod.outputs = [blob_out]

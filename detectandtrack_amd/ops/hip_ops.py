@@ -751,6 +751,71 @@ def bn_bwd_apply(g, z, dtype, C_real, mean, rstd, a, sums, frame_lo=0):
     return dz
 
 
+# ---- GroupNorm (HIP.USE_GN): blobs [clips * frames, H, W, cs] NDHWC, tables fp32 [clips, cs] with zeros in the padding channels --------
+def _gn_ws(dtype, clips, rows, cs, device):
+    n = int(L._lib.dat_gn_workspace_bytes(dtype, clips, C.c_longlong(rows), cs))
+    assert n > 0, 'GroupNorm: %d clips of %d rows at channel stride %d' % (clips, rows, cs)
+    return torch.empty(n, dtype=torch.uint8, device=device), n
+
+
+def _gn_rows(z, clips):
+    cs = z.shape[-1]
+    assert z.is_contiguous() and z.shape[0] % clips == 0, (tuple(z.shape), clips)
+    return cs, z.numel() // cs // clips
+
+
+def gn_stats(z, dtype, C_real, groups, scale, bias, eps, clips=1):
+    """Group statistics of every clip of z ([clips * frames, H, W, cs]) over its positions x the C_real / groups channels of each
+    group -> fp32 [4, clips, cs]: mean, rstd, and the pair a = scale * rstd, b' = bias - mean * a that gn_apply reads."""
+    cs, rows = _gn_rows(z, clips)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (scale, bias))
+    st = torch.empty((4, clips, cs), dtype=torch.float32, device=z.device)
+    ws, n = _gn_ws(dtype, clips, rows, cs, z.device)
+    ctx().call('dat_gn_stats', _stream(), dtype, _ptr(z), clips, C.c_longlong(rows), C_real, cs, groups, _ptr(scale), _ptr(bias),
+               C.c_float(eps), _ptr(st[0]), _ptr(st[1]), _ptr(st[2]), _ptr(st[3]), _ptr(ws), C.c_size_t(n))
+    return st
+
+
+def gn_apply(z, dtype, C_real, a, b, clips=1, relu=False, residual=None, out=None):
+    """y = act(z * a[clip, c] + b[clip, c] (+ residual)); out may be z (in place: only when z is not needed again) or the residual."""
+    cs, rows = _gn_rows(z, clips)
+    assert residual is None or (residual.shape == z.shape and residual.is_contiguous())
+    assert tuple(a.shape) == tuple(b.shape) == (clips, cs) and a.is_contiguous() and b.is_contiguous()
+    y = torch.empty_like(z) if out is None else out
+    ctx().call('dat_gn_apply', _stream(), dtype, _ptr(z), _ptr(residual), _ptr(y), _ptr(a), _ptr(b), clips, C.c_longlong(rows), C_real, cs,
+               int(relu))
+    return y
+
+
+def gn_bwd_reduce(dy, y, z, dtype, C_real, groups, mean, rstd, scale, clips=1, frame_lo=0, relu=False, dbeta=None, dgamma=None,
+                  inplace=False):
+    """dy: the gradient of every frame of the `clips` clips of z, or (one clip) of its frames [frame_lo, frame_lo + dy.shape[0]); y = the
+    op's output, read for the ReLU mask.  -> (g = dy * [y > 0], sums fp32 [clips, 2, cs] = sum g, sum g * xhat per clip, coef fp32
+    [clips, 2, cs] for gn_bwd_apply); dbeta / dgamma (fp32 [C]) ACCUMULATE the sums of all clips."""
+    cs, rows = _gn_rows(z, clips)
+    per = rows // (z.shape[0] // clips)
+    assert dy.is_contiguous() and dy.shape[1:] == z.shape[1:] and (y is None or y.is_contiguous()) and dy.shape[0] % clips == 0
+    g = dy if inplace else torch.empty_like(dy)
+    sums = torch.empty((clips, 2, cs), dtype=torch.float32, device=z.device)
+    coef = torch.empty((clips, 2, cs), dtype=torch.float32, device=z.device)
+    ws, n = _gn_ws(dtype, clips, rows, cs, z.device)
+    ctx().call('dat_gn_bwd_reduce', _stream(), dtype, _ptr(dy), _ptr(y) if relu else None, _ptr(z), _ptr(g), _ptr(mean), _ptr(rstd),
+               _ptr(scale), clips, C.c_longlong(rows), C.c_longlong(frame_lo * per), C.c_longlong(dy.shape[0] // clips * per), C_real, cs,
+               groups, int(relu), _ptr(sums), _ptr(coef), _ptr(dbeta), _ptr(dgamma), _ptr(ws), C.c_size_t(n))
+    return g, sums, coef
+
+
+def gn_bwd_apply(g, z, dtype, C_real, mean, a, coef, clips=1, frame_lo=0):
+    """dz for EVERY frame of the blob z: a g + coef[0] + coef[1] (z - mean), g = 0 outside its frame window."""
+    cs, rows = _gn_rows(z, clips)
+    per = rows // (z.shape[0] // clips)
+    assert g.is_contiguous() and g.shape[0] % clips == 0
+    dz = torch.empty_like(z)
+    ctx().call('dat_gn_bwd_apply', _stream(), dtype, _ptr(g), _ptr(z), _ptr(dz), _ptr(mean), _ptr(a), _ptr(coef), clips, C.c_longlong(rows),
+               C.c_longlong(frame_lo * per), C.c_longlong(g.shape[0] // clips * per), C_real, cs)
+    return dz
+
+
 def upsample2x_bwd(g, dtype, dtop=None):
     frames, H2, W2, cs = g.shape
     acc = dtop is not None

@@ -483,6 +483,36 @@ class TrainExecutor(Executor):
         if op.inputs[0] not in self.no_grad:
             self._add_grad(op.inputs[0], ops.bn_bwd_apply(g, z, y.dt, y.C, st[0], st[1], st[2], sums, frame_lo=lo), 0)
 
+    def bwd_GroupNorm(self, i, op):
+        """g = dy masked by the fused ReLU (also the residual's gradient), dbias = sum g, dscale = sum g * xhat, and
+        dz = rstd * (s g - A / Mg - xhat B / Mg) over ALL frames of the input, A / B the group's sums of s * sum g / s * sum g xhat: the
+        group statistics couple every position of a clip, so a frame-window gradient does not stay a window here."""
+        ws, a = self.ws, op.args
+        out = op.outputs[0]
+        y = ws.blobs[out]
+        dy, lo = self._take_grad(out, y.dt)
+        assert not self._last_masked, 'a ReLU-masked gradient reached a GroupNorm (the mask fusions of bwd_Conv are for Conv producers)'
+        self._last_masked = False
+        if dy is None:
+            return
+        z, st = y.bn
+        assert lo == 0 and dy.shape[0] == z.shape[0] or y.N == 1, 'frame-window gradients assume one clip per forward'
+        dev = {}
+        for key in ('bias', 'scale'):
+            name = a[key]
+            if self._trainable(name):       # the kernel ACCUMULATES: straight into the (zeroed) arena view when there is one
+                dev[key] = self.arena[name] if (self.arena is not None and name in self.arena) else \
+                    torch.zeros(y.C, dtype=torch.float32, device=ws.device)
+        g, _, coef = ops.gn_bwd_reduce(dy if dy.is_contiguous() else dy.contiguous(), y.t, z, y.dt, y.C, a['groups'], st[0], st[1],
+                                       self._master(a['scale']), clips=y.N, frame_lo=lo, relu=bool(a['relu']), dbeta=dev.get('bias'),
+                                       dgamma=dev.get('scale'))
+        for key, t in dev.items():
+            self._pgrad(a[key], t)
+        if a['residual']:
+            self._add_grad(a['residual'], g, lo)
+        if op.inputs[0] not in self.no_grad:
+            self._add_grad(op.inputs[0], ops.gn_bwd_apply(g, z, y.dt, y.C, st[0], st[2], coef, clips=y.N, frame_lo=lo), 0)
+
     def _bwd_rpn_head(self, i):
         ws = self.ws
         lo, do, gi = self._fused[i]
@@ -797,7 +827,7 @@ def no_grad_blobs(net):
     return ng
 
 
-_PARAM_KEYS = {'SpatialBN': ('scale', 'bias')}     # op type -> the args that name its trainable parameters (default: w, b)
+_PARAM_KEYS = {'SpatialBN': ('scale', 'bias'), 'GroupNorm': ('scale', 'bias')}     # op type -> the args that name its trainable parameters (default: w, b)
 
 
 def param_ready_index(net, fused=None):

@@ -72,7 +72,7 @@ def synthetic_params(model, seed=3):
         elif name in getattr(model, 'computed_params', ()):
             # SpatialBN running mean: small, non-zero; running variance in (0.5, 1.5) -- a test must not pass on the identities 0 / 1
             out[name] = (rs_stats.randn(*shape) * 0.1 if name.endswith('_rm') else rs_stats.uniform(0.5, 1.5, shape)).astype(np.float32)
-        elif spec.get('affine') or spec.get('bn'):
+        elif spec.get('affine') or spec.get('bn') or spec.get('gn'):
             if name.endswith('_s'):
                 lo, hi = (0.2, 0.4) if name.endswith(last_bn) else (0.5, 1.0)   # (the (2+1)D bodies: their last affine is `_temporal_bn`)
                 out[name] = rs.uniform(lo, hi, shape).astype(np.float32)

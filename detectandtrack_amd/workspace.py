@@ -35,7 +35,8 @@ class Blob(object):
                                 # the reading conv / RoIAlign address that frame themselves)
         self.t2c = False        # time moved into channels (detector.py:480-491): still stored as T frames of C channels
         self.keyframe = None    # set when only this frame of a T-frame blob was computed (cfg.HIP.KEYFRAME_DCE)
-        self.bn = None          # output of a training-mode SpatialBN: (its input tensor z, fp32 [4, cs] = mean, rstd, a, b') for the backward
+        self.bn = None          # output of a training-mode SpatialBN: (its input tensor z, fp32 [4, cs] = mean, rstd, a, b') for the backward;
+                                # of a GroupNorm: (z, fp32 [4, clips, cs])
 
 
 class Workspace(object):
@@ -229,12 +230,17 @@ def _valid_rows(b, arr):
 
 
 def check_bn_sees_every_frame(net):
-    """A training-mode SpatialBN normalises with the statistics of ALL frames of its input: it cannot run in a forward that computes
-    a subset of the frames."""
-    if (cfg.HIP.KEYFRAME_DCE or int(cfg.HIP.FRAME_TRUNK_CACHE) > 0) and any(op.type == 'SpatialBN' for op in net.ops):
+    """A training-mode SpatialBN normalises with the statistics of ALL frames of its input, a GroupNorm (training and test nets alike)
+    with those of all frames of the clip: neither can run in a forward that computes a subset of the frames."""
+    if not (cfg.HIP.KEYFRAME_DCE or int(cfg.HIP.FRAME_TRUNK_CACHE) > 0):
+        return
+    if any(op.type == 'SpatialBN' for op in net.ops):
         raise ValueError('net %r holds training-mode SpatialBN ops (MODEL.USE_BN), whose batch statistics need every frame of their '
                          'input: not combinable with HIP.KEYFRAME_DCE / HIP.FRAME_TRUNK_CACHE, which compute a subset of the frames'
                          % (net.name,))
+    if any(op.type == 'GroupNorm' for op in net.ops):
+        raise ValueError('net %r holds GroupNorm ops (HIP.USE_GN), whose statistics need every frame of the clip: not combinable with '
+                         'HIP.KEYFRAME_DCE / HIP.FRAME_TRUNK_CACHE, which compute a subset of the frames' % (net.name,))
 
 
 def _mode(ws=None):
@@ -679,6 +685,22 @@ class Executor(object):
                           ws.dev_param(a['rm']), ws.dev_param(a['riv']))
         res = ws.blobs[a['residual']].t if a['residual'] else None
         y = ops.bn_apply(x.t, x.dt, x.C, st[2], st[3], relu=a['relu'], residual=res)
+        b = Blob(y, 'fmap', x.N, x.T, x.C, x.dt, x.five_d)
+        b.bn = (x.t, st)
+        ws.blobs[op.outputs[0]] = b
+
+    def op_GroupNorm(self, i, op):
+        """GroupNorm (+ fused residual / ReLU), the same in training and inference: one statistics pass per clip (x.N clips per forward),
+        then one normalise pass.  Nothing synchronises, so the op is captured into a clip graph like a conv.  The output keeps
+        (z, mean / rstd / a / b') for the backward."""
+        ws, a = self.ws, op.args
+        x = ws.blobs[op.inputs[0]]
+        assert x.kind == 'fmap' and x.keyframe is None and x.tsel is None and not x.t2c, (op, x.kind)
+        assert x.count is None, 'GroupNorm over a row-counted blob (per-RoI head) is not supported'
+        assert x.t.shape[0] == x.N * x.T, (op, tuple(x.t.shape), x.N, x.T)
+        st = ops.gn_stats(x.t, x.dt, x.C, a['groups'], ws.dev_param(a['scale']), ws.dev_param(a['bias']), a['eps'], clips=x.N)
+        res = ws.blobs[a['residual']].t if a['residual'] else None
+        y = ops.gn_apply(x.t, x.dt, x.C, st[2], st[3], clips=x.N, relu=a['relu'], residual=res)
         b = Blob(y, 'fmap', x.N, x.T, x.C, x.dt, x.five_d)
         b.bn = (x.t, st)
         ws.blobs[op.outputs[0]] = b

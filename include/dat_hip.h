@@ -578,6 +578,39 @@ int dat_bn_bwd_reduce(dat_ctx* ctx, dat_stream s, int dtype, const void* dy, con
 int dat_bn_bwd_apply(dat_ctx* ctx, dat_stream s, int dtype, const void* g, const void* z, void* dz, const float* mean, const float* rstd,
                      const float* a, const float* sums, long long rows, long long row_lo, long long nrows, int C, int cstride);
 
+/* ---- GroupNorm (HIP.USE_GN) ---------------------------------------------------------------------------
+ * torch.nn.functional.group_norm on NDHWC blobs [clips][rows][cstride] (rows = T*H*W positions of ONE clip): the C real channels form
+ * `groups` groups of cg = C / groups consecutive channels (any cg); mean and the biased variance of (clip, group) are taken over the
+ * clip's rows x the group's cg channels.  No running statistics: the same function in training and at test time.  Tensor formats,
+ * padding channels, alignment and determinism as for SpatialBN above; in addition the results of a clip depend on that clip's rows
+ * only and not on `clips` (bit for bit what the clip gives in a call of its own).  Tables mean / rstd / a / bprime: fp32
+ * [clips][cstride];  sums / coef: fp32 [clips][2][cstride];  scale / bias / dbeta / dgamma: C floats.
+ * `ws`: caller-owned scratch of dat_gn_workspace_bytes(dtype, clips, rows, cstride) bytes, enough for every call below on that blob
+ * (0: bad shape); nothing allocates or synchronises, so every call can be captured into a hipGraph. */
+size_t dat_gn_workspace_bytes(int dtype, int clips, long long rows, int cstride);
+/* Per (clip, channel) (count, mean, M2) partials of z minus the clip's first row (Welford / Chan, never E[x^2] - mean^2), merged over the blocks and then over the cg
+ * channels of each group in fixed orders; then per channel  mean, rstd = 1 / sqrt(M2 / (rows * cg) + eps)  (equal within a group),
+ * a = scale * rstd,  bprime = bias - mean * a.  rows * cg < 2 is DAT_ERR_ARG. */
+int dat_gn_stats(dat_ctx* ctx, dat_stream s, int dtype, const void* z, int clips, long long rows, int C, int cstride, int groups,
+                 const float* scale, const float* bias, float eps, float* mean, float* rstd, float* a, float* bprime, void* ws,
+                 size_t ws_bytes);
+/* y = act(z * a[clip][c] + bprime[clip][c] (+ residual)), act = ReLU when relu.  y may alias z and / or residual (NULL: none). */
+int dat_gn_apply(dat_ctx* ctx, dat_stream s, int dtype, const void* z, const void* residual, void* y, const float* a, const float* bprime,
+                 int clips, long long rows, int C, int cstride, int relu);
+/* dy, g: the rows [row_lo, row_lo + nrows) of every clip -- all rows of clips >= 1 clips, or a frame window of ONE clip; any other
+ * shape is DAT_ERR_ARG and launches nothing.  y (the op's output; NULL without relu) and z: the WHOLE blob.  g = dy * [y > 0] (g may
+ * alias dy);  sums[clip][0][c] = sum g,  sums[clip][1][c] = sum g * xhat over the clip's window, xhat = (z - mean) * rstd;
+ * dbeta[c] += sum over the clips of sums[clip][0][c],  dgamma[c] += ... sums[clip][1][c]  (either may be NULL);  coef: what
+ * dat_gn_bwd_apply reads, per channel of group g with A = sum_{c in g} scale[c] sums[clip][0][c], B = ... sums[clip][1][c] and
+ * Mg = rows * cg:  coef[clip][0][c] = -rstd * A / Mg,  coef[clip][1][c] = -rstd^2 * B / Mg. */
+int dat_gn_bwd_reduce(dat_ctx* ctx, dat_stream s, int dtype, const void* dy, const void* y, const void* z, void* g, const float* mean,
+                      const float* rstd, const float* scale, int clips, long long rows, long long row_lo, long long nrows, int C,
+                      int cstride, int groups, int relu, float* sums, float* coef, float* dbeta, float* dgamma, void* ws, size_t ws_bytes);
+/* dz = a * g + coef[clip][0] + coef[clip][1] * (z - mean)  ( = rstd * (scale * g - A / Mg - xhat * B / Mg) ) for EVERY row of every
+ * clip; g (rows [row_lo, row_lo + nrows), shapes as above) counts as zero outside its window -- dz does not vanish there. */
+int dat_gn_bwd_apply(dat_ctx* ctx, dat_stream s, int dtype, const void* g, const void* z, void* dz, const float* mean, const float* a,
+                     const float* coef, int clips, long long rows, long long row_lo, long long nrows, int C, int cstride);
+
 /* ---- training input pipeline: RPN anchor labelling, device half -------------------------------------
  * Replaces the O(anchors x gts) part of reference lib/roi_data/rpn.py:283-312: the straddle filter (:283-291), the Cython
  * IoU lib/utils/cython_bbox.pyx:16-57 averaged over the tube's frames (lib/utils/boxes.py:60-69), anchor->gt max / first
