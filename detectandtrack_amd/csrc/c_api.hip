@@ -69,6 +69,7 @@ int dat_ctx_create(dat_ctx** out, int device) {
         c->dbg_persist_pct = env_int("DAT_PERSIST_PCT", 100);
         c->dbg_bt_min = env_int("DAT_CONV_BT_MIN", 390);   // smallest grid of the big-tile kernel, in hundredths of a round of the CUs
         c->dbg_bt = env_int("DAT_CONV_BT", 1);   // round 6: on for grids of >= 3.9 even rounds (FPN P2 output conv, conv_rpn_fpn2): +1.3 % on the R-18 forward, same box
+        c->dbg_mfma = env_int("DAT_CONV_MFMA", 1) == 1;   // MFMA shape of the two dominant 3x3 kernels: 0 = 32x32x16, 1 = 16x16x32 (default: +4.6 % on the R-18 forward, same box, every run of three pairs: DESIGN.md section 3.1)
         c->dbg_roi_fold = env_int("DAT_ROI_BWD_FOLD", 1);
         c->dbg_ws_poison = env_int("DAT_WS_POISON", 0);
         c->num_cu = 0;

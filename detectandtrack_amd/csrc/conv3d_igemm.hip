@@ -57,9 +57,16 @@ template <int BP, int NTAP> struct MinWaves { static constexpr int value = (NTAP
 // epilogue's element type know about it.
 //
 // ONE is always 1: it keeps the kernel names' template-argument layout, which bench.py's _short_kernel parses (fifth argument).
-template <int DT, int BN, int BP, int WAVES_N, int ONE, int NTAP, int ODT>
+//
+// MF = 1 (DAT_CONV_MFMA=1; the bf16 128-channel dense 3x3 variants only, always together with the big-tile kernel, which is held bit for bit
+// against them): v_mfma_f32_16x16x32 on the same wave tile.  The wave's 64 channels are four 16-row blocks, its positions 16-position groups
+// (the same positions in the same order); a tap is two K = 32 slices, each A fragment a lane gather from two neighbouring 1-KiB fragments
+// of the unchanged packed weights, each B fragment logical slot 4 s + (lane >> 4) of patch row (lane & 15) (patch_swz<1>).  The loop keeps
+// its four units per tap with PT fragment reads each: a unit is half of a K32 slice (the first / second half of the position groups).
+template <int DT, int BN, int BP, int WAVES_N, int ONE, int NTAP, int ODT, int MF = 0>
 __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_igemm_kernel(const ConvParams p) {
     static_assert(ONE == 1, "see the comment above");
+    static_assert(!MF || (DT == DAT_BF16 && ODT == DAT_BF16 && BN == 128 && NTAP == 9), "the 16x16x32 shape exists for the bf16 128-channel dense 3x3 variants");
     constexpr int ES = ElemOf<DT>::size;
     constexpr int OES = ElemOf<ODT>::size;
     constexpr int CK = Mma<DT>::CK;
@@ -69,6 +76,8 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
     constexpr int MT = WN / 32;
     constexpr int PT = WP / 32;
     static_assert(MT >= 1 && PT >= 1, "tile too small");
+    constexpr int MTX = MF ? 2 * MT : MT, PTX = MF ? 2 * PT : PT;   // accumulator tiles: 32 x 32 (16 registers) / 16 x 16 (4 registers)
+    typedef std::conditional_t<MF != 0, f32x4_t, f32x16_t> acc_t;
 
 #ifdef DAT_CONV_TRACE
     const unsigned long long tr_k0 = __builtin_amdgcn_s_memtime();
@@ -121,22 +130,22 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
     const int iw0 = ow0 * p.sw - p.pw;
 
     // per-lane patch row of each position sub-tile (tap offset added per tap)
-    int rowbase[PT];
+    int rowbase[PTX];
 #pragma unroll
-    for (int j = 0; j < PT; ++j) {
-        const int pos = wave_p * WP + j * 32 + (lane & 31);
+    for (int j = 0; j < PTX; ++j) {
+        const int pos = wave_p * WP + (MF ? j * 16 + (lane & 15) : j * 32 + (lane & 31));
         const int ohl = pos >> p.tw_log2, owl = pos & (TW - 1);
         rowbase[j] = ohl * p.rsh * p.PW + owl * p.rsw;
     }
     const int khalf = lane >> 5;
 
-    f32x16_t acc[MT][PT];
+    acc_t acc[MTX][PTX];
 #pragma unroll
-    for (int i = 0; i < MT; ++i)
+    for (int i = 0; i < MTX; ++i)
 #pragma unroll
-        for (int j = 0; j < PT; ++j)
+        for (int j = 0; j < PTX; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+            for (int r = 0; r < (MF ? 4 : 16); ++r) acc[i][j][r] = 0.f;
 
     // valid temporal taps for this output frame
     int kt_lo = 0, kt_hi = p.KT - 1;
@@ -179,22 +188,21 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
         // row * 128 + ((khalf ^ (g & 1)) << 4) + (((g >> 1) ^ ks) << 5), g = (row >> 1) & 7 -- bits 5-6 of the first two terms are 0
         // (a patch is < 64 KiB: two 16-bit addresses per register -- NTAP x PT / 2 registers instead of NTAP x PT)
         constexpr bool PACK16 = NTAP != 10;                    // (the dense stride-2 patch is 70 KiB: one address per register there)
-        constexpr int NQ = PACK16 ? (PT + 1) / 2 : PT;
+        constexpr int NQ = PACK16 ? (PTX + 1) / 2 : PTX;
         unsigned qp[NT][NQ];
 #pragma unroll
         for (int tp = 0; tp < NT; ++tp)
 #pragma unroll
-            for (int j = 0; j < PT; ++j) {
+            for (int j = 0; j < PTX; ++j) {
                 int row = rowbase[j] + p.tab_rowoff[tp];
                 if (p.lin_w > 0) {   // linear tiling: a tap that leaves the lane's map (row / column / map border) reads the zero row
-                    const int gpos = ow0 + wave_p * WP + j * 32 + (lane & 31);
+                    const int gpos = ow0 + wave_p * WP + (MF ? j * 16 + (lane & 15) : j * 32 + (lane & 31));
                     const int rem = gpos % (p.lin_h * p.lin_w);
                     const int y = rem / p.lin_w, x = rem - y * p.lin_w;
                     const int yy = y + tp / p.KW - p.KH / 2, xx = x + tp % p.KW - p.KW / 2;
                     if ((unsigned)yy >= (unsigned)p.lin_h || (unsigned)xx >= (unsigned)p.lin_w) row = p.lin_zero_row;
                 }
-                const int g = (row >> 1) & 7;
-                const unsigned a16 = (unsigned)(row * PPITCH) + (unsigned)(((khalf ^ (g & 1)) << 4) | ((g >> 1) << 5));
+                const unsigned a16 = patch_frag_addr<MF>(row, MF ? lane >> 4 : khalf);
                 if (!PACK16) qp[tp][j] = a16;
                 else if (j & 1) qp[tp][j >> 1] |= a16 << 16;
                 else qp[tp][j >> 1] = a16;
@@ -209,7 +217,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
             int off = -2;                                      // -2: no such piece / item
             if (c < nchunks && it < npatch_items) {
                 const int row = it >> 3;
-                const int slot = (it ^ (row >> 1)) & 7;
+                const int slot = patch_src_slot<MF>(it);
                 const int prow = p.pw_magic ? (int)__umulhi((unsigned)row, p.pw_magic) : row, pcol = row - prow * p.PW;
                 const int ih = ih0 + p.tab_dy[0] + prow * p.psh, iw = iw0 + p.tab_dx[0] + pcol * p.psw;
                 off = (ih >= 0 && ih < p.H && iw >= 0 && iw < p.W && row != p.lin_zero_row) ? (int)((unsigned)(ih * p.W + iw) * (unsigned)(p.Cin * ES) + (unsigned)(slot * 16)) : -1;
@@ -221,13 +229,17 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
         //  no per-lane 64-bit pointer arithmetic and no pointer registers per tap)
         const size_t tap_stride = (size_t)p.n_cchunks * wd_cc_stride;
         const char* const wd_base = p.w + (size_t)((n0 + wave_n * WN) >> 5) * 4096;       // uniform
-        const unsigned lane16 = (unsigned)lane * 16u;
+        // (MF = 1: 16-row block i, K32 slice s = lane l's 16 bytes at 16 * (((i & 1) << 4) + (l & 15) + 32 * (kg & 1)) of the 1-KiB fragment of
+        //  32-row block i >> 1, k-slice 2 s + (kg >> 1), kg = l >> 4: the lane part in one register, the rest in the immediate)
+        constexpr int NKS = MF ? 2 : 4;                        // k-slices per tap
+        const unsigned lane16 = MF ? 16u * (((unsigned)lane & 15u) + 32u * (((unsigned)lane >> 4) & 1u)) + ((unsigned)lane >> 5) * 1024u : (unsigned)lane * 16u;
+#define W_OFF(I_, KS_) (MF ? ((I_) & 1) * 256 + ((I_) >> 1) * 4096 + (KS_) * 2048 : (I_) * 4096 + (KS_) * 1024)
         const char* wcur = wd_base + ((size_t)(kt * ntap) * p.n_cchunks + cc) * wd_cc_stride;
-        uint4 wa[MT][4];
+        uint4 wa[MTX][NKS];
 #pragma unroll
-        for (int i = 0; i < MT; ++i)
+        for (int i = 0; i < MTX; ++i)
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) wa[i][ks] = *(const uint4*)(wcur + i * 4096 + ks * 1024 + lane16);
+            for (int ks = 0; ks < NKS; ++ks) wa[i][ks] = *(const uint4*)(wcur + W_OFF(i, ks) + lane16);
         const int npat = pi_hi - pi_lo;
         for (int pi = 0; pi < npat; ++pi) {
             // (bf16x3: chunk 3q + 1 reads the SAME source line as chunk 3q -- x_hi against W_lo after x_hi against W_hi -- so the patch
@@ -238,8 +250,12 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
                 const char* xbase = p.x + ((size_t)fin * p.H * p.W) * p.Cin * ES + (size_t)(p.x3 ? (cc / 3) * 2 + (cc % 3 == 2) : cc) * CK * ES;
 #pragma unroll
                 for (int u = 0; u < MAXCH; ++u) {
-                    if (poff[u] != -2) {
-                        const char* src = poff[u] >= 0 ? xbase + (unsigned)poff[u] : p.zeros;
+                    int po = poff[u];
+                    // (the 16x16x32 variants have no register to spare: opaque here, or the compiler keeps every offset as a zero-extended
+                    //  64-bit pair, and its two compares as lane masks, across the patch loop)
+                    if constexpr (MF != 0) asm volatile("" : "+v"(po));
+                    if (po != -2) {
+                        const char* src = po >= 0 ? xbase + (unsigned)po : p.zeros;
                         P_DMA(src, patch + (wave + 4 * u) * 1024);
                     }
                 }
@@ -253,46 +269,64 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
             __builtin_amdgcn_s_setprio(1);
             // (the empty asm makes the packed addresses opaque per tap: without it the compiler hoists all NTAP x PT x 4 unpacked and
             //  xor-ed addresses out of the patch loop as loop invariants -- 144 registers, spilled to scratch)
-            uint4 b[2][PT];
-            unsigned qa[PT];
+            // A unit is BF fragment reads + the MFMAs they feed, its reads issued one unit ahead (two register buffers).  MF = 0: a unit is a
+            // k-slice (all PT sub-tiles).  MF = 1: a K32 slice has 2 PT position groups; a unit takes BF of them (PT at 128 positions; 2 at 256,
+            // where a buffer of four 16-byte fragments more than the 32x32x16 variant holds would not fit 256 registers), and the group
+            // addresses are unpacked per unit instead of per tap
+            constexpr int BF = MF ? (PT >= 4 ? 2 : PT) : PT;       // fragments per unit
+            constexpr int UPS = PTX / BF, NU = NKS * UPS;          // units per k-slice, per tap
+            uint4 b[2][BF];
+            unsigned qa[MF ? 1 : PT];
+            // address (k-slice 0) of position sub-tile / group j of tap tp_
+#define Q_ADDR(TP_, J_) (!PACK16 ? qp[TP_][(J_) % NQ] : ((J_) & 1) ? (qp[TP_][((J_) >> 1) % NQ] >> 16) : (qp[TP_][((J_) >> 1) % NQ] & 0xffffu))
 #pragma unroll
             for (int jj = 0; jj < NQ; ++jj) asm volatile("" : "+v"(qp[0][jj]));
+            if constexpr (!MF) {
 #pragma unroll
-            for (int j = 0; j < PT; ++j) qa[j] = !PACK16 ? qp[0][j % NQ] : (j & 1) ? (qp[0][(j >> 1) % NQ] >> 16) : (qp[0][(j >> 1) % NQ] & 0xffffu);
+                for (int j = 0; j < PT; ++j) qa[j] = Q_ADDR(0, j);
+            }
 #pragma unroll
-            for (int j = 0; j < PT; ++j) b[0][j] = *(const uint4*)(patch + qa[j]);
+            for (int j = 0; j < BF; ++j) b[0][j] = *(const uint4*)(patch + (MF ? Q_ADDR(0, j) : qa[j % (MF ? 1 : PT)]));
 #pragma unroll
             for (int tp = 0; tp < NT; ++tp) {
                 const char* wnext = (tp + 1 < NT) ? wcur + (size_t)(tp + 1) * tap_stride : wnextpatch;
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const int cur = ks & 1, nxt = cur ^ 1;
-                    if (ks < 3) {
+                for (int u = 0; u < NU; ++u) {
+                    const int cur = u & 1, nxt = cur ^ 1;
+                    const int ks = u / UPS, jb = (u % UPS) * BF;
+                    if (u + 1 < NU) {
+                        const int nks = (u + 1) / UPS, njb = ((u + 1) % UPS) * BF;
 #pragma unroll
-                        for (int j = 0; j < PT; ++j) b[nxt][j] = *(const uint4*)(patch + (qa[j] ^ (unsigned)((ks + 1) << 5)));
+                        for (int j = 0; j < BF; ++j)
+                            b[nxt][j] = *(const uint4*)(patch + ((MF ? Q_ADDR(tp, njb + j) : qa[j % (MF ? 1 : PT)]) ^ (unsigned)(nks << (MF ? 6 : 5))));
                     } else if (tp + 1 < NT) {
-                        // the first fragments of the NEXT tap, behind this tap's last k-slice: no tap opens with an exposed LDS round trip
+                        // the first fragments of the NEXT tap, behind this tap's last unit: no tap opens with an exposed LDS round trip
 #pragma unroll
                         for (int jj = 0; jj < NQ; ++jj) asm volatile("" : "+v"(qp[tp + 1 < NT ? tp + 1 : tp][jj]));
+                        if constexpr (!MF) {
 #pragma unroll
-                        for (int j = 0; j < PT; ++j) {
-                            const unsigned w2 = qp[tp + 1 < NT ? tp + 1 : tp][(PACK16 ? j >> 1 : j) % NQ];
-                            qa[j] = !PACK16 ? w2 : (j & 1) ? (w2 >> 16) : (w2 & 0xffffu);
+                            for (int j = 0; j < PT; ++j) qa[j] = Q_ADDR(tp + 1 < NT ? tp + 1 : tp, j);
                         }
 #pragma unroll
-                        for (int j = 0; j < PT; ++j) b[nxt][j] = *(const uint4*)(patch + qa[j]);
+                        for (int j = 0; j < BF; ++j) b[nxt][j] = *(const uint4*)(patch + (MF ? Q_ADDR(tp + 1 < NT ? tp + 1 : tp, j) : qa[j % (MF ? 1 : PT)]));
                     }
 #pragma unroll
-                    for (int i = 0; i < MT; ++i)
+                    for (int i = 0; i < MTX; ++i)
 #pragma unroll
-                        for (int j = 0; j < PT; ++j) Mma<DT>::step(wa[i][ks], b[cur][j], acc[i][j]);
+                        for (int j = 0; j < BF; ++j) {
+                            if constexpr (MF) acc[i][jb + j] = DAT_MFMA16K32(wa[i][ks], b[cur][j], acc[i][jb + j]);
+                            else Mma<DT>::step(wa[i][ks], b[cur][j], acc[i][j]);
+                        }
+                    if ((u + 1) % UPS == 0) {      // the k-slice's last unit
 #pragma unroll
-                    for (int i = 0; i < MT; ++i) wa[i][ks] = *(const uint4*)(wnext + i * 4096 + ks * 1024 + lane16);   // a whole tap to land
+                        for (int i = 0; i < MTX; ++i) wa[i][ks] = *(const uint4*)(wnext + W_OFF(i, ks) + lane16);   // a whole tap to land
+                    }
                     // keep this k-slice's reloads HERE: left alone, the scheduler sinks all eight loads of a tap behind its last MFMA and
                     // the next tap's first MFMA then waits out a full L2 round trip
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
+#undef Q_ADDR
             __builtin_amdgcn_s_setprio(0);
             wcur = wnextpatch;
             cc = ncc; kt = nkt;
@@ -300,6 +334,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
       }
     } else
     if (total > 0) {
+        static_assert(!MF, "the table-driven loop runs 32x32x16 only");
         // temporal taps are visited in order of the INPUT frame index mod KT, not of kt: the blocks of output frames
         // t-1, t, t+1 (queue neighbours on one XCD) then stage the same input frame during the same third of their
         // lifetime, so the temporal re-reads hit that XCD's L2 instead of going back to the fabric
@@ -418,6 +453,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
         tr_k1 = __builtin_amdgcn_s_memtime();
 #endif
     }
+#undef W_OFF
 #undef WD_PTR
 #undef P_COMMIT
 #undef P_DMA
@@ -479,12 +515,19 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
     for (int j = 0; j < PT; ++j) {
         if (res_pre && j + 1 < PT) res_fetch(j + 1, rq[(j + 1) & 1]);
         // phase 1: accumulators -> LDS [position][channel] fp32
+        if constexpr (MF) {
 #pragma unroll
-        for (int i = 0; i < MT; ++i)
+            for (int i = 0; i < MTX; ++i)
 #pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *(float4*)(est + (lane & 31) * EPI_PITCH + (i * 32 + g * 8 + khalf * 4) * 4) =
-                    make_float4(acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1], acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
+                for (int jl = 0; jl < 2; ++jl) epi_stage16(est, lane, i, jl, acc[i][(2 * j + jl) % PTX]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *(float4*)(est + (lane & 31) * EPI_PITCH + (i * 32 + g * 8 + khalf * 4) * 4) =
+                        make_float4(acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1], acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
+        }
         __builtin_amdgcn_wave_barrier();
         // phase 2: position-major read back, fused epilogue, 16-byte stores
 #pragma unroll
@@ -744,7 +787,7 @@ int conv_set_frame_window(dat_ctx* ctx, const dat_conv_desc* d, ConvParams& p, c
 
 namespace {
 
-template <int DT, int BN, int BP, int WAVES_N, int NTAP, int ODT>
+template <int DT, int BN, int BP, int WAVES_N, int NTAP, int ODT, int MF = 0>
 int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ksplit, bool linear = false) {
     TileChoice tc = choose_tile(p.Ho, p.Wo, bp_log2, p.sh, p.sw, p.KH, p.KW);
     p.lin_h = p.lin_w = 0;
@@ -843,7 +886,7 @@ int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ks
     if (lds < EPI_SLICES_BYTES) lds = EPI_SLICES_BYTES;                     // epilogue staging slices
     DAT_ENFORCE(ctx, lds <= 160 * 1024, "conv3d: LDS patch of %zu bytes exceeds 160 KiB (tile %dx%d, stride %dx%d)", lds,
                 th, tw, p.sh, p.sw);
-    auto kern = conv3d_igemm_kernel<DT, BN, BP, WAVES_N, 1, NTAP, ODT>;
+    auto kern = conv3d_igemm_kernel<DT, BN, BP, WAVES_N, 1, NTAP, ODT, MF>;
     if (NTAP > 0) {   // what the unrolled variant assumes (the dispatcher only picks it for these shapes)
         DAT_ENFORCE(ctx, p.tab_n == (NTAP == 10 ? 9 : NTAP) && p.tab_new == 1u &&
                              (((size_t)p.PH * p.PW * 8 + 63) >> 6) <= (size_t)4 * patch_pieces_per_wave(NTAP, BP) && (NTAP == 10 || (size_t)p.PH * p.PW * PPITCH < 65536),
@@ -1069,7 +1112,10 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
 #define DAT_CONV_LAUNCH(DT_, BN_, WN_, ODT_) (ntapv == 10 ? launch_conv<DT_, BN_, 128, WN_, 10, ODT_>(ctx, st, p, 7, ksplit) : ntapv == 9 ? (big ? launch_conv<DT_, BN_, 256, WN_, 9, ODT_>(ctx, st, p, 8, ksplit, lin) : launch_conv<DT_, BN_, 128, WN_, 9, ODT_>(ctx, st, p, 7, ksplit, lin)) \
                             : ntapv == 1 ? (big ? launch_conv<DT_, BN_, 256, WN_, 1, ODT_>(ctx, st, p, 8, ksplit) : launch_conv<DT_, BN_, 128, WN_, 1, ODT_>(ctx, st, p, 7, ksplit)) \
                             : (big ? launch_conv<DT_, BN_, 256, WN_, 0, ODT_>(ctx, st, p, 8, ksplit) : launch_conv<DT_, BN_, 128, WN_, 0, ODT_>(ctx, st, p, 7, ksplit)))
-        if (x3) rc = small_n ? DAT_CONV_LAUNCH(DAT_BF16, 64, 1, DAT_F32) : DAT_CONV_LAUNCH(DAT_BF16, 128, 2, DAT_F32);
+        // DAT_CONV_MFMA=1: the bf16 128-channel dense 3x3 variants (2-D tiles, linear strips, split-K) on 16x16x32, like the big-tile kernel
+        if (ctx->dbg_mfma && ntapv == 9 && !x3 && !small_n && d->dtype == DAT_BF16)
+            rc = big ? launch_conv<DAT_BF16, 128, 256, 2, 9, DAT_BF16, 1>(ctx, st, p, 8, ksplit, lin) : launch_conv<DAT_BF16, 128, 128, 2, 9, DAT_BF16, 1>(ctx, st, p, 7, ksplit, lin);
+        else if (x3) rc = small_n ? DAT_CONV_LAUNCH(DAT_BF16, 64, 1, DAT_F32) : DAT_CONV_LAUNCH(DAT_BF16, 128, 2, DAT_F32);
         else if (small_n) rc = d->dtype == DAT_BF16 ? DAT_CONV_LAUNCH(DAT_BF16, 64, 1, DAT_BF16) : DAT_CONV_LAUNCH(DAT_F32, 64, 1, DAT_F32);
         else rc = d->dtype == DAT_BF16 ? DAT_CONV_LAUNCH(DAT_BF16, 128, 2, DAT_BF16) : DAT_CONV_LAUNCH(DAT_F32, 128, 2, DAT_F32);
 #undef DAT_CONV_LAUNCH

@@ -8,7 +8,8 @@
 // (row pitch = channels * 4 + 16 B: conflict-free b128 writes) and reads it back position-major, 16 B of output per lane, so one store
 // instruction covers whole channel runs.  A kernel supplies what differs: its position decode, how it prefetches the residual rows,
 // its scale / bias convention for channels past Cout, and any split-K partial path.  The helpers are the steps in between, in the
-// order every kernel applies them: epi_stage, (wave barrier), epi_load, epi_affine, epi_residual | epi_residual4, epi_relu, epi_store.
+// order every kernel applies them: epi_stage | epi_stage16 (the accumulator layout of the 16x16x32 MFMA shape), (wave barrier), epi_load,
+// epi_affine, epi_residual | epi_residual4, epi_relu, epi_store.
 #ifndef DAT_CONV_EPILOGUE_H
 #define DAT_CONV_EPILOGUE_H
 
@@ -31,6 +32,14 @@ __device__ __forceinline__ void epi_stage(char* est, int row, int khalf, int i, 
 #pragma unroll
     for (int g = 0; g < 4; ++g)
         *(float4*)(est + row * PITCH + (i * 32 + g * 8 + khalf * 4) * 4) = make_float4(acc[g * 4 + 0], acc[g * 4 + 1], acc[g * 4 + 2], acc[g * 4 + 3]);
+}
+
+// the same staging step for the 16x16x32 MFMA shape, whose accumulator tile holds column (position) lane & 15 and rows (channels)
+// (lane >> 4) * 4 + register: 16-row block i16 of the 64 channels, 16-position half jl of the 32-position group -> the same LDS image,
+// so everything after the transpose is shared
+template <int PITCH = EPI_PITCH>
+__device__ __forceinline__ void epi_stage16(char* est, int lane, int i16, int jl, const f32x4_t& acc) {
+    *(float4*)(est + (jl * 16 + (lane & 15)) * PITCH + (i16 * 16 + (lane >> 4) * 4) * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
 }
 
 // position-major read back: CPL channels from channel sl_c of position pl

@@ -105,6 +105,25 @@ __device__ __forceinline__ float res_combine4(float v, float old, float m) { ret
 
 namespace dat_conv __attribute__((visibility("hidden"))) {
 
+// XOR swizzle of a patch row's eight 16-byte slots (applied on the source side of the LDS-DMA, undone by the B-fragment reads), by MFMA
+// shape.  MF = 0 (32x32x16: a 16-lane read group takes 8 + 8 consecutive rows, one k-half): (row >> 1) & 7.  MF = 1 (16x16x32: a read group
+// takes 16 consecutive rows, rows 4-11 from the neighbouring k-group of rows 0-3 / 12-15): no XOR of whole slots is conflict-free for every
+// first row, so 32-byte slot pairs move by (row >> 1) & 3 and the rows 8 apart that share a pair read its two different halves
+// (tests/test_conv_mfma16_cpu.py enumerates the banks).
+template <int MF>
+__device__ __forceinline__ int patch_swz(int row) { return MF ? ((row >> 1) & 3) << 1 : (row >> 1) & 7; }
+// the logical slot the LDS-DMA lane of patch item `it` (row it >> 3, physical slot it & 7) fetches
+template <int MF>
+__device__ __forceinline__ int patch_src_slot(int it) { const int row = it >> 3; return MF ? (it & 7) ^ patch_swz<1>(row) : (it ^ (row >> 1)) & 7; }
+// byte address inside the patch of a lane's B fragment of the first k-slice: k-group kg (lane >> 5 of 2 / lane >> 4 of 4) of patch row `row`;
+// the later slices are `^ (ks << 5)` (MF = 0, K = 16 each) / `^ (s << 6)` (MF = 1, K = 32 each)
+template <int MF>
+__device__ __forceinline__ unsigned patch_frag_addr(int row, int kg) {
+    if (MF) return (unsigned)(row * PPITCH) + (unsigned)((kg ^ patch_swz<1>(row)) << 4);
+    const int g = (row >> 1) & 7;
+    return (unsigned)(row * PPITCH) + (unsigned)(((kg ^ (g & 1)) << 4) | ((g >> 1) << 5));
+}
+
 // compile-time index sequence for the hand-scheduled loops (`#pragma unroll` is refused for bodies of this size, and immediates /
 // register-ring slots need constant indices)
 template <int... I, class F>

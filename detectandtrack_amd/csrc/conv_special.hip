@@ -891,11 +891,21 @@ __global__ __launch_bounds__(KS_THREADS) void conv_kt1x1_ks_kernel(const TkParam
 //     starts (36 k-slices = 18 k cycles earlier); one barrier per patch.  Every wave issues the same number of DMA pieces (the
 //     tail re-fetches the last piece), so that the vmcnt arithmetic is the same in all waves.
 // The launcher uses it for 256-channel-multiple layers whose grid fills the chip at least ~2 times (FPN P2 / P3 outputs).
-template <int TWL, int R>
+//
+// MF = 1 (DAT_CONV_MFMA=1): the same wave tile on v_mfma_f32_16x16x32 -- 8 x 8 accumulator tiles of 4 registers, the same 256 AGPRs.  A step
+// is one K = 32 slice of a tap: 8 A fragments, 8 B fragments, 64 MFMAs (the same 1024 matrix cycles as two K = 16 steps), 18 steps per patch.
+// The packed weights are untouched: the A fragment of 16-row block r16 and K32 slice s is a lane gather from two neighbouring 1-KiB
+// fragments of the 32x32x16 order (lane l = row l & 15, k-group l >> 4: 16 bytes at 16 * (((r16 & 1) << 4) + (l & 15) + 32 * (kg & 1)) of the
+// fragment of block r16 >> 1, k-slice 2 s + (kg >> 1); a load still reads four whole 256-byte runs); the weight ring holds R steps of 8
+// loads.  The B fragments (lane = position l & 15, logical slot 4 s + (l >> 4) of the patch row, patch_swz<1>) are read HALF a step ahead,
+// four at a time, so that the read ring stays at 2 x 4 fragments: a half step is 8 x 4 MFMAs on four position groups.
+template <int TWL, int R, int MF>
 __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv3x3_bt_kernel(const ConvParams p) {
     constexpr int TW = 1 << TWL, TH = 256 >> TWL, PW = TW + 2, PH = TH + 2;
     constexpr int NPIX = PH * PW, NPIECE = (NPIX * 8 + 63) / 64, PBYTES = NPIECE * 1024, UMAX = (NPIECE + 3) / 4;
-    static_assert(36 % R == 0 && PBYTES < 65536, "ring slots are static per unrolled step; 16-bit patch addresses");
+    constexpr int NSTEP = MF ? 18 : 36, APS = MF ? 8 : 4;      // steps per patch, A fragments (weight loads) per step
+    static_assert(NSTEP % R == 0 && PBYTES < 65536, "ring slots are static per unrolled step; 16-bit patch addresses");
+    static_assert(APS * R + UMAX < 64, "vmcnt is a 6-bit counter");
     typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
@@ -934,24 +944,33 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 1))
 
     // ---- swizzled LDS address (k-slice 0) of the B fragment of every (tap, position sub-tile j), two per register ----
     // sub-tile j of this wave: 16 x 16 tiles: rows 8*wave_p + 2*j + (n >> 4), column n & 15; 8 x 32 tiles: row 4*wave_p + j, column n
-    unsigned qp[9][2];
+    // (MF = 1: 16-position groups jj, position wave_p * 128 + jj * 16 + (lane & 15) of the tile in row-major order: the same positions)
+    constexpr int NJ = MF ? 8 : 4;
+    unsigned qp[9][NJ / 2];
 #pragma unroll
     for (int tp = 0; tp < 9; ++tp)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int r = TWL == 5 ? 4 * wave_p + j : 8 * wave_p + 2 * j + (n >> 4), c = TWL == 5 ? n : (n & 15);
+        for (int j = 0; j < NJ; ++j) {
+            const int pos = wave_p * 128 + (MF ? j * 16 + (lane & 15) : j * 32 + n);
+            const int r = pos >> TWL, c = pos & (TW - 1);
             const int row = (r + tp / 3) * PW + c + tp % 3;
-            const int g = (row >> 1) & 7;
-            const unsigned a16 = (unsigned)(row * PPITCH) + (unsigned)(((khalf ^ (g & 1)) << 4) | ((g >> 1) << 5));
+            const unsigned a16 = patch_frag_addr<MF>(row, MF ? lane >> 4 : khalf);
             if (j & 1) qp[tp][j >> 1] |= a16 << 16; else qp[tp][j >> 1] = a16;
         }
     // ---- weights: fragment (tap, chunk, 32-row block, k-slice) = 1 KiB at (((tap * ncc + chunk) * MB + block) * 4 + k-slice) * 1024 ----
     const size_t wd_cc_stride = (size_t)(p.Cout_pad >> 5) * 4096;
     const size_t tap_stride = (size_t)p.n_cchunks * wd_cc_stride;
     const char* const wd_base = p.w + (size_t)(nb * 8 + wave_n * 4) * 4096;        // this wave's four 32-row blocks
-    unsigned aoff[4];
+    unsigned aoff[APS];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) aoff[i] = (unsigned)lane * 16u + (unsigned)i * 4096u;
+    for (int i = 0; i < APS; ++i) {
+        if (MF) {       // 16-row block i of the wave's 128 channels, K32 slice 0: the gather described above
+            const unsigned kg = (unsigned)lane >> 4;
+            aoff[i] = 16u * ((unsigned)((i & 1) << 4) + ((unsigned)lane & 15u) + 32u * (kg & 1u)) + (kg >> 1) * 1024u + (unsigned)(i >> 1) * 4096u;
+        } else {
+            aoff[i] = (unsigned)lane * 16u + (unsigned)i * 4096u;
+        }
+    }
 
     // patch (KT_, CC_) of this tile -> LDS buffer B_: every wave issues exactly UMAX pieces (wave, wave + 4, ...; indices past the
     // last piece re-fetch it); lane-linear LDS-DMA image, XOR swizzle on the source side, halo / tail lanes fetch zeros
@@ -962,7 +981,7 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 1))
         _Pragma("unroll") for (int u_ = 0; u_ < UMAX; ++u_) {                                                             \
             const int piece_ = min(wave + 4 * u_, NPIECE - 1);                                                            \
             const int it_ = piece_ * 64 + lane, row_ = it_ >> 3;                                                          \
-            const int slot_ = (it_ ^ (row_ >> 1)) & 7;                                                                    \
+            const int slot_ = patch_src_slot<MF>(it_);                                                                    \
             const int prow_ = row_ / PW, pcol_ = row_ - prow_ * PW;                                                       \
             const int ih_ = oh0 - 1 + prow_, iw_ = ow0 - 1 + pcol_;                                                       \
             const bool ok_ = row_ < NPIX && (unsigned)ih_ < (unsigned)p.H && (unsigned)iw_ < (unsigned)p.W;               \
@@ -971,36 +990,49 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 1))
         }                                                                                                                 \
     }
 #define BT_WPATCH(KT_, CC_) (wd_base + ((size_t)((KT_) * 9) * p.n_cchunks + (CC_)) * wd_cc_stride)
-    // A fragments of step S_ (tap S_ / 4, k-slice S_ % 4) of the patch whose first tap sits at WP_ -> ring slot SLOT_
+    // A fragments of step S_ (tap S_ / SPT, k-slice S_ % SPT) of the patch whose first tap sits at WP_ -> ring slot SLOT_
+    constexpr int SPT = NSTEP / 9;                          // steps per tap: 4 slices of K = 16 / 2 slices of K = 32
 #define BT_ALOAD(WP_, S_, SLOT_)                                                                                          \
     {                                                                                                                     \
-        const char* wt_ = (WP_) + (size_t)((S_) / 4) * tap_stride;                                                        \
-        _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                                  \
-            asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(aq[SLOT_][i_]) : "v"(aoff[i_]), "s"(wt_), "n"(((S_) % 4) * 1024) : "memory"); \
+        const char* wt_ = (WP_) + (size_t)((S_) / SPT) * tap_stride;                                                      \
+        _Pragma("unroll") for (int i_ = 0; i_ < APS; ++i_)                                                                \
+            asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(aq[SLOT_][i_]) : "v"(aoff[i_]), "s"(wt_), "n"(((S_) % SPT) * (4096 / SPT)) : "memory"); \
     }
-    // B fragments of step S_ from buffer offset BOFF_ -> ring slot S_ % 2
-#define BT_BREAD(S_, BOFF_)                                                                                               \
+    // the four B fragments of unit U_ from buffer offset BOFF_ -> ring slot U_ % 2.  A unit is a step (MF = 0: k-slice U_ % 4 of tap U_ / 4,
+    // all four 32-position sub-tiles) or half a step (MF = 1: K32 slice (U_ / 2) % 2 of tap U_ / 4, 16-position groups 4 (U_ % 2) .. + 3)
+#define BT_BREAD(U_, BOFF_)                                                                                               \
     {                                                                                                                     \
-        if ((S_) % 4 == 0) {                                                                                              \
-            unsigned q0_ = qp[(S_) / 4][0], q1_ = qp[(S_) / 4][1];                                                        \
+        if ((U_) % 4 == 0) {                                                                                              \
+            unsigned q0_ = qp[(U_) / 4][0], q1_ = qp[(U_) / 4][1], q2_ = qp[(U_) / 4][NJ / 2 - 2], q3_ = qp[(U_) / 4][NJ / 2 - 1]; \
             asm volatile("" : "+v"(q0_), "+v"(q1_));   /* opaque: keeps the unpacked / xor-ed addresses out of registers */ \
             ba[0] = (q0_ & 0xffffu) + (BOFF_); ba[1] = (q0_ >> 16) + (BOFF_);                                             \
             ba[2] = (q1_ & 0xffffu) + (BOFF_); ba[3] = (q1_ >> 16) + (BOFF_);                                             \
+            if constexpr (MF != 0) {                                                                                      \
+                asm volatile("" : "+v"(q2_), "+v"(q3_));                                                                  \
+                ba[NJ - 4] = (q2_ & 0xffffu) + (BOFF_); ba[NJ - 3] = (q2_ >> 16) + (BOFF_);                               \
+                ba[NJ - 2] = (q3_ & 0xffffu) + (BOFF_); ba[NJ - 1] = (q3_ >> 16) + (BOFF_);                               \
+            }                                                                                                             \
         }                                                                                                                 \
         _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                                                  \
-            asm volatile("ds_read_b128 %0, %1" : "=v"(bq[(S_) % 2][j_]) : "v"(ba[j_] ^ (unsigned)(((S_) % 4) << 5)) : "memory"); \
+            asm volatile("ds_read_b128 %0, %1" : "=v"(bq[(U_) % 2][j_])                                                   \
+                         : "v"(ba[(MF ? ((U_) % 2) * 4 : 0) + j_] ^ (unsigned)(MF ? (((U_) / 2) % 2) << 6 : ((U_) % 4) << 5)) : "memory"); \
     }
-#define BT_MFMA(ACC_, A_, B_) asm volatile(DAT_MFMA16_OP " %0, %1, %2, %0" : "+a"(ACC_) : "v"(A_), "v"(B_) : "memory")
+#define BT_MFMA(ACC_, A_, B_)                                                                                             \
+    {                                                                                                                     \
+        if constexpr (MF) asm volatile(DAT_MFMA16K32_OP " %0, %1, %2, %0" : "+a"(ACC_) : "v"(A_), "v"(B_) : "memory");    \
+        else asm volatile(DAT_MFMA16_OP " %0, %1, %2, %0" : "+a"(ACC_) : "v"(A_), "v"(B_) : "memory");                    \
+    }
 
-    f32x16_t acc[4][4];
+    typedef std::conditional_t<MF != 0, f32x4_t, f32x16_t> acc_t;
+    acc_t acc[APS][NJ];                                     // 4 x 4 tiles of 16 registers / 8 x 8 tiles of 4: all 256 AGPRs
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < APS; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < NJ; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    u32x4_t aq[R][4], bq[2][4];
-    unsigned ba[4] = {0, 0, 0, 0};
+            for (int r = 0; r < (MF ? 4 : 16); ++r) acc[i][j][r] = 0.f;
+    u32x4_t aq[R][APS], bq[2][4];
+    unsigned ba[NJ] = {};
 
     if (npat > 0) {
         // ---- prologue: first patch, first R steps of weights ----
@@ -1011,7 +1043,7 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 1))
             (void)&aq; (void)&aoff;                            // (operands of asm statements alone do not capture)
             BT_ALOAD(wcur, s0, s0);
         });
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 * R) : "memory");      // the DMA pieces (older than the R x 4 weight loads)
+        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(APS * R) : "memory");    // the DMA pieces (older than the R x APS weight loads)
         __syncthreads();
         int buf = 0;
         for (int pi = 0; pi < npat; ++pi, buf ^= 1) {
@@ -1024,26 +1056,34 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 1))
             const unsigned boff = (unsigned)buf * PBYTES;
             __builtin_amdgcn_s_setprio(1);
             BT_BREAD(0, boff);
+            // 36 units of four B-fragment reads either way: MF = 0 a unit is a step, MF = 1 half a step (unit 2 st opens step st, unit
+            // 2 st + 1 ends it)
             static_for(std::make_integer_sequence<int, 36>{}, [&](auto ic_) __attribute__((always_inline)) {
-                constexpr int st = decltype(ic_)::value;
+                constexpr int un = decltype(ic_)::value;
+                constexpr int st = MF ? un / 2 : un, jb = MF ? (un % 2) * 4 : 0;
+                constexpr bool opens = !MF || un % 2 == 0, ends = !MF || un % 2 == 1;
                 (void)&aq; (void)&aoff; (void)&bq; (void)&ba; (void)&acc; (void)&qp;   // (asm operands alone do not capture)
-                if (st + 1 < 36) BT_BREAD(st + 1, boff);
-                // LDS returns in order: all but the 4 reads of the next step have landed
-                if (st + 1 < 36) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if (un + 1 < 36) BT_BREAD(un + 1, boff);
+                // LDS returns in order: all but the 4 reads of the next unit have landed
+                if (un + 1 < 36) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 // vector memory returns in order: younger than this step's weight loads are the loads of the R - 1 later steps and,
                 // while those loads still date from the previous patch (st < R), this patch's UMAX DMA pieces
-                if constexpr (st < R) {
-                    if (has_next) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 * (R - 1) + UMAX) : "memory");
-                    else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 * (R - 1)) : "memory");
-                } else {
-                    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 * (R - 1)) : "memory");
+                if constexpr (opens) {
+                    if constexpr (st < R) {
+                        if (has_next) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(APS * (R - 1) + UMAX) : "memory");
+                        else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(APS * (R - 1)) : "memory");
+                    } else {
+                        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(APS * (R - 1)) : "memory");
+                    }
                 }
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
+                for (int i = 0; i < APS; ++i)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) BT_MFMA(acc[i][j], aq[st % R][i], bq[st % 2][j]);
+                    for (int j = 0; j < 4; ++j) BT_MFMA(acc[i][jb + j], aq[st % R][i], bq[un % 2][j]);
                 // re-load the consumed slot with the step R ahead (this patch, or the first steps of the next one)
-                if constexpr (st + R < 36) { BT_ALOAD(wcur, st + R, st % R); } else { BT_ALOAD(wnxt, st + R - 36, st % R); }
+                if constexpr (ends) {
+                    if constexpr (st + R < NSTEP) { BT_ALOAD(wcur, st + R, st % R); } else { BT_ALOAD(wnxt, st + R - NSTEP, st % R); }
+                }
             });
             __builtin_amdgcn_s_setprio(0);
             // every wave's pieces of the next patch have landed (its vmcnt waits from step R on cover them) and it has left this buffer
@@ -1097,12 +1137,19 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 1))
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (res_on && j + 1 < 4) res_fetch(j + 1, rq[(j + 1) & 1]);
+            if constexpr (MF) {        // 16-row blocks 4 h .. 4 h + 3, position groups 2 j and 2 j + 1: the same LDS image
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+                for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *(float4*)(est + n * EPITCH + (i * 32 + g * 8 + khalf * 4) * 4) =
-                        make_float4(acc[2 * h + i][j][g * 4 + 0], acc[2 * h + i][j][g * 4 + 1], acc[2 * h + i][j][g * 4 + 2], acc[2 * h + i][j][g * 4 + 3]);
+                    for (int jl = 0; jl < 2; ++jl) epi_stage16(est, lane, i, jl, acc[(4 * h + i) % APS][(2 * j + jl) % NJ]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+                        *(float4*)(est + n * EPITCH + (i * 32 + g * 8 + khalf * 4) * 4) =
+                            make_float4(acc[2 * h + i][j][g * 4 + 0], acc[2 * h + i][j][g * 4 + 1], acc[2 * h + i][j][g * 4 + 2], acc[2 * h + i][j][g * 4 + 3]);
+            }
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -1203,13 +1250,15 @@ int launch_bt(dat_ctx* ctx, hipStream_t st, ConvParams& p) {
     p.nblocks = (unsigned)nblocks;
     const int npiece = ((th + 2) * (tw + 2) * 8 + 63) / 64;
     const size_t lds = (size_t)2 * npiece * 1024;
-#define BT_LAUNCH(TWL_, R_)                                                                                            \
+#define BT_LAUNCH(TWL_, R_, MF_)                                                                                           \
     {                                                                                                                  \
-        if (dat_ensure_lds(ctx, (const void*)conv3x3_bt_kernel<TWL_, R_>, 160 * 1024) != DAT_OK) return DAT_ERR_LAUNCH; \
-        hipLaunchKernelGGL((conv3x3_bt_kernel<TWL_, R_>), dim3(p.nblocks), dim3(NTHREADS), lds, st, p);                \
+        if (dat_ensure_lds(ctx, (const void*)conv3x3_bt_kernel<TWL_, R_, MF_>, 160 * 1024) != DAT_OK) return DAT_ERR_LAUNCH; \
+        hipLaunchKernelGGL((conv3x3_bt_kernel<TWL_, R_, MF_>), dim3(p.nblocks), dim3(NTHREADS), lds, st, p);           \
     }
     // (a 9-step weight ring was tried: 256 VGPRs, spills -- and a scratch access in the loop would break the counted vmcnt waits)
-    if (twl == 5) BT_LAUNCH(5, 6) else BT_LAUNCH(4, 6)
+    // 16x16x32 (DAT_CONV_MFMA=1): a step is twice as long (64 MFMAs of 16 cycles), so 3 steps of 8 loads are the same look-ahead
+    if (ctx->dbg_mfma) { if (twl == 5) BT_LAUNCH(5, 3, 1) else BT_LAUNCH(4, 3, 1) }
+    else if (twl == 5) BT_LAUNCH(5, 6, 0) else BT_LAUNCH(4, 6, 0)
 #undef BT_LAUNCH
     DAT_CHECK_LAUNCH(ctx, "conv3x3_bt");
     return DAT_OK;

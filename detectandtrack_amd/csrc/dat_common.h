@@ -52,6 +52,7 @@ struct dat_ctx {
     int dbg_roi_fold;                       // DAT_ROI_BWD_FOLD (default 1): RoIAlign backward folds a bin's samples into one weight per distinct pixel before the atomics
     int num_cu;                             // compute units of the device (persistent-kernel grids)
     int dbg_ntap;                           // DAT_CONV_NTAP (default 1): unrolled-tap variants of the implicit-GEMM kernel (3x3 stride 1, 1x1)
+    int dbg_mfma;                           // DAT_CONV_MFMA (default 1): MFMA shape of the big-tile 3x3 kernel and of the generic kernel's bf16 128-channel 3x3 stride-1 variants, always the same for both: 0 = 32x32x16, 1 = 16x16x32
     int dbg_temporal;                       // DAT_CONV_TEMPORAL (default 1): temporal-tap K-streaming kernel for kT x 1 x 1 layers ((2+1)D blocks) with Cout a multiple of 256 on grids of >= 3/4 block per CU; 2 = every supported shape (tests, tools/probes/temporal_probe.py); 0 = the generic kernel
     // kernels whose dynamic-LDS limit was already raised on this context's device (the attribute is per device)
     std::unordered_set<const void*> lds_attr_done;
@@ -109,6 +110,8 @@ __device__ __forceinline__ uint32_t f2bf2(float lo, float hi) {
 __device__ __forceinline__ float bf2f(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
 #define DAT_MFMA16(A_, B_, C_) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8_t, A_), __builtin_bit_cast(h16x8_t, B_), C_, 0, 0, 0)
 #define DAT_MFMA16_OP "v_mfma_f32_32x32x16_f16"
+#define DAT_MFMA16K32(A_, B_, C_) __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8_t, A_), __builtin_bit_cast(h16x8_t, B_), C_, 0, 0, 0)
+#define DAT_MFMA16K32_OP "v_mfma_f32_16x16x32_f16"
 #define DAT_H16_FORMAT 1
 #else
 // fp32 -> bf16, round to nearest even: gfx950 has the conversion in hardware (v_cvt_pk_bf16_f32); the integer-arithmetic
@@ -124,6 +127,10 @@ __device__ __forceinline__ uint32_t f2bf2(float lo, float hi) {
 __device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
 #define DAT_MFMA16(A_, B_, C_) __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, A_), __builtin_bit_cast(bf16x8_t, B_), C_, 0, 0, 0)
 #define DAT_MFMA16_OP "v_mfma_f32_32x32x16_bf16"
+// the second MFMA shape of the two dominant 3x3 kernels (DAT_CONV_MFMA=1): 16 rows x 16 columns x K = 32, the same
+// 16-byte operand fragments per lane, a quarter of the accumulator registers per tile
+#define DAT_MFMA16K32(A_, B_, C_) __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, A_), __builtin_bit_cast(bf16x8_t, B_), C_, 0, 0, 0)
+#define DAT_MFMA16K32_OP "v_mfma_f32_16x16x32_bf16"
 #define DAT_H16_FORMAT 0
 #endif
 
