@@ -287,13 +287,17 @@ def _build_defaults():
     # USE_GN (opt-in): every AffineChannel[Nd] of the body becomes a GroupNorm layer (csrc/group_norm.hip) behind the
     # unfused conv, in training AND test graphs -- statistics per clip over T x H x W x the group's channels, no running statistics, trainable
     # scale / bias.  GN_NUM_GROUPS: a layer of C channels gets the largest divisor of C that is <= this many groups (modeling/detector.py
-    # gn_groups).  GN_EPSILON: added to the variance.  Not combinable with MODEL.USE_BN, HIP.KEYFRAME_DCE or HIP.FRAME_TRUNK_CACHE
+    # gn_groups).  GN_EPSILON: added to the variance.  Not combinable with MODEL.USE_BN, HIP.KEYFRAME_DCE or HIP.FRAME_TRUNK_CACHE.  Layers behind
+    # a RoIFeatureTransform (the per-RoI res5 stage of the C4 heads) take their statistics per RoI, in one fused launch
+    # (csrc/group_norm_roi.hip).
+    # GN_KPS_HEAD (opt-in, needs USE_GN): every conv_fcn{i} of the keypoint head add_roi_pose_head_v1convX[_3d] becomes conv without bias ->
+    # GroupNorm `conv_fcn{i}_gn` (per RoI) -> ReLU; off, the head is the reference's eight bare conv + ReLU layers
     c.HIP = AttrDict({'DTYPE': 'bf16', 'KEYFRAME_DCE': False, 'DEVICE_KPS_DECODE': True, 'FRAME_TRUNK_CACHE': 0,
                       'DEVICE_BOX_RESULTS': True, 'FUSE_STEM_POOL': True, 'RCCL_DIRECT': False,
                       'PIPELINE_DEPTH': 4, 'CLIP_GRAPH': True, 'IMS_PER_FORWARD': 1, 'FUSE_RELU_BWD': True, 'FUSE_RELU_SUM_BWD': True, 'PERSISTENT_CU_SHARE': 50, 'DET_SPARE_ROWS': 4,
                       'DEFER_WGRAD_FINISH': True, 'MAX_GRAPHS_PER_SLOT': 6, 'PAD_TAIL_FORWARD': True,
                       'OVERLAP_ALLREDUCE': True, 'WGRAD_PW_BATCH': 16, 'DEVICE_ROI_SAMPLING': True, 'DECONV_GROUP_IGNORED': False, 'STEM_FROM_UINT8': True,
-                      'TRAIN_GROUPED_CONV': False, 'USE_GN': False, 'GN_NUM_GROUPS': 32, 'GN_EPSILON': 1e-5})
+                      'TRAIN_GROUPED_CONV': False, 'USE_GN': False, 'GN_NUM_GROUPS': 32, 'GN_EPSILON': 1e-5, 'GN_KPS_HEAD': False})
     return c
 
 

@@ -25,6 +25,13 @@ constexpr int BN_MAX_BLOCKS = 1024;     // row blocks x channel chunks (four 256
 template <int DT> struct Vec;
 template <> struct Vec<DAT_F32> {
     static constexpr int N = 4;
+    // one 16-byte vector in registers <-> its N values
+    __device__ static __forceinline__ void unpack(const uint4& a, float* v) {
+        v[0] = __uint_as_float(a.x); v[1] = __uint_as_float(a.y); v[2] = __uint_as_float(a.z); v[3] = __uint_as_float(a.w);
+    }
+    __device__ static __forceinline__ uint4 pack(const float* v) {
+        return make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
+    }
     __device__ static __forceinline__ void ld(const void* p, size_t elem, float* v) {
         const float4 a = *(const float4*)((const float*)p + elem);
         v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
@@ -35,8 +42,8 @@ template <> struct Vec<DAT_F32> {
 };
 template <> struct Vec<DAT_BF16> {
     static constexpr int N = 8;
-    __device__ static __forceinline__ void ld(const void* p, size_t elem, float* v) {
-        const uint4 a = *(const uint4*)((const uint16_t*)p + elem);
+    // one 16-byte vector in registers <-> its N values: the only copy of the 16-bit conversion of these kernels (ld / st go through it)
+    __device__ static __forceinline__ void unpack(const uint4& a, float* v) {
         const uint32_t w[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -44,11 +51,13 @@ template <> struct Vec<DAT_BF16> {
             v[2 * i + 1] = bf2f((uint16_t)(w[i] >> 16));
         }
     }
-    __device__ static __forceinline__ void st(void* p, size_t elem, const float* v) {
+    __device__ static __forceinline__ uint4 pack(const float* v) {
         uint4 a;
         a.x = f2bf2(v[0], v[1]); a.y = f2bf2(v[2], v[3]); a.z = f2bf2(v[4], v[5]); a.w = f2bf2(v[6], v[7]);
-        *(uint4*)((uint16_t*)p + elem) = a;
+        return a;
     }
+    __device__ static __forceinline__ void ld(const void* p, size_t elem, float* v) { unpack(*(const uint4*)((const uint16_t*)p + elem), v); }
+    __device__ static __forceinline__ void st(void* p, size_t elem, const float* v) { *(uint4*)((uint16_t*)p + elem) = pack(v); }
 };
 
 // the thread's place in the layout of the file comment

@@ -172,6 +172,9 @@ _PROTOS = {
     'dat_gn_apply': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _ll, _i, _i, _i]),
     'dat_gn_bwd_reduce': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _ll, _ll, _ll, _i, _i, _i, _i, _p, _p, _p, _p, _p, C.c_size_t]),
     'dat_gn_bwd_apply': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _ll, _ll, _ll, _i, _i]),
+    'dat_gn_roi_workspace_bytes': (C.c_size_t, [_i, _i]),
+    'dat_gn_roi_fwd': (_i, [_p, _p, _i, _p, _p, _p, _i, _ll, _i, _i, _i, _p, _p, _f, _i, _p, _p, _p, _i]),
+    'dat_gn_roi_bwd': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _ll, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, C.c_size_t]),
     'dat_zero_insert2x': (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i]),
     'dat_upsample2x_bwd': (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i]),
     'dat_sgd_momentum': (_i, [_p, _p, _p, _p, _p, C.c_longlong, _f, _f, _f, _i]),

@@ -816,6 +816,51 @@ def gn_bwd_apply(g, z, dtype, C_real, mean, a, coef, clips=1, frame_lo=0):
     return dz
 
 
+# ---- GroupNorm on per-RoI blobs [R * Tr, H, W, cs]: tables fp32 [R, groups] -----------------------------------
+def _gn_roi_count(count, R):
+    """(count tensor to keep alive, pointer, n_seg) of a device RoI count (one entry per image over equal row segments), or of None"""
+    if count is None:
+        return None, None, 1
+    c = count.reshape(-1).to(torch.int32).contiguous()
+    assert R % c.numel() == 0, (R, c.numel())
+    return c, _ptr(c), int(c.numel())
+
+
+def gn_roi_fwd(z, dtype, C_real, groups, scale, bias, eps, R, relu=False, residual=None, count=None, out=None):
+    """GroupNorm of every RoI of z ([R * Tr, H, W, cs]) in one launch -> (y, mean, rstd), mean / rstd fp32 [R, groups].  count: device
+    int32 [n_images] (RoI r is live iff r % (R / n_images) < count[r // (R / n_images)]) or None; dead RoIs give zero rows."""
+    cs, rows = _gn_rows(z, R)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (scale, bias))
+    assert residual is None or (residual.shape == z.shape and residual.is_contiguous())
+    y = torch.empty_like(z) if out is None else out
+    mean = torch.empty((R, groups), dtype=torch.float32, device=z.device)
+    rstd = torch.empty((R, groups), dtype=torch.float32, device=z.device)
+    keep, cp, n_seg = _gn_roi_count(count, R)
+    ctx().call('dat_gn_roi_fwd', _stream(), dtype, _ptr(z), _ptr(residual), _ptr(y), R, C.c_longlong(rows), C_real, cs, groups, _ptr(scale),
+               _ptr(bias), C.c_float(eps), int(relu), _ptr(mean), _ptr(rstd), cp, n_seg)
+    return y, mean, rstd
+
+
+def gn_roi_bwd(dy, y, z, dtype, C_real, groups, mean, rstd, scale, R, relu=False, count=None, want_g=True, want_dz=True, dbeta=None,
+               dgamma=None, inplace=False):
+    """-> (g = dy * [y > 0] or None, dz or None, sums fp32 [R, 2, cs] = sum g, sum g * xhat per RoI); dbeta / dgamma (fp32 [C])
+    ACCUMULATE the sums of the live RoIs."""
+    cs, rows = _gn_rows(z, R)
+    assert dy.is_contiguous() and dy.shape == z.shape and (y is None or y.is_contiguous())
+    assert tuple(mean.shape) == tuple(rstd.shape) == (R, groups) and mean.is_contiguous() and rstd.is_contiguous()
+    g = (dy if inplace else torch.empty_like(dy)) if want_g else None
+    dz = torch.empty_like(z) if want_dz else None
+    sums = torch.empty((R, 2, cs), dtype=torch.float32, device=z.device)
+    n = int(L._lib.dat_gn_roi_workspace_bytes(R, cs))
+    assert n > 0, 'GroupNorm: %d RoIs at channel stride %d' % (R, cs)
+    ws = torch.empty(n, dtype=torch.uint8, device=z.device)
+    keep, cp, n_seg = _gn_roi_count(count, R)
+    ctx().call('dat_gn_roi_bwd', _stream(), dtype, _ptr(dy), _ptr(y) if relu else None, _ptr(z), _ptr(mean), _ptr(rstd), _ptr(scale), R,
+               C.c_longlong(rows), C_real, cs, groups, int(relu), cp, n_seg, _ptr(g), _ptr(dz), _ptr(sums), _ptr(dbeta), _ptr(dgamma),
+               _ptr(ws), C.c_size_t(n))
+    return g, dz, sums
+
+
 def upsample2x_bwd(g, dtype, dtop=None):
     frames, H2, W2, cs = g.shape
     acc = dtop is not None

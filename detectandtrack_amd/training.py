@@ -496,13 +496,25 @@ class TrainExecutor(Executor):
         if dy is None:
             return
         z, st = y.bn
-        assert lo == 0 and dy.shape[0] == z.shape[0] or y.N == 1, 'frame-window gradients assume one clip per forward'
+        assert lo == 0 and dy.shape[0] == z.shape[0] or (y.N == 1 and not y.roi), 'frame-window gradients assume one clip per forward'
         dev = {}
         for key in ('bias', 'scale'):
             name = a[key]
             if self._trainable(name):       # the kernel ACCUMULATES: straight into the (zeroed) arena view when there is one
                 dev[key] = self.arena[name] if (self.arena is not None and name in self.arena) else \
                     torch.zeros(y.C, dtype=torch.float32, device=ws.device)
+        if y.roi:       # per-RoI blob: the fused backward (a per-RoI gradient always covers the RoI's frames)
+            need_dz = op.inputs[0] not in self.no_grad
+            g, dz, _ = ops.gn_roi_bwd(dy if dy.is_contiguous() else dy.contiguous(), y.t, z, y.dt, y.C, a['groups'], st[0], st[1],
+                                      self._master(a['scale']), R=y.N, relu=bool(a['relu']), count=y.count, want_g=bool(a['residual']),
+                                      want_dz=need_dz, dbeta=dev.get('bias'), dgamma=dev.get('scale'))
+            for key, t in dev.items():
+                self._pgrad(a[key], t)
+            if a['residual']:
+                self._add_grad(a['residual'], g, 0)
+            if need_dz:
+                self._add_grad(op.inputs[0], dz, 0)
+            return
         g, _, coef = ops.gn_bwd_reduce(dy if dy.is_contiguous() else dy.contiguous(), y.t, z, y.dt, y.C, a['groups'], st[0], st[1],
                                        self._master(a['scale']), clips=y.N, frame_lo=lo, relu=bool(a['relu']), dbeta=dev.get('bias'),
                                        dgamma=dev.get('scale'))

@@ -22,12 +22,14 @@ logger = logging.getLogger(__name__)
 class Blob(object):
     """A device blob.  kind: 'fmap' [N*T,H,W,Cs] | 'rows' [1,1,R,Cs] (FC activations) | 'mat' fp32 tensor |
     'rois' fp32 [cap, cols] + device count."""
-    __slots__ = ('t', 'kind', 'N', 'T', 'C', 'dt', 'five_d', 'count', 'sigmoid_of', 'host', 'keyframe', 't2c', 'split', 'tsel', 'bn')
+    __slots__ = ('t', 'kind', 'N', 'T', 'C', 'dt', 'five_d', 'count', 'sigmoid_of', 'host', 'keyframe', 't2c', 'split', 'tsel', 'bn', 'roi')
 
     def __init__(self, t, kind, N=1, T=1, C=0, dt=0, five_d=False, count=None):
         self.t, self.kind, self.N, self.T, self.C, self.dt = t, kind, N, T, C, dt
         self.five_d = five_d
         self.count = count
+        self.roi = False        # the blob descends from a RoIFeatureTransform: its leading axis counts RoIs (x Tr frames), not clips; set there and
+                                # carried wherever `count` is carried (in training `count` is None and the flag is all that tells)
         self.sigmoid_of = None
         self.host = None
         self.split = None       # bf16x3 mode: the hi / lo bf16 split of `t`, made by the first conv that reads the blob and shared by the others
@@ -36,7 +38,7 @@ class Blob(object):
         self.t2c = False        # time moved into channels (detector.py:480-491): still stored as T frames of C channels
         self.keyframe = None    # set when only this frame of a T-frame blob was computed (cfg.HIP.KEYFRAME_DCE)
         self.bn = None          # output of a training-mode SpatialBN: (its input tensor z, fp32 [4, cs] = mean, rstd, a, b') for the backward;
-                                # of a GroupNorm: (z, fp32 [4, clips, cs])
+                                # of a GroupNorm: (z, fp32 [4, clips, cs]); of a GroupNorm over a per-RoI blob: (z, (mean, rstd) fp32 [R, groups])
 
 
 class Workspace(object):
@@ -501,7 +503,7 @@ class Executor(object):
             self._log_conv(op.outputs[0], layer, xin.t.shape[0], xin.t.shape[1], xin.t.shape[2], oframes=xin.N)
             y = layer(xin.t, T=tfull, out_t=(kf, 1))
             b = Blob(y, 'fmap', xin.N, 1, a['dim_out'], dt, False)
-            b.count = xin.count
+            b.count, b.roi = xin.count, xin.roi
             ws.blobs[op.outputs[0]] = b
             return
         k = self._keyframe.get(op.outputs[0])
@@ -520,7 +522,7 @@ class Executor(object):
         b = Blob(y, 'fmap', xin.N, xin.T, a['dim_out'], dt, xin.five_d)
         b.split = getattr(y, '_split', None)      # (bf16x3: written by this conv's epilogue for the convs that read the blob)
         b.keyframe = xin.keyframe
-        b.count = xin.count   # per-RoI heads (ResNet3D.py:301-327): the live RoI count travels with the features
+        b.count, b.roi = xin.count, xin.roi   # per-RoI heads (ResNet3D.py:301-327): the live RoI count travels with the features
         ws.blobs[op.outputs[0]] = b
 
     def _pad_unread(self, name):
@@ -691,15 +693,26 @@ class Executor(object):
 
     def op_GroupNorm(self, i, op):
         """GroupNorm (+ fused residual / ReLU), the same in training and inference: one statistics pass per clip (x.N clips per forward),
-        then one normalise pass.  Nothing synchronises, so the op is captured into a clip graph like a conv.  The output keeps
-        (z, mean / rstd / a / b') for the backward."""
+        then one normalise pass; over a per-RoI blob (`x.roi`), one fused launch.  Nothing synchronises, so the
+        op is captured into a clip graph like a conv.  The output keeps (z, mean / rstd / a / b') for the backward."""
         ws, a = self.ws, op.args
         x = ws.blobs[op.inputs[0]]
         assert x.kind == 'fmap' and x.keyframe is None and x.tsel is None and not x.t2c, (op, x.kind)
-        assert x.count is None, 'GroupNorm over a row-counted blob (per-RoI head) is not supported'
         assert x.t.shape[0] == x.N * x.T, (op, tuple(x.t.shape), x.N, x.T)
-        st = ops.gn_stats(x.t, x.dt, x.C, a['groups'], ws.dev_param(a['scale']), ws.dev_param(a['bias']), a['eps'], clips=x.N)
         res = ws.blobs[a['residual']].t if a['residual'] else None
+        if x.roi:
+            # a per-RoI blob (C4 res5 head, keypoint head): N counts RoIs.  One fused launch per layer; the live count stays on the device
+            # (inference: per-image segment counts; training: the sampled RoIs are fed with exact shapes, count is None)
+            assert x.count is None or isinstance(x.count, torch.Tensor), type(x.count)
+            y, mean, rstd = ops.gn_roi_fwd(x.t, x.dt, x.C, a['groups'], ws.dev_param(a['scale']), ws.dev_param(a['bias']), a['eps'], R=x.N,
+                                           relu=a['relu'], residual=res, count=x.count)
+            b = Blob(y, 'fmap', x.N, x.T, x.C, x.dt, x.five_d)
+            b.bn = (x.t, (mean, rstd))
+            b.count, b.roi = x.count, True
+            ws.blobs[op.outputs[0]] = b
+            return
+        assert x.count is None, 'GroupNorm over a row-counted blob that is no per-RoI feature is not supported'
+        st = ops.gn_stats(x.t, x.dt, x.C, a['groups'], ws.dev_param(a['scale']), ws.dev_param(a['bias']), a['eps'], clips=x.N)
         y = ops.gn_apply(x.t, x.dt, x.C, st[2], st[3], clips=x.N, relu=a['relu'], residual=res)
         b = Blob(y, 'fmap', x.N, x.T, x.C, x.dt, x.five_d)
         b.bn = (x.t, st)
@@ -784,7 +797,7 @@ class Executor(object):
         m = ops.spatial_mean(x.t, x.dt, cs)                       # fp32 [R*T, Cs]
         y = m if x.dt == ops.F32 else m.to(ops.tdtype(x.dt))
         b = Blob(y.view(f, 1, 1, cs), 'fmap', x.N, x.T, x.C, x.dt, x.five_d)
-        b.count = x.count
+        b.count, b.roi = x.count, x.roi
         self.ws.blobs[op.outputs[0]] = b
 
     def _head_rows(self, x):
@@ -799,7 +812,7 @@ class Executor(object):
         m = self._head_rows(x)
         y = ops.time_avg(m.contiguous().view(x.N * x.T, 1, 1, x.C), ops.F32, x.N, x.T).view(1, 1, x.N, x.C)
         b = Blob(y, 'rows', 1, 1, x.C, ops.F32)
-        b.count = x.count
+        b.count, b.roi = x.count, x.roi
         self.ws.blobs[op.outputs[0]] = b
 
     def op_TubeDeltasToRows(self, i, op):
@@ -809,7 +822,7 @@ class Executor(object):
         R, T, K4 = m.shape
         y = m.view(R, T, K4 // 4, 4).permute(0, 2, 1, 3).reshape(R, K4 * T).contiguous()
         b = Blob(y, 'mat')
-        b.count = x.count
+        b.count, b.roi = x.count, x.roi
         self.ws.blobs[op.outputs[0]] = b
 
     def op_Alias(self, i, op):
@@ -900,7 +913,7 @@ class Executor(object):
                           pooled=a['resolution'], sampling=a['sampling_ratio'], k_min=cfg.FPN.ROI_MIN_LEVEL,
                           canon_scale=float(cfg.FPN.ROI_CANONICAL_SCALE), canon_level=cfg.FPN.ROI_CANONICAL_LEVEL)
         b = Blob(y, 'fmap', R, Tr, f0.C, f0.dt, Tr > 1)
-        b.count = rois.count
+        b.count, b.roi = rois.count, True
         ws.blobs[op.outputs[0]] = b
 
     def op_FC(self, i, op):
@@ -926,7 +939,7 @@ class Executor(object):
         self._log_conv(op.outputs[0], layer, 1, 1, xin.shape[2])
         y = layer(xin, T=1, zero_pad=not self._pad_unread(op.outputs[0]))
         b = Blob(y, 'rows', 1, 1, a['dim_out'], dt)
-        b.count = x.count
+        b.count, b.roi = x.count, x.roi
         ws.blobs[op.outputs[0]] = b
 
     def _rows_to_mat(self, b):
@@ -937,7 +950,7 @@ class Executor(object):
         x = self.ws.blobs[op.inputs[0]]
         m = self._rows_to_mat(x)
         b = Blob(ops.softmax_rows(m, x.C), 'mat')
-        b.count = x.count
+        b.count, b.roi = x.count, x.roi
         self.ws.blobs[op.outputs[0]] = b
 
     def op_ConvTranspose(self, i, op):
@@ -1005,7 +1018,7 @@ class Executor(object):
                                 layer.hbm_bytes(x.t.shape[0], x.t.shape[1], x.t.shape[2], oframes=x.N)))
         y = layer(x.t, T=T, out_t=(0, 1), zero_pad=not self._pad_unread(op.outputs[0]))
         b = Blob(y, 'fmap', x.N, 1, 4 * a['dim_out'], dt, False)
-        b.count = x.count
+        b.count, b.roi = x.count, x.roi
         ws.blobs[op.outputs[0]] = b
 
     def op_BilinearInterpolation(self, i, op):

@@ -611,6 +611,31 @@ int dat_gn_bwd_reduce(dat_ctx* ctx, dat_stream s, int dtype, const void* dy, con
 int dat_gn_bwd_apply(dat_ctx* ctx, dat_stream s, int dtype, const void* g, const void* z, void* dz, const float* mean, const float* a,
                      const float* coef, int clips, long long rows, long long row_lo, long long nrows, int C, int cstride);
 
+/* ---- GroupNorm on per-RoI blobs (the C4 res5 box head, the keypoint head) -------------------------------
+ * The same function on blobs [R][rows][cstride], rows = Tr*H*W positions of ONE RoI: statistics per (RoI, group), fused with the
+ * normalisation.  cstride: a multiple of 64, at most 2048; groups of any cg = C / groups; rows * cg < 2 is DAT_ERR_ARG.  Tables
+ * mean / rstd: fp32 [R][groups] (NOT per channel);  sums: fp32 [R][2][cstride].  `count` (device int32[n_seg], or NULL: every RoI
+ * is live): the R rows are n_seg equal segments (one per image) and RoI r is live iff r % (R / n_seg) < count[r / (R / n_seg)];
+ * R % n_seg != 0 is DAT_ERR_ARG.  A dead RoI's inputs are not read, its rows of every output are zeros and it enters no sum.
+ * The summation order depends on (dtype, rows, C, cstride, groups) only: a RoI gets the same bits alone and among others; no float
+ * atomics.  Nothing allocates, synchronises or reads back, so every call can be captured into a hipGraph. */
+/* ONE launch: mean and the biased variance (a second pass around the mean over the same values, never E[x^2] - mean^2) per (RoI,
+ * group), then y = act(z * a + bprime (+ residual)) with a = scale * rstd, bprime = bias - mean * a in fp32 (the form of dat_gn_apply).
+ * RoIs too large for the registers are split into channel slabs of whole groups (one block each) or re-read z, inside the same launch.  y may alias z and / or residual (NULL: none). */
+int dat_gn_roi_fwd(dat_ctx* ctx, dat_stream s, int dtype, const void* z, const void* residual, void* y, int R, long long rows, int C,
+                   int cstride, int groups, const float* scale, const float* bias, float eps, int relu, float* mean, float* rstd,
+                   const int* count, int n_seg);
+/* bytes of the caller-owned scratch of dat_gn_roi_bwd (0: bad shape) */
+size_t dat_gn_roi_workspace_bytes(int R, int cstride);
+/* At most two launches.  g = dy * [y > 0] (y: the op's output, NULL without relu; g: NULL when nobody reads it, may alias dy);
+ * sums[r][0][c] = S1 = sum g, sums[r][1][c] = S2 = sum g * xhat over the RoI's rows, xhat = (z - mean) * rstd;  per group
+ * A = sum scale * S1, B = sum scale * S2, Mg = rows * cg and  dz = rstd * (scale * g - A / Mg - xhat * B / Mg)  evaluated as
+ * a * g + q + r * (z - mean)  (dz: NULL when the input needs no gradient).  dbeta[c] += sum_r S1, dgamma[c] += sum_r S2 (either may be
+ * NULL), summed in an order that depends on R only. */
+int dat_gn_roi_bwd(dat_ctx* ctx, dat_stream s, int dtype, const void* dy, const void* y, const void* z, const float* mean, const float* rstd,
+                   const float* scale, int R, long long rows, int C, int cstride, int groups, int relu, const int* count, int n_seg,
+                   void* g, void* dz, float* sums, float* dbeta, float* dgamma, void* ws, size_t ws_bytes);
+
 /* ---- training input pipeline: RPN anchor labelling, device half -------------------------------------
  * Replaces the O(anchors x gts) part of reference lib/roi_data/rpn.py:283-312: the straddle filter (:283-291), the Cython
  * IoU lib/utils/cython_bbox.pyx:16-57 averaged over the tube's frames (lib/utils/boxes.py:60-69), anchor->gt max / first
