@@ -81,7 +81,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
 
 #ifdef DAT_CONV_TRACE
     const unsigned long long tr_k0 = __builtin_amdgcn_s_memtime();
-    unsigned long long tr_k1 = tr_k0;
+    unsigned long long tr_k1 = tr_k0, tr_first = 0, tr_unrolled = 0;   // (unrolled-tap variants: first tap reached / tap loop left)
 #endif
     unsigned long long clk_c0 = 0, clk_r0 = 0;
     if (p.clk) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
@@ -190,23 +190,54 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
         constexpr bool PACK16 = NTAP != 10;                    // (the dense stride-2 patch is 70 KiB: one address per register there)
         constexpr int NQ = PACK16 ? (PTX + 1) / 2 : PTX;
         unsigned qp[NT][NQ];
-#pragma unroll
-        for (int tp = 0; tp < NT; ++tp)
+        // The 256-position variants run the POSITION GROUP outermost: under linear tiling the lane's map coordinates then take one pair of
+        // divisions per group, and the tap's row and column are compile-time (strips exist for 3 x 3 taps only: launch_conv).  With the taps
+        // outermost the compiler repeats the divisions for every tap -- the nine copies sit in nine conditional blocks -- 144 integer divisions
+        // per lane: a strip block took 63.6k cycles to reach its first tap against 21.6k on 2-D tiles, 21.1k now (profiles/persist/README.md).
+        // The other variants keep the tap-outermost nest as it was, and the two nests are not one loop with the order as a parameter:
+        // <bf16,128,128,...,MF = 1> sits at its 168-register budget (three blocks per CU) and spills 24 bytes of scratch per lane with the new
+        // order, 16 with the old order written as such a loop; as below every variant but the 256-position ones compiles as before.
+        if constexpr (BP == 256) {
 #pragma unroll
             for (int j = 0; j < PTX; ++j) {
-                int row = rowbase[j] + p.tab_rowoff[tp];
-                if (p.lin_w > 0) {   // linear tiling: a tap that leaves the lane's map (row / column / map border) reads the zero row
+                int lin_y = 0, lin_x = 0;
+                if (p.lin_w > 0) {
                     const int gpos = ow0 + wave_p * WP + (MF ? j * 16 + (lane & 15) : j * 32 + (lane & 31));
                     const int rem = gpos % (p.lin_h * p.lin_w);
-                    const int y = rem / p.lin_w, x = rem - y * p.lin_w;
-                    const int yy = y + tp / p.KW - p.KH / 2, xx = x + tp % p.KW - p.KW / 2;
-                    if ((unsigned)yy >= (unsigned)p.lin_h || (unsigned)xx >= (unsigned)p.lin_w) row = p.lin_zero_row;
+                    lin_y = rem / p.lin_w; lin_x = rem - lin_y * p.lin_w;
                 }
-                const unsigned a16 = patch_frag_addr<MF>(row, MF ? lane >> 4 : khalf);
-                if (!PACK16) qp[tp][j] = a16;
-                else if (j & 1) qp[tp][j >> 1] |= a16 << 16;
-                else qp[tp][j >> 1] = a16;
+#pragma unroll
+                for (int tp = 0; tp < NT; ++tp) {
+                    int row = rowbase[j] + p.tab_rowoff[tp];
+                    if (p.lin_w > 0) {   // linear tiling: a tap that leaves the lane's map (row / column / map border) reads the zero row
+                        const int yy = lin_y + tp / 3 - 1, xx = lin_x + tp % 3 - 1;
+                        if ((unsigned)yy >= (unsigned)p.lin_h || (unsigned)xx >= (unsigned)p.lin_w) row = p.lin_zero_row;
+                    }
+                    const unsigned a16 = patch_frag_addr<MF>(row, MF ? lane >> 4 : khalf);
+                    if (!PACK16) qp[tp][j] = a16;
+                    else if (j & 1) qp[tp][j >> 1] |= a16 << 16;    // (the even group of a pair comes first in either order)
+                    else qp[tp][j >> 1] = a16;
+                }
             }
+        } else {
+#pragma unroll
+            for (int tp = 0; tp < NT; ++tp)
+#pragma unroll
+                for (int j = 0; j < PTX; ++j) {
+                    int row = rowbase[j] + p.tab_rowoff[tp];
+                    if (p.lin_w > 0) {   // linear tiling: a tap that leaves the lane's map (row / column / map border) reads the zero row
+                        const int gpos = ow0 + wave_p * WP + (MF ? j * 16 + (lane & 15) : j * 32 + (lane & 31));
+                        const int rem = gpos % (p.lin_h * p.lin_w);
+                        const int y = rem / p.lin_w, x = rem - y * p.lin_w;
+                        const int yy = y + tp / p.KW - p.KH / 2, xx = x + tp % p.KW - p.KW / 2;
+                        if ((unsigned)yy >= (unsigned)p.lin_h || (unsigned)xx >= (unsigned)p.lin_w) row = p.lin_zero_row;
+                    }
+                    const unsigned a16 = patch_frag_addr<MF>(row, MF ? lane >> 4 : khalf);
+                    if (!PACK16) qp[tp][j] = a16;
+                    else if (j & 1) qp[tp][j >> 1] |= a16 << 16;
+                    else qp[tp][j >> 1] = a16;
+                }
+        }
         // ---- per-lane source offsets of this wave's patch pieces (relative to the frame/chunk base; -1 = halo outside the frame)
         const int nchunks = (npatch_items + 63) >> 6;
         int poff[MAXCH];
@@ -261,6 +292,9 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
                 }
                 P_COMMIT();
                 __syncthreads();
+#ifdef DAT_CONV_TRACE
+                if (!tr_first) tr_first = __builtin_amdgcn_s_memtime();
+#endif
             }
             // the patch after this one (its first tap's weights are fetched during this patch's last tap)
             int ncc = cc + 1, nkt = kt;
@@ -331,6 +365,10 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
             wcur = wnextpatch;
             cc = ncc; kt = nkt;
         }
+#ifdef DAT_CONV_TRACE
+        tr_k1 = __builtin_amdgcn_s_memtime();
+        tr_unrolled = 1;
+#endif
       }
     } else
     if (total > 0) {
@@ -635,11 +673,17 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
         atomicAdd(&p.clk[1], __builtin_amdgcn_s_memrealtime() - clk_r0);
     }
 #ifdef DAT_CONV_TRACE
+    const unsigned long long tr_st = __builtin_amdgcn_s_memtime();   // the last store is issued
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (tid == 0 && p.dbg) {
         const unsigned long long e = __builtin_amdgcn_s_memtime();
         atomicAdd(&p.dbg[8], e - tr_k0);
         atomicAdd(&p.dbg[9], e - tr_k1);
+        if (tr_unrolled) {   // unrolled-tap variants: prologue up to the first tap, store drain, blocks
+            atomicAdd(&p.dbg[10], tr_first - tr_k0);
+            atomicAdd(&p.dbg[11], e - tr_st);
+            atomicAdd(&p.dbg[13], 1ull);
+        }
     }
 #endif
 }
@@ -909,6 +953,9 @@ int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ks
         unsigned long long h[16];
         hipStreamSynchronize(st);
         hipMemcpy(h, dbg, 128, hipMemcpyDeviceToHost);
+        if (h[13]) fprintf(stderr, "TRACE unrolled BN=%d BP=%d blocks=%llu | per block, shader cycles: total %.0f = prologue %.0f + taps %.0f + epilogue %.0f + store drain %.0f\n",
+                           BN, BP, h[13], (double)h[8] / h[13], (double)h[10] / h[13], (double)(h[8] - h[9] - h[10]) / h[13],
+                           (double)(h[9] - h[11]) / h[13], (double)h[11] / h[13]);
         if (h[5]) fprintf(stderr, "TRACE BN=%d BP=%d blocks=%u steps/blk=%.1f | per step: reload %.0f wait %.0f barrier %.0f issue %.0f mma %.0f | shader clock %.0f MHz | per block: total %.0f epilogue %.0f cycles\n",
                           BN, BP, p.nblocks, (double)h[5] / p.nblocks, (double)h[0] / h[5], (double)h[1] / h[5], (double)h[2] / h[5],
                           (double)h[3] / h[5], (double)h[4] / h[5], 100.0 * (double)h[6] / (double)h[7], (double)h[8] / p.nblocks, (double)h[9] / p.nblocks);
