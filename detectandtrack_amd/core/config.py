@@ -292,12 +292,18 @@ def _build_defaults():
     # (csrc/group_norm_roi.hip).
     # GN_KPS_HEAD (opt-in, needs USE_GN): every conv_fcn{i} of the keypoint head add_roi_pose_head_v1convX[_3d] becomes conv without bias ->
     # GroupNorm `conv_fcn{i}_gn` (per RoI) -> ReLU; off, the head is the reference's eight bare conv + ReLU layers
+    # TUBE_SOFT_NMS (opt-in): TEST.SOFT_NMS / TEST.BBOX_VOTE for TUBE detections (3D body feeding 3D heads), which the reference leaves undefined
+    # (nms_wrapper.py:34-35 raises, boxes.py:294-310 votes four columns).  On: the overlap of two tubes is the mean of their per-frame IoUs (what
+    # py_cpu_nms_tubes uses), Soft-NMS re-scores with it, voting replaces all 4T coordinates -- on the host path
+    # (dat_soft_nms_tubes_host, utils/boxes.box_voting) and on the device path (soft_nms_tubes_kernel, box_vote_tubes_kernel), which then admits
+    # such configs.  Off: tubes with either TEST switch stay on the host path and behave as in the reference
     c.HIP = AttrDict({'DTYPE': 'bf16', 'KEYFRAME_DCE': False, 'DEVICE_KPS_DECODE': True, 'FRAME_TRUNK_CACHE': 0,
                       'DEVICE_BOX_RESULTS': True, 'FUSE_STEM_POOL': True, 'RCCL_DIRECT': False,
                       'PIPELINE_DEPTH': 4, 'CLIP_GRAPH': True, 'IMS_PER_FORWARD': 1, 'FUSE_RELU_BWD': True, 'FUSE_RELU_SUM_BWD': True, 'PERSISTENT_CU_SHARE': 50, 'DET_SPARE_ROWS': 4,
                       'DEFER_WGRAD_FINISH': True, 'MAX_GRAPHS_PER_SLOT': 6, 'PAD_TAIL_FORWARD': True,
                       'OVERLAP_ALLREDUCE': True, 'WGRAD_PW_BATCH': 16, 'DEVICE_ROI_SAMPLING': True, 'DECONV_GROUP_IGNORED': False, 'STEM_FROM_UINT8': True,
-                      'TRAIN_GROUPED_CONV': False, 'USE_GN': False, 'GN_NUM_GROUPS': 32, 'GN_EPSILON': 1e-5, 'GN_KPS_HEAD': False})
+                      'TRAIN_GROUPED_CONV': False, 'USE_GN': False, 'GN_NUM_GROUPS': 32, 'GN_EPSILON': 1e-5, 'GN_KPS_HEAD': False,
+                      'TUBE_SOFT_NMS': False})
     return c
 
 

@@ -129,7 +129,7 @@ def box_results_with_nms_and_limit(scores, boxes):
         inds = np.where(scores[:, j] > cfg.TEST.SCORE_THRESH)[0]
         dets_j = np.hstack((boxes[inds, j * 4 * time_dim:(j + 1) * 4 * time_dim],
                             scores[inds, j][:, np.newaxis])).astype(np.float32, copy=False)
-        if cfg.TEST.SOFT_NMS.ENABLED:    # (:766-772; not implemented for time_dim > 1)
+        if cfg.TEST.SOFT_NMS.ENABLED:    # (:766-772; for time_dim > 1 only with cfg.HIP.TUBE_SOFT_NMS, as voting of all 4T columns)
             nms_dets, _ = soft_nms(dets_j, sigma=cfg.TEST.SOFT_NMS.SIGMA, overlap_thresh=cfg.TEST.NMS, score_thresh=0.0001,
                                    method=cfg.TEST.SOFT_NMS.METHOD)
         else:
@@ -198,14 +198,24 @@ def _tube_detections():
 
 
 
+def _soft_nms_capacity():
+    """Rows per class the device Soft-NMS holds in LDS for this config's detections: SOFT_NMS_MAX_BOXES for boxes, and for tubes what
+    their 4T coordinates leave of a workgroup's LDS (2048 up to T = 4, falling beyond)."""
+    if not _tube_detections():
+        return SOFT_NMS_MAX_BOXES
+    from detectandtrack_amd.ops.hip_ops import soft_nms_tubes_max_boxes
+    return soft_nms_tubes_max_boxes(cfg.VIDEO.NUM_FRAMES_MID)
+
+
 def device_results_supported():
-    """The device post-processing covers FASTER_RCNN with hard NMS, and TEST.SOFT_NMS / TEST.BBOX_VOTE (:766-779) for box detections.
-    Tubes with either switch stay on the host path, where Soft-NMS is the loud error the reference raises (nms_wrapper.py:34-35);
-    so does Soft-NMS over more rois per image (TEST.RPN_POST_NMS_TOP_N, the capacity of the `rois` blob) than the device kernel
-    holds: the host loop has no capacity."""
+    """The device post-processing covers FASTER_RCNN with hard NMS, and TEST.SOFT_NMS / TEST.BBOX_VOTE (:766-779) for box detections
+    and, with HIP.TUBE_SOFT_NMS, for tube detections.  Without that switch tubes with either one stay on the host path, where Soft-NMS
+    is the loud error the reference raises (nms_wrapper.py:34-35); so does Soft-NMS over more rois per image
+    (TEST.RPN_POST_NMS_TOP_N, the capacity of the `rois` blob) than the device kernel holds for the clip's T: the host loop has no
+    capacity."""
     return bool(cfg.HIP.DEVICE_BOX_RESULTS and cfg.MODEL.FASTER_RCNN and cfg.TEST.BBOX_REG and
-                not ((cfg.TEST.SOFT_NMS.ENABLED or cfg.TEST.BBOX_VOTE.ENABLED) and _tube_detections()) and
-                not (cfg.TEST.SOFT_NMS.ENABLED and cfg.TEST.RPN_POST_NMS_TOP_N > SOFT_NMS_MAX_BOXES) and
+                not ((cfg.TEST.SOFT_NMS.ENABLED or cfg.TEST.BBOX_VOTE.ENABLED) and _tube_detections() and not cfg.HIP.TUBE_SOFT_NMS) and
+                not (cfg.TEST.SOFT_NMS.ENABLED and cfg.TEST.RPN_POST_NMS_TOP_N > _soft_nms_capacity()) and
                 not cfg.TEST.SVM and not cfg.KRCNN.NMS_OKS and
                 (cfg.HIP.DEVICE_KPS_DECODE or not cfg.MODEL.KEYPOINTS_ON))
 
@@ -251,7 +261,8 @@ def enqueue_results_on_device(model, im_shape, im_scale, out_cap=None, image=Non
         # (:766-779) the reference's arguments: overlap_thresh = TEST.NMS, score_thresh = 0.0001
         soft_nms=dict(method=cfg.TEST.SOFT_NMS.METHOD, sigma=cfg.TEST.SOFT_NMS.SIGMA, score_thresh=0.0001)
         if cfg.TEST.SOFT_NMS.ENABLED else None,
-        bbox_vote=cfg.TEST.BBOX_VOTE.VOTE_TH if cfg.TEST.BBOX_VOTE.ENABLED else None)
+        bbox_vote=cfg.TEST.BBOX_VOTE.VOTE_TH if cfg.TEST.BBOX_VOTE.ENABLED else None,
+        tubes=bool(cfg.HIP.TUBE_SOFT_NMS))
     xy = None
     if cfg.MODEL.KEYPOINTS_ON:
         if image is not None:

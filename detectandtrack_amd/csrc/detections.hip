@@ -477,6 +477,271 @@ __global__ __launch_bounds__(VOTE_THREADS) void box_vote_kernel(const VoteParams
     }
 }
 
+// ---- Soft-NMS and box voting for tubes (rows of 4T coordinates + score; include/dat_hip.h) -------------
+// The tube overlap of the current maximum row a (positions a0 .. of the caller) and a row b: per frame the IoU of soft_nms_kernel,
+// the T values added in float32 in frame order from 0, divided by (float)T.  At T = 1 this is soft_nms_kernel's `ov` bit for bit
+// ((0 + x) / 1 == x).  A and B read coordinate c of the two rows.
+template <typename A, typename B>
+__device__ __forceinline__ float tube_overlap(int T, A a, B b) {
+    float sum = 0.f;
+    for (int t = 0; t < T; ++t) {
+        const float tx1 = a(4 * t + 0), ty1 = a(4 * t + 1), tx2 = a(4 * t + 2), ty2 = a(4 * t + 3);
+        const float x1 = b(4 * t + 0), y1 = b(4 * t + 1), x2 = b(4 * t + 2), y2 = b(4 * t + 3);
+        const double tarea = ((double)(tx2 - tx1) + 1.0) * ((double)(ty2 - ty1) + 1.0);
+        const float area = (float)(((double)(x2 - x1) + 1.0) * ((double)(y2 - y1) + 1.0));
+        const float iw = (float)((double)(fminf(tx2, x2) - fmaxf(tx1, x1)) + 1.0);
+        const float ih = (float)((double)(fminf(ty2, y2) - fmaxf(ty1, y1)) + 1.0);
+        float iou = 0.f;
+        if (iw > 0 && ih > 0) {
+            const float ua = (float)((tarea + (double)area) - (double)(iw * ih));
+            iou = iw * ih / ua;
+        }
+        sum = sum + iou;
+    }
+    return sum / (float)T;
+}
+
+// Dynamic LDS of soft_nms_tubes_kernel for `rows` rows (a multiple of 64): COORD [4T][rows] and SC [rows] floats, IDX [rows] ints,
+// HOLE [rows] shorts, DEAD [rows] bytes = 16T + 11 bytes a row; the per-wave arrays of the reductions are static (the compiler
+// reports 304 bytes of static LDS for the kernel).
+constexpr int SOFT_TUBE_LDS_BUDGET = 160 * 1024 - 512;      // what a gfx950 workgroup gets, less the static arrays rounded up
+inline size_t soft_tube_lds_bytes(int rows, int T) { return (size_t)rows * (16 * T + 11); }
+inline int soft_tube_capacity(int T) {
+    if (T < 1 || T > DET_MAX_T) return 0;
+    const int rows = SOFT_TUBE_LDS_BUDGET / (16 * T + 11) / 64 * 64;
+    return rows < SOFT_NMS_CAP ? rows : SOFT_NMS_CAP;
+}
+
+struct SoftTubeParams {
+    SoftParams s;           // rows [n, 4T+1]; cls_stride in floats, cap = rows per class of inds / ident
+    int T;
+    int lds_rows;           // rows the launch's dynamic LDS holds (a multiple of 64, >= every row count the block may meet)
+};
+
+// soft_nms_kernel for 4T coordinates: the same arg-max reduction, re-score and compaction; the rows live in dynamic LDS as a
+// structure of arrays [4T][lds_rows], so lane q reads consecutive words of every coordinate.  The swap of row i with the arg-max
+// row is done in LDS (one thread per column) before the re-score, which then reads row i by broadcast.
+__global__ __launch_bounds__(SOFT_THREADS) void soft_nms_tubes_kernel(const SoftTubeParams tp) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char soft_tube_lds[];
+    __shared__ float w_s[SOFT_WAVES];
+    __shared__ int w_pos[SOFT_WAVES];
+    __shared__ unsigned w_scan[SOFT_WAVES];
+    const SoftParams& p = tp.s;
+    const int T = max(1, min(tp.T, DET_MAX_T)), C4 = 4 * T, cols = C4 + 1;
+    const int L = tp.lds_rows;
+    float* COORD = (float*)soft_tube_lds;                   // [C4][L]
+    float* SC = COORD + (size_t)C4 * L;
+    int* IDX = (int*)(SC + L);
+    unsigned short* HOLE = (unsigned short*)(IDX + L);
+    unsigned char* DEAD = (unsigned char*)(HOLE + L);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int img = blockIdx.x, c = blockIdx.y;
+    const size_t ioff = (size_t)img * p.img_stride;
+    const float* src = (const float*)((const char*)p.dets + ioff) + (size_t)c * p.cls_stride;
+    float* dst = (float*)((char*)p.out + ioff) + (size_t)c * p.cls_stride;
+    int n = p.n_dev ? ((const int*)((const char*)p.n_dev + ioff))[c] : p.n_host;
+    n = max(0, min(n, min(p.cap, min(L, SOFT_NMS_CAP))));
+    for (int e = tid; e < n * cols; e += SOFT_THREADS) {
+        const int r = e / cols, cc = e - r * cols;
+        const float v = src[e];
+        if (cc < C4) COORD[cc * L + r] = v;
+        else SC[r] = v;
+    }
+    for (int r = tid; r < n; r += SOFT_THREADS) IDX[r] = r;
+    __syncthreads();
+    int N = n;
+    for (int i = 0; i < n; ++i) {              // (N only shrinks; every thread holds the same N)
+        if (i >= N) break;
+        SoftBest b = {SC[i], i};
+        for (int q = i + 1 + tid; q < N; q += SOFT_THREADS) {
+            const float s = SC[q];
+            if (b.s < s) { b.s = s; b.pos = q; }       // ascending q per thread: the strict `<` of the reference
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            SoftBest o = {__shfl_xor(b.s, off), __shfl_xor(b.pos, off)};
+            b = soft_better(b, o);
+        }
+        if (lane == 0) { w_s[wave] = b.s; w_pos[wave] = b.pos; }
+        __syncthreads();
+        SoftBest best = {w_s[0], w_pos[0]};
+#pragma unroll
+        for (int w = 1; w < SOFT_WAVES; ++w) {
+            const SoftBest o = {w_s[w], w_pos[w]};
+            best = soft_better(best, o);
+        }
+        const int maxpos = best.pos;           // i <= maxpos < N
+        // the swap of rows i and maxpos: one thread per column (4T coordinates, the score, the index)
+        if (maxpos != i) {
+            if (tid < C4) {
+                const float a = COORD[tid * L + i], m = COORD[tid * L + maxpos];
+                COORD[tid * L + i] = m; COORD[tid * L + maxpos] = a;
+            } else if (tid == C4) {
+                const float a = SC[i], m = SC[maxpos];
+                SC[i] = m; SC[maxpos] = a;
+            } else if (tid == C4 + 1) {
+                const int a = IDX[i], m = IDX[maxpos];
+                IDX[i] = m; IDX[maxpos] = a;
+            }
+        }
+        __syncthreads();                       // (also: w_s / w_pos are not written again before every thread has read them)
+        int ndead_local = 0;                   // (a flag: did this thread remove a row)
+        for (int q = i + 1 + tid; q < N; q += SOFT_THREADS) {
+            float s = SC[q];
+            const float ov = tube_overlap(T, [&](int cc) { return COORD[cc * L + i]; }, [&](int cc) { return COORD[cc * L + q]; });
+            bool dead = false;
+            if (ov > 0) {                      // (T = 1: iw > 0 && ih > 0 -- there ua >= both areas > 0 and iw * ih > 0)
+                float weight;
+                if (p.method == 1) weight = ov > p.Nt ? (float)(1.0 - (double)ov) : 1.f;
+                else if (p.method == 2) weight = (float)exp((double)(-(ov * ov) / p.sigma));
+                else weight = ov > p.Nt ? 0.f : 1.f;
+                s = weight * s;
+                dead = s < p.threshold;
+            }
+            SC[q] = s;
+            DEAD[q] = dead ? 1 : 0;
+            ndead_local |= dead ? 1 : 0;
+        }
+        // (the barrier also orders this iteration's LDS writes before the next iteration's reads)
+        if (!__syncthreads_or(ndead_local)) continue;
+        // ---- compaction, as in soft_nms_kernel: holes below N' (ascending) <- survivors at >= N' (descending)
+        const int span = N - (i + 1);
+        const int per = (span + SOFT_THREADS - 1) / SOFT_THREADS;
+        const int lo = min(N, i + 1 + tid * per), hi = min(N, lo + per);
+        unsigned cnt = 0;
+        for (int q = lo; q < hi; ++q) cnt += DEAD[q];
+        unsigned incl = cnt;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned u = __shfl_up(incl, off);
+            if (lane >= off) incl += u;
+        }
+        if (lane == 63) w_scan[wave] = incl;
+        __syncthreads();
+        unsigned before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < SOFT_WAVES; ++w) {
+            if (w < wave) before += w_scan[w];
+            total += w_scan[w];
+        }
+        const int ndead = (int)total;
+        const int N2 = N - ndead;
+        int rank = (int)(before + incl - cnt);             // removed rows before position lo
+        for (int q = lo; q < hi; ++q) {
+            if (DEAD[q]) {
+                if (q < N2) HOLE[rank] = (unsigned short)q;
+                ++rank;
+            }
+        }
+        __syncthreads();
+        rank = (int)(before + incl - cnt);
+        for (int q = lo; q < hi; ++q) {
+            if (DEAD[q]) { ++rank; continue; }
+            if (q >= N2) {
+                // the highest survivor fills the lowest hole; the slot index is in [0, #holes) for every consistent arrangement and
+                // is clamped to the rows in LDS for any other
+                const int slot = min(max((N - 1 - q) - (ndead - rank), 0), L - 1);
+                const int h = min((int)HOLE[slot], L - 1);
+                for (int cc = 0; cc < C4; ++cc) COORD[cc * L + h] = COORD[cc * L + q];
+                SC[h] = SC[q]; IDX[h] = IDX[q];
+            }
+        }
+        N = N2;
+        __syncthreads();
+    }
+    for (int e = tid; e < N * cols; e += SOFT_THREADS) {
+        const int r = e / cols, cc = e - r * cols;
+        dst[e] = cc < C4 ? COORD[cc * L + r] : SC[r];
+    }
+    for (int r = tid; r < N; r += SOFT_THREADS) {
+        if (p.inds) ((int*)((char*)p.inds + ioff))[(size_t)c * p.cap + r] = IDX[r];
+        if (p.ident) ((int*)((char*)p.ident + ioff))[(size_t)c * p.cap + r] = r;
+    }
+    if (tid == 0) ((int*)((char*)p.n_out + ioff))[c] = N;
+}
+
+// box_vote_kernel for 4T coordinates: one wave per kept row, whose coordinate l stays in lane l's register for the whole row (the
+// overlap reads it by a lane broadcast), so the row may be overwritten in place.  The 4T + 1 double sums are formed VOTE_CHUNK
+// frames at a time (16 coordinate sums + the weight sum in registers); a row of more than VOTE_CHUNK frames walks the voters once
+// per chunk and finds the same voter set each time (the overlap depends on registers and on `all` only).
+constexpr int VOTE_CHUNK = 4;
+
+struct VoteTubeParams {
+    VoteParams v;           // rows [., 4T+1]
+    int T;
+};
+
+__global__ __launch_bounds__(VOTE_THREADS) void box_vote_tubes_kernel(const VoteTubeParams tp) {
+    const VoteParams& p = tp.v;
+    const int T = max(1, min(tp.T, DET_MAX_T)), C4 = 4 * T, cols = C4 + 1;
+    const int lane = threadIdx.x & 63;
+    const int img = blockIdx.x, c = blockIdx.y;
+    const size_t ioff = (size_t)img * p.img_stride;
+    const size_t coff = (size_t)c * p.cls_stride;
+    const float* top = (const float*)((const char*)p.top + ioff) + coff;
+    const float* all = (const float*)((const char*)p.all + ioff) + coff;
+    float* out = (float*)((char*)p.out + ioff) + coff;
+    const int n_top = p.n_top ? ((const int*)((const char*)p.n_top + ioff))[c] : p.n_top_host;
+    const int n_all = p.n_all ? ((const int*)((const char*)p.n_all + ioff))[c] : p.n_all_host;
+    const int* keep = p.keep ? (const int*)((const char*)p.keep + ioff) + (size_t)c * p.cap : nullptr;
+    int* ident = p.ident ? (int*)((char*)p.ident + ioff) + (size_t)c * p.cap : nullptr;
+    const int wpb = VOTE_THREADS / 64;
+    for (int k = blockIdx.z * wpb + (threadIdx.x >> 6); k < n_top; k += gridDim.z * wpb) {      // (k is the same in every lane of a wave)
+        const float* t = top + (size_t)(keep ? keep[k] : k) * cols;
+        const float mine = lane < C4 ? t[lane] : 0.f;          // lane l: coordinate l of the kept row (4T <= 64 lanes)
+        const float bs = t[C4];
+        for (int f0 = 0; f0 < T; f0 += VOTE_CHUNK) {
+            const int c0 = 4 * f0;
+            double sw = 0., sc[4 * VOTE_CHUNK];
+#pragma unroll
+            for (int j = 0; j < 4 * VOTE_CHUNK; ++j) sc[j] = 0.;
+            // every lane runs every trip (the broadcasts below read all lanes); a lane past n_all votes with nothing
+            for (int m0 = 0; m0 < n_all; m0 += 64) {
+                const int m = m0 + lane;
+                const bool valid = m < n_all;
+                const float* q = all + (size_t)(valid ? m : 0) * cols;
+                const float ov = tube_overlap(T, [&](int cc) { return __shfl(mine, cc); }, [&](int cc) { return q[cc]; });
+                if (valid && ov >= p.thresh) {
+                    const double dw = (double)q[C4];
+                    sw += dw;
+#pragma unroll
+                    for (int j = 0; j < 4 * VOTE_CHUNK; ++j)
+                        if (c0 + j < C4) sc[j] += dw * (double)q[c0 + j];
+                }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                sw += __shfl_xor(sw, off);
+#pragma unroll
+                for (int j = 0; j < 4 * VOTE_CHUNK; ++j) sc[j] += __shfl_xor(sc[j], off);
+            }
+            // In-place use, as in box_vote_kernel: `out` may be `top` and `ident` may be `keep`.  Only this wave touches row k of either,
+            // every lane has loaded its word of t[] and keep[k] before the first butterfly, and no later chunk reads t[] again.
+            if (lane == 0) {
+                float* o = out + (size_t)k * cols;
+#pragma unroll
+                for (int j = 0; j < 4 * VOTE_CHUNK; ++j)
+                    if (c0 + j < C4) o[c0 + j] = (float)(sc[j] / sw);
+            }
+        }
+        if (lane == 0) {
+            out[(size_t)k * cols + C4] = bs;
+            if (ident) ident[k] = k;
+        }
+    }
+}
+
+// max_rows: the most rows a block of this launch may meet (checked against the capacity by the callers)
+int launch_soft_nms_tubes(dat_ctx* ctx, hipStream_t st, const SoftParams& sp, int T, int max_rows, dim3 grid) {
+    SoftTubeParams tp;
+    tp.s = sp; tp.T = T;
+    tp.lds_rows = min(soft_tube_capacity(T), max(64, (max_rows + 63) / 64 * 64));
+    const int rc = dat_ensure_lds(ctx, (const void*)soft_nms_tubes_kernel, SOFT_TUBE_LDS_BUDGET);
+    if (rc != DAT_OK) return rc;
+    hipLaunchKernelGGL(soft_nms_tubes_kernel, grid, dim3(SOFT_THREADS), soft_tube_lds_bytes(tp.lds_rows, T), st, tp);
+    return DAT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -510,11 +775,11 @@ static int box_results_impl(dat_ctx* ctx, dat_stream s, const float* rois, const
     const int nc = d->num_classes - 1, T = d->T, cols = 4 * T + 1;
     const bool soft = o && o->soft_nms_enabled, vote = o && o->bbox_vote_enabled;
     if (soft || vote) {
-        DAT_ENFORCE(ctx, T == 1, "box_results: Soft-NMS / box voting are defined for boxes, not for tubes of %d frames", T);
+        DAT_ENFORCE(ctx, T == 1 || o->tubes_enabled, "box_results: Soft-NMS / box voting are defined for boxes, not for tubes of %d frames", T);
         DAT_ENFORCE(ctx, !soft || (o->soft_nms_method >= 0 && o->soft_nms_method <= 2), "box_results: Soft-NMS method %d (0 hard, 1 linear, 2 gaussian)",
                     soft ? o->soft_nms_method : 0);
-        DAT_ENFORCE(ctx, !soft || roi_cap <= SOFT_NMS_CAP, "box_results: Soft-NMS holds a class's rows in LDS: roi capacity %d > %d", roi_cap,
-                    SOFT_NMS_CAP);
+        DAT_ENFORCE(ctx, !soft || roi_cap <= soft_tube_capacity(T), "box_results: Soft-NMS holds a class's rows in LDS: roi capacity %d > %d", roi_cap,
+                    soft_tube_capacity(T));
     }
     const size_t img_ws = dat_box_results_ex_workspace_bytes(roi_cap, d->num_classes, T, o);
     char* ws = (char*)workspace;
@@ -557,7 +822,8 @@ static int box_results_impl(dat_ctx* ctx, dat_stream s, const float* rois, const
         sp.dets = dets; sp.n_dev = n_sel; sp.out = rows2; sp.ident = keep; sp.n_out = n_keep; sp.img_stride = img_ws;
         sp.cls_stride = roi_cap * cols; sp.cap = roi_cap; sp.method = o->soft_nms_method; sp.sigma = o->soft_nms_sigma;
         sp.Nt = d->nms_thresh; sp.threshold = o->soft_nms_score_thresh;
-        hipLaunchKernelGGL(soft_nms_kernel, dim3(ni, nc), dim3(SOFT_THREADS), 0, st, sp);
+        if (T == 1) hipLaunchKernelGGL(soft_nms_kernel, dim3(ni, nc), dim3(SOFT_THREADS), 0, st, sp);
+        else if (int rc = launch_soft_nms_tubes(ctx, st, sp, T, roi_cap, dim3(ni, nc))) return rc;
     }
     if (vote) {
         // (test.py:776-779) the kept rows -- dets[keep] after the NMS, rows2 after Soft-NMS -- voted by the class's selected rows
@@ -566,7 +832,12 @@ static int box_results_impl(dat_ctx* ctx, dat_stream s, const float* rois, const
         vp.top = soft ? rows2 : dets; vp.keep = soft ? nullptr : keep; vp.n_top = n_keep; vp.all = dets; vp.n_all = n_sel;
         vp.out = rows2; vp.ident = soft ? nullptr : keep; vp.img_stride = img_ws; vp.cls_stride = roi_cap * cols; vp.cap = roi_cap;
         vp.thresh = o->bbox_vote_thresh;
-        hipLaunchKernelGGL(box_vote_kernel, dim3(ni, nc, VOTE_BLOCKS), dim3(VOTE_THREADS), 0, st, vp);
+        if (T == 1) hipLaunchKernelGGL(box_vote_kernel, dim3(ni, nc, VOTE_BLOCKS), dim3(VOTE_THREADS), 0, st, vp);
+        else {
+            VoteTubeParams vt;
+            vt.v = vp; vt.T = T;
+            hipLaunchKernelGGL(box_vote_tubes_kernel, dim3(ni, nc, VOTE_BLOCKS), dim3(VOTE_THREADS), 0, st, vt);
+        }
     }
     e.dets = (soft || vote) ? rows2 : dets; e.keep = keep; e.n_keep = n_keep; e.K = d->num_classes; e.T = T; e.cap = roi_cap; e.D = d->detections_per_im;
     e.out_cap = out_cap; e.img_ws = img_ws; e.dets_out = dets_out; e.kp_rois = keypoint_rois; e.n_out = n_out;
@@ -617,6 +888,43 @@ int dat_box_voting(dat_ctx* ctx, dat_stream s, const float* top_dets, int n_top,
     const int blocks = min((n_top + VOTE_THREADS / 64 - 1) / (VOTE_THREADS / 64), 1024);
     hipLaunchKernelGGL(box_vote_kernel, dim3(1, 1, blocks), dim3(VOTE_THREADS), 0, (hipStream_t)s, vp);
     DAT_CHECK_LAUNCH(ctx, "box_voting");
+    return DAT_OK;
+}
+
+int dat_soft_nms_tubes_max_boxes(int T) { return soft_tube_capacity(T); }
+
+// Soft-NMS of n <= dat_soft_nms_tubes_max_boxes(T) device rows [n, 4T+1]: the device twin of dat_soft_nms_tubes_host below.
+int dat_soft_nms_tubes(dat_ctx* ctx, dat_stream s, const float* dets, int n, int T, float sigma, float Nt, float threshold, int method,
+                       float* dets_out, int* inds_out, int* n_out) {
+    DAT_ENFORCE(ctx, dets_out && inds_out && n_out && (dets || n == 0), "soft_nms_tubes: null argument");
+    DAT_ENFORCE(ctx, T >= 1 && T <= DET_MAX_T, "soft_nms_tubes: T %d (1..%d)", T, DET_MAX_T);
+    DAT_ENFORCE(ctx, n >= 0 && n <= soft_tube_capacity(T), "soft_nms_tubes: %d tubes of %d frames (0..%d: the rows stay in LDS)", n, T,
+                soft_tube_capacity(T));
+    DAT_ENFORCE(ctx, method >= 0 && method <= 2, "soft_nms_tubes: method %d (0 hard, 1 linear, 2 gaussian)", method);
+    SoftParams sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.dets = dets; sp.n_host = n; sp.out = dets_out; sp.inds = inds_out; sp.n_out = n_out; sp.cap = soft_tube_capacity(T);
+    sp.method = method; sp.sigma = sigma; sp.Nt = Nt; sp.threshold = threshold;
+    const int rc = launch_soft_nms_tubes(ctx, (hipStream_t)s, sp, T, n, dim3(1, 1));
+    if (rc != DAT_OK) return rc;
+    DAT_CHECK_LAUNCH(ctx, "soft_nms_tubes");
+    return DAT_OK;
+}
+
+// Voting of n_top device rows [n_top, 4T+1] by n_all device rows [n_all, 4T+1] -> out [n_top, 4T+1] (out may be top_dets).
+int dat_box_voting_tubes(dat_ctx* ctx, dat_stream s, const float* top_dets, int n_top, const float* all_dets, int n_all, int T, float thresh,
+                         float* out) {
+    DAT_ENFORCE(ctx, n_top >= 0 && n_all >= 0 && (n_top == 0 || (top_dets && all_dets && out)), "box_voting_tubes: null argument or negative count");
+    DAT_ENFORCE(ctx, T >= 1 && T <= DET_MAX_T, "box_voting_tubes: T %d (1..%d)", T, DET_MAX_T);
+    if (n_top == 0) return DAT_OK;
+    DAT_ENFORCE(ctx, n_all >= 1, "box_voting_tubes: %d rows to refine and no row to vote with (the weight sum would be zero)", n_top);
+    VoteTubeParams vt;
+    memset(&vt, 0, sizeof(vt));
+    vt.v.top = top_dets; vt.v.all = all_dets; vt.v.out = out; vt.v.n_top_host = n_top; vt.v.n_all_host = n_all; vt.v.thresh = thresh;
+    vt.T = T;
+    const int blocks = min((n_top + VOTE_THREADS / 64 - 1) / (VOTE_THREADS / 64), 1024);
+    hipLaunchKernelGGL(box_vote_tubes_kernel, dim3(1, 1, blocks), dim3(VOTE_THREADS), 0, (hipStream_t)s, vt);
+    DAT_CHECK_LAUNCH(ctx, "box_voting_tubes");
     return DAT_OK;
 }
 
@@ -673,6 +981,70 @@ int dat_soft_nms_host(const float* boxes_in, int n, float sigma, float Nt, float
                         --N;
                         --pos;
                     }
+                }
+            }
+            ++pos;
+        }
+    }
+    *n_out = N;
+    return DAT_OK;
+}
+
+// dat_soft_nms_host for rows [n, 4T+1] (include/dat_hip.h): the same serial loop, the per-pair overlap being the float32 mean of the
+// per-frame IoUs in frame order, and a pair re-scored iff that overlap is > 0.  Plain host code: the comparison path of
+// dat_soft_nms_tubes and what core/nms_wrapper.soft_nms runs for tube rows with HIP.TUBE_SOFT_NMS.
+int dat_soft_nms_tubes_host(const float* boxes_in, int n, int T, float sigma, float Nt, float threshold, int method, float* boxes_out,
+                            int* inds_out, int* n_out) {
+    if (!boxes_in || !boxes_out || !inds_out || !n_out || n < 0 || method < 0 || method > 2 || T < 1 || T > DET_MAX_T) return DAT_ERR_ARG;
+    const int C4 = 4 * T, cols = C4 + 1;
+    float* b = boxes_out;
+    memcpy(b, boxes_in, (size_t)n * cols * sizeof(float));
+    for (int i = 0; i < n; ++i) inds_out[i] = i;
+    int N = n;
+    float tmp[4 * DET_MAX_T + 1];
+    for (int i = 0; i < N; ++i) {
+        float maxscore = b[(size_t)i * cols + C4];
+        int maxpos = i;
+        for (int pos = i + 1; pos < N; ++pos)
+            if (maxscore < b[(size_t)pos * cols + C4]) { maxscore = b[(size_t)pos * cols + C4]; maxpos = pos; }
+        memcpy(tmp, b + (size_t)i * cols, cols * sizeof(float));
+        const int ti = inds_out[i];
+        memmove(b + (size_t)i * cols, b + (size_t)maxpos * cols, cols * sizeof(float));
+        inds_out[i] = inds_out[maxpos];
+        memcpy(b + (size_t)maxpos * cols, tmp, cols * sizeof(float));
+        inds_out[maxpos] = ti;
+        const float* a = b + (size_t)i * cols;
+        int pos = i + 1;
+        while (pos < N) {
+            float* r = b + (size_t)pos * cols;
+            float sum = 0.f;
+            for (int t = 0; t < T; ++t) {
+                const float tx1 = a[4 * t], ty1 = a[4 * t + 1], tx2 = a[4 * t + 2], ty2 = a[4 * t + 3];
+                const float x1 = r[4 * t], y1 = r[4 * t + 1], x2 = r[4 * t + 2], y2 = r[4 * t + 3];
+                const float area = (float)(((double)(x2 - x1) + 1.0) * ((double)(y2 - y1) + 1.0));
+                const float iw = (float)((double)(fminf(tx2, x2) - fmaxf(tx1, x1)) + 1.0);
+                float iou = 0.f;
+                if (iw > 0) {
+                    const float ih = (float)((double)(fminf(ty2, y2) - fmaxf(ty1, y1)) + 1.0);
+                    if (ih > 0) {
+                        const float ua = (float)((((double)(tx2 - tx1) + 1.0) * ((double)(ty2 - ty1) + 1.0) + (double)area) - (double)(iw * ih));
+                        iou = iw * ih / ua;
+                    }
+                }
+                sum = sum + iou;
+            }
+            const float ov = sum / (float)T;
+            if (ov > 0) {
+                float weight;
+                if (method == 1) weight = ov > Nt ? (float)(1.0 - (double)ov) : 1.f;
+                else if (method == 2) weight = (float)exp((double)(-(ov * ov) / sigma));
+                else weight = ov > Nt ? 0.f : 1.f;
+                r[C4] = weight * r[C4];
+                if (r[C4] < threshold) {        // discard: swap with the last row, shrink N, revisit this slot
+                    memmove(r, b + (size_t)(N - 1) * cols, cols * sizeof(float));
+                    inds_out[pos] = inds_out[N - 1];
+                    --N;
+                    --pos;
                 }
             }
             ++pos;

@@ -64,7 +64,8 @@ class DetDesc(C.Structure):
 
 class DetOpts(C.Structure):
     _fields_ = [('soft_nms_enabled', C.c_int), ('soft_nms_method', C.c_int), ('soft_nms_sigma', C.c_float),
-                ('soft_nms_score_thresh', C.c_float), ('bbox_vote_enabled', C.c_int), ('bbox_vote_thresh', C.c_float)]
+                ('soft_nms_score_thresh', C.c_float), ('bbox_vote_enabled', C.c_int), ('bbox_vote_thresh', C.c_float),
+                ('tubes_enabled', C.c_int)]
 
 
 class RpnLevel(C.Structure):
@@ -145,6 +146,10 @@ _PROTOS = {
     'dat_soft_nms': (_i, [_p, _p, _p, _i, _f, _f, _f, _i, _p, _p, _p]),
     'dat_box_voting': (_i, [_p, _p, _p, _i, _p, _i, _f, _p]),
     'dat_soft_nms_host': (_i, [C.POINTER(_f), _i, _f, _f, _f, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
+    'dat_soft_nms_tubes_max_boxes': (_i, [_i]),
+    'dat_soft_nms_tubes': (_i, [_p, _p, _p, _i, _i, _f, _f, _f, _i, _p, _p, _p]),
+    'dat_soft_nms_tubes_host': (_i, [C.POINTER(_f), _i, _i, _f, _f, _f, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
+    'dat_box_voting_tubes': (_i, [_p, _p, _p, _i, _p, _i, _i, _f, _p]),
     'dat_deconv_k4s2_weights': (_i, [_p, _p, _p, _i, _i, _p]),
     'dat_kps_finalize': (_i, [_p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
     'dat_stem_conv_weight_bytes': (C.c_size_t, [_i]),

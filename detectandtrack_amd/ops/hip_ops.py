@@ -1187,8 +1187,44 @@ def box_voting(top_dets, all_dets, thresh):
     return out
 
 
+def soft_nms_tubes_max_boxes(T):
+    """dat_soft_nms_tubes_max_boxes: the rows of 4T coordinates the tube Soft-NMS kernel holds in LDS (2048 for T <= 4, falling with T;
+    0 for T outside 1..16)."""
+    return int(L.lib().dat_soft_nms_tubes_max_boxes(int(T)))
+
+
+def soft_nms_tubes(dets, T, sigma=0.5, overlap_thresh=0.3, score_thresh=0.001, method='linear'):
+    """dat_soft_nms_tubes (Soft-NMS with the mean per-frame IoU as the overlap): dets CUDA fp32
+    [n <= soft_nms_tubes_max_boxes(T), 4T+1]; returns (re-scored rows [n, 4T+1], original row indices int32 [n], count int32[1]) on the
+    device, as soft_nms does."""
+    T = int(T)
+    assert dets.dim() == 2 and dets.shape[1] == 4 * T + 1 and dets.dtype == torch.float32
+    m = SOFT_NMS_METHODS[method] if isinstance(method, str) else int(method)
+    n = int(dets.shape[0])
+    out = torch.empty((max(n, 1), 4 * T + 1), dtype=torch.float32, device=dets.device)
+    inds = torch.empty((max(n, 1),), dtype=torch.int32, device=dets.device)
+    cnt = torch.empty((1,), dtype=torch.int32, device=dets.device)
+    ctx().call('dat_soft_nms_tubes', _stream(), _ptr(dets.contiguous()), n, T, C.c_float(sigma), C.c_float(overlap_thresh),
+               C.c_float(score_thresh), m, _ptr(out), _ptr(inds), _ptr(cnt))
+    return out[:n], inds[:n], cnt
+
+
+def box_voting_tubes(top_dets, all_dets, T, thresh, out=None):
+    """dat_box_voting_tubes: CUDA fp32 [n_top, 4T+1], [n_all, 4T+1] -> voted rows [n_top, 4T+1] (all 4T coordinates; the score stays).
+    out: optional destination; it may be top_dets itself (in place)."""
+    T = int(T)
+    assert top_dets.dtype == all_dets.dtype == torch.float32 and top_dets.shape[1] == all_dets.shape[1] == 4 * T + 1
+    top_dets = top_dets.contiguous()
+    if out is None:
+        out = torch.empty_like(top_dets)
+    assert out.is_contiguous() and out.shape == top_dets.shape and out.dtype == torch.float32
+    ctx().call('dat_box_voting_tubes', _stream(), _ptr(top_dets), int(top_dets.shape[0]), _ptr(all_dets.contiguous()),
+               int(all_dets.shape[0]), T, C.c_float(thresh), _ptr(out))
+    return out
+
+
 def box_results(rois, n_rois, cls_prob, bbox_pred, num_classes, T, im_scale, im_shape, reg_weights, xform_clip, score_thresh,
-                nms_thresh, detections_per_im, out_cap, cls_agnostic=False, n_images=1, soft_nms=None, bbox_vote=None):
+                nms_thresh, detections_per_im, out_cap, cls_agnostic=False, n_images=1, soft_nms=None, bbox_vote=None, tubes=False):
     """dat_box_results (lib/core/test.py:215-252, 750-806, 78-123 on the device).  rois CUDA fp32 [cap, 4T+1] with the DEVICE count
     n_rois (int32[1]); cls_prob [R, K], bbox_pred [R, K*4T] CUDA fp32.  Returns (dets [out_cap, 4T+2], keypoint_rois [out_cap, 4T+1],
     n_out int32[2]) on the device -- no host synchronisation.  n_images > 1 (dat_box_results_batch): rois [n_images * cap, ...] with
@@ -1196,7 +1232,7 @@ def box_results(rois, n_rois, cls_prob, bbox_pred, num_classes, T, im_scale, im_
     [n_images * out_cap, 4T+1] (col 0 = image index) and n_out int32[n_images, 2].
     soft_nms: None | dict(method='hard'|'linear'|'gaussian', sigma, score_thresh) -- TEST.SOFT_NMS in place of the NMS (overlap
     threshold = nms_thresh; detections carry the re-scored scores); bbox_vote: None | the voting IoU threshold (TEST.BBOX_VOTE).
-    Either one routes to dat_box_results_ex (boxes only: T == 1)."""
+    Either one routes to dat_box_results_ex (T == 1, or any T with tubes=True -- cfg.HIP.TUBE_SOFT_NMS: the tube kernels)."""
     ni = int(n_images)
     cap = int(rois.shape[0]) // ni
     assert cap * ni == int(rois.shape[0])
@@ -1218,6 +1254,7 @@ def box_results(rois, n_rois, cls_prob, bbox_pred, num_classes, T, im_scale, im_
     opts = None
     if soft_nms is not None or bbox_vote is not None:
         opts = L.DetOpts()
+        opts.tubes_enabled = int(bool(tubes))
         if soft_nms is not None:
             m = soft_nms.get('method', 'linear')
             opts.soft_nms_enabled, opts.soft_nms_method = 1, SOFT_NMS_METHODS[m] if isinstance(m, str) else int(m)

@@ -127,9 +127,31 @@ def clip_tiled_boxes(boxes, im_shape):
     return boxes
 
 
+def tube_overlaps(tubes, query_tubes):
+    """Pairwise tube overlap of (N, 4T) vs (K, 4T) rows as Soft-NMS and box voting for tubes define it: the
+    per-frame float32 IoUs of _iou_matrix added in float32 IN FRAME ORDER starting from 0, divided by float32(T) -- an explicit
+    loop, not np.mean, whose reduction order is NumPy's business."""
+    parts, T = split_tube_into_boxes(tubes)
+    qparts, _ = split_tube_into_boxes(query_tubes)
+    total = np.zeros((tubes.shape[0], query_tubes.shape[0]), dtype=np.float32)
+    for p, q in zip(parts, qparts):
+        total = total + _iou_matrix(p, q)
+    return total / np.float32(T)
+
+
 def box_voting(top_dets, all_dets, thresh):
     """Refine `top_dets` [N, 5] by score-weighted averaging of the `all_dets` boxes that overlap each by >= thresh (:294-310,
-    https://arxiv.org/abs/1505.01749)."""
+    https://arxiv.org/abs/1505.01749).  Tube rows [N, 4T+1] with cfg.HIP.TUBE_SOFT_NMS: all 4T coordinates are voted, by the rows
+    whose tube_overlaps with the kept row is >= thresh (without the switch, the reference's behaviour: the first four columns)."""
+    if top_dets.shape[1] > 5 and cfg.HIP.TUBE_SOFT_NMS:
+        out = top_dets.copy()
+        nc = top_dets.shape[1] - 1
+        overlaps = tube_overlaps(top_dets[:, :nc], all_dets[:, :nc])
+        for k in range(out.shape[0]):
+            vote = np.where(overlaps[k] >= thresh)[0]
+            # float64 sums rounded once, as the device kernel forms them
+            out[k, :nc] = np.average(all_dets[vote, :nc].astype(np.float64), axis=0, weights=all_dets[vote, nc].astype(np.float64))
+        return out
     out = top_dets.copy()
     all_boxes, all_scores = all_dets[:, :4], all_dets[:, 4]
     overlaps = bbox_overlaps(top_dets[:, :4], all_boxes)

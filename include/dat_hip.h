@@ -363,7 +363,8 @@ int dat_box_results_batch(dat_ctx* ctx, dat_stream s, const float* rois, const i
 /* ---- Soft-NMS and box voting on the device (lib/core/test.py:766-779) ----------------------------------------------------------
  * Soft-NMS keeps a class's rows in LDS for the whole greedy loop (one block per image and class), so it accepts at most
  * DAT_SOFT_NMS_MAX_BOXES rows (2048 x 27 bytes = 54 KB of the 64 KB a block may declare; the reference's TEST.RPN_POST_NMS_TOP_N
- * is 1000); more is a DAT_ERR_ARG.  Boxes only (T = 1): the reference has no Soft-NMS for tubes (lib/core/nms_wrapper.py:34-35). */
+ * is 1000); more is a DAT_ERR_ARG.  These entry points take boxes only (T = 1): the reference has no Soft-NMS for tubes
+ * (lib/core/nms_wrapper.py:34-35); this project's definition for tubes has entry points of its own, further below. */
 #define DAT_SOFT_NMS_MAX_BOXES 2048
 /* The device twin of dat_soft_nms_host: dets fp32 [n, 5] -> dets_out [*n_out <= n, 5] (re-scored, in the order the greedy loop leaves
  * them), inds_out (rows of dets), n_out int32[1]; all DEVICE pointers, buffers of n rows, no host synchronisation.  method 0 = hard,
@@ -381,7 +382,8 @@ int dat_box_voting(dat_ctx* ctx, dat_stream s, const float* top_dets, int n_top,
  * dat_det_desc.nms_thresh, as the reference passes TEST.NMS) and the detections carry the RE-SCORED scores, on which the
  * DETECTIONS_PER_IM rule (and n_out[1]) then works; voting replaces the kept boxes' coordinates, and keypoint_rois are formed from
  * the voted boxes.  With both switches off this IS dat_box_results_batch (same code, same workspace size, byte-identical outputs).
- * Requires T == 1 when a switch is on, and roi_cap <= DAT_SOFT_NMS_MAX_BOXES with Soft-NMS.  workspace: n_images x
+ * Requires T == 1 when a switch is on unless tubes_enabled is set (then T <= 16 and the tube kernels below run), and
+ * roi_cap <= dat_soft_nms_tubes_max_boxes(T) with Soft-NMS (= DAT_SOFT_NMS_MAX_BOXES for T <= 4).  workspace: n_images x
  * dat_box_results_ex_workspace_bytes. */
 typedef struct {
     int soft_nms_enabled;         /* TEST.SOFT_NMS.ENABLED */
@@ -390,6 +392,7 @@ typedef struct {
     float soft_nms_score_thresh;  /* rows re-scored below it are dropped (the reference passes 0.0001) */
     int bbox_vote_enabled;        /* TEST.BBOX_VOTE.ENABLED */
     float bbox_vote_thresh;       /* TEST.BBOX_VOTE.VOTE_TH */
+    int tubes_enabled;            /* HIP.TUBE_SOFT_NMS: accept T > 1 with a switch on (0: the DAT_ERR_ARG the box-only code gives) */
 } dat_det_opts;
 size_t dat_box_results_ex_workspace_bytes(int roi_cap, int num_classes, int T, const dat_det_opts* o);
 int dat_box_results_ex(dat_ctx* ctx, dat_stream s, const float* rois, const int* n_rois, int roi_cap, const float* cls_prob, int prob_ld,
@@ -401,6 +404,30 @@ int dat_box_results_ex(dat_ctx* ctx, dat_stream s, const float* rois, const int*
  * method 0 = hard, 1 = linear, 2 = gaussian (nms_wrapper.py:37).  Buffers hold n rows.  The comparison path of dat_soft_nms. */
 int dat_soft_nms_host(const float* boxes_in, int n, float sigma, float Nt, float threshold, int method, float* boxes_out,
                       int* inds_out, int* n_out);
+
+/* ---- Soft-NMS and box voting for TUBES (rows of 4T coordinates + score) -------------------------------
+ * The reference defines neither (lib/core/nms_wrapper.py:34-35 raises, lib/utils/boxes.py:294-310 votes four columns); this
+ * project does, with the tube overlap the reference's tube NMS uses (lib/nms/py_cpu_nms_tubes.py, lib/utils/boxes.py:60-69): the
+ * mean of the per-frame IoUs.  ov(a, b): per frame the IoU in the arithmetic of dat_soft_nms_host (a = the current maximum row,
+ * its area in double; 0 when iw <= 0 or ih <= 0), the T values summed in float32 in frame order from 0 and divided by (float)T.
+ * Soft-NMS is the loop of dat_soft_nms_host with that overlap, a pair being re-scored iff ov > 0; at T = 1 it IS that loop, bit
+ * for bit, and with method 0 it keeps the rows py_cpu_nms_tubes keeps, in its order.  Voting replaces ALL 4T coordinates of a
+ * kept row by the score-weighted means over the rows whose ov with it (the kept row in a's role) is >= thresh.
+ *
+ * The device kernel keeps a class's rows in dynamic LDS, 16T + 11 bytes each, within the 160 KB of a gfx950 workgroup:
+ * dat_soft_nms_tubes_max_boxes(T) = the largest multiple of 64 that fits, at most DAT_SOFT_NMS_MAX_BOXES (2048 for T <= 4, 1792 for
+ * T = 5, 1024 for T = 9, 576 for T = 16); 0 for T outside 1..16. */
+int dat_soft_nms_tubes_max_boxes(int T);
+/* dat_soft_nms for rows [n, 4T+1] (1 <= T <= 16); n above dat_soft_nms_tubes_max_boxes(T) is a DAT_ERR_ARG.  DEVICE pointers, buffers
+ * of n rows; bit-identical to dat_soft_nms_tubes_host for methods 0 and 1, scores within one float ulp per re-scoring for method 2. */
+int dat_soft_nms_tubes(dat_ctx* ctx, dat_stream s, const float* dets, int n, int T, float sigma, float Nt, float threshold, int method,
+                       float* dets_out, int* inds_out, int* n_out);
+/* The host twin in C float arithmetic (HOST pointers): the comparison path, and what core/nms_wrapper.soft_nms runs for tube rows. */
+int dat_soft_nms_tubes_host(const float* boxes_in, int n, int T, float sigma, float Nt, float threshold, int method, float* boxes_out,
+                            int* inds_out, int* n_out);
+/* dat_box_voting for rows [., 4T+1]: out [n_top, 4T+1] (may be top_dets; must not overlap all_dets).  Sums in double in a fixed order. */
+int dat_box_voting_tubes(dat_ctx* ctx, dat_stream s, const float* top_dets, int n_top, const float* all_dets, int n_all, int T, float thresh,
+                         float* out);
 
 /* ---- keypoint head tail: ConvTranspose k4s2p1 (as 3x3 sub-pixel conv) + bilinear up (detector.py:348-380) -- */
 /* Expand kps_score_lowres_w fp32 [Cin, K, 4, 4] (Caffe2 ConvTranspose layout) into an equivalent 3x3 conv

@@ -1,6 +1,7 @@
 """Soft-NMS / box voting on the device: what they cost.
 
-    python tools/probes/soft_nms_ab.py [rois per image] [images per launch]
+    python tools/probes/soft_nms_ab.py [rois per image] [images per launch] [frames per tube]
+        (frames per tube > 1: tube detections through the kernels of HIP.TUBE_SOFT_NMS)
         ops.box_results (select + decode, NMS or Soft-NMS, voting, limit + emit) with each Soft-NMS method and with voting against
         hard NMS on the same clustered synthetic proposals: hip events, median of 50 launches after 10 warm-up launches.
     python tools/probes/soft_nms_ab.py e2e <tree> [cfg opts ...]
@@ -50,16 +51,19 @@ def e2e(root, opts):
                       'steady_clips_per_s': st.get('steady_clips_per_s') if st else None}))
 
 
-def inputs(seed, R, K, H=720, W=1280):
+def inputs(seed, R, K, H=720, W=1280, T=1):
     rs = np.random.RandomState(seed)
     centres = np.stack([rs.uniform(100, W - 300, 12), rs.uniform(100, H - 300, 12)], axis=1)
     xy = centres[rs.randint(0, 12, R)] + rs.uniform(-40, 40, (R, 2))
     wh = rs.uniform(60, 260, (R, 2))
-    rois = np.zeros((R, 5), np.float32)
+    rois = np.zeros((R, 4 * T + 1), np.float32)
     rois[:, 1:3], rois[:, 3:5] = xy, xy + wh
+    for t in range(1, T):                          # (the frames of a tube: the first frame's box moved by up to 4 pixels)
+        jit = rs.uniform(-4, 4, (R, 2))
+        rois[:, 1 + 4 * t:3 + 4 * t], rois[:, 3 + 4 * t:5 + 4 * t] = xy + jit, xy + jit + wh
     logits = rs.randn(R, K).astype(np.float32) * 2
     prob = (np.exp(logits) / np.exp(logits).sum(axis=1, keepdims=True)).astype(np.float32)
-    pred = (rs.randn(R, K * 4) * 0.5).astype(np.float32)
+    pred = (rs.randn(R, K * 4 * T) * 0.5).astype(np.float32)
     return rois, prob, pred
 
 
@@ -68,8 +72,9 @@ def main():
         return e2e(os.path.abspath(sys.argv[2]), sys.argv[3:])
     R = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
     ni = int(sys.argv[2]) if len(sys.argv) > 2 else 4
+    T = int(sys.argv[3]) if len(sys.argv) > 3 else 1
     K = 2
-    per = [inputs(i, R, K) for i in range(ni)]
+    per = [inputs(i, R, K, T=T) for i in range(ni)]
     rois, prob, pred = (torch.from_numpy(np.concatenate([p[c] for p in per])).cuda() for c in range(3))
     n_rois = torch.tensor([R] * ni, dtype=torch.int32).cuda()
     modes = [('hard NMS', None, None), ('soft hard', 'hard', None), ('soft linear', 'linear', None), ('soft gaussian', 'gaussian', None),
@@ -77,9 +82,10 @@ def main():
     for thr in (0.05, 0.0):
         for name, soft, vote in modes:
             def run():
-                return ops.box_results(rois, n_rois, prob, pred, K, 1, 1.0, (720, 1280, 3), (10., 10., 5., 5.), float(np.float32(np.log(1000. / 16.))),
+                return ops.box_results(rois, n_rois, prob, pred, K, T, 1.0, (720, 1280, 3), (10., 10., 5., 5.), float(np.float32(np.log(1000. / 16.))),
                                        thr, 0.5, 100, 104, n_images=ni,
-                                       soft_nms=dict(method=soft, sigma=0.5, score_thresh=0.0001) if soft else None, bbox_vote=vote)
+                                       soft_nms=dict(method=soft, sigma=0.5, score_thresh=0.0001) if soft else None, bbox_vote=vote,
+                                       tubes=T > 1)
             for _ in range(10):
                 out = run()
             ts = []
@@ -90,8 +96,8 @@ def main():
                 b.record()
                 b.synchronize()
                 ts.append(a.elapsed_time(b) * 1e3)
-            print('%d rois x %d images, SCORE_THRESH %.2f  %-20s %8.1f us   (rows kept %s)' % (
-                R, ni, thr, name, float(np.median(ts)), out[2].cpu().numpy().reshape(-1, 2)[:, 1].tolist()))
+            print('%d rois x %d images, T %d, SCORE_THRESH %.2f  %-20s %8.1f us   (rows kept %s)' % (
+                R, ni, T, thr, name, float(np.median(ts)), out[2].cpu().numpy().reshape(-1, 2)[:, 1].tolist()))
 
 
 if __name__ == '__main__':
