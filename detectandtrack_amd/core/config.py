@@ -295,7 +295,7 @@ def _build_defaults():
     # TUBE_SOFT_NMS (opt-in): TEST.SOFT_NMS / TEST.BBOX_VOTE for TUBE detections (3D body feeding 3D heads), which the reference leaves undefined
     # (nms_wrapper.py:34-35 raises, boxes.py:294-310 votes four columns).  On: the overlap of two tubes is the mean of their per-frame IoUs (what
     # py_cpu_nms_tubes uses), Soft-NMS re-scores with it, voting replaces all 4T coordinates -- on the host path
-    # (dat_soft_nms_tubes_host, utils/boxes.box_voting) and on the device path (soft_nms_tubes_kernel, box_vote_tubes_kernel), which then admits
+    # (dat_soft_nms_tubes_host, utils/boxes.box_voting) and on the device path (soft_nms_kernel, box_vote_kernel: the box kernels ARE these at T = 1), which then admits
     # such configs.  Off: tubes with either TEST switch stay on the host path and behave as in the reference
     c.HIP = AttrDict({'DTYPE': 'bf16', 'KEYFRAME_DCE': False, 'DEVICE_KPS_DECODE': True, 'FRAME_TRUNK_CACHE': 0,
                       'DEVICE_BOX_RESULTS': True, 'FUSE_STEM_POOL': True, 'RCCL_DIRECT': False,

@@ -231,25 +231,26 @@ __global__ __launch_bounds__(SEL_THREADS) void det_limit_emit_kernel(const EmitP
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
-// ---- Soft-NMS on the device (lib/utils/cython_nms.pyx:98-203; the host twin is dat_soft_nms_host below) -------------------------
-// One block per (image, class).  The class's rows [x1 y1 x2 y2 score] and their original indices stay in LDS (structure of arrays)
-// for the whole greedy loop.  Iteration i of the reference:
+// ---- Soft-NMS on the device, for boxes and tubes: rows of 4T coordinates + score, T = 1 being lib/utils/cython_nms.pyx:98-203
+// (include/dat_hip.h, DESIGN.md sections 3.3 and 3.13; the host twin is dat_soft_nms_tubes_host below) ------------------------------
+// One block per (image, class).  The class's rows and their original indices stay in LDS (structure of arrays) for the whole greedy
+// loop.  Iteration i of the reference:
 //   1. arg-max of the scores at positions [i, N) -- strict `<` scan, so the EARLIEST position wins a tie -- swapped into position i;
-//   2. positions (i, N) are re-scored against box i, one after the other; a row whose new score is < threshold is overwritten by
+//   2. positions (i, N) are re-scored against row i, one after the other; a row whose new score is < threshold is overwritten by
 //      row N - 1, N shrinks and the slot is visited again.
-// Each re-score depends on box i and the position's own row only, so step 2 is: re-score all positions in parallel, then put the
+// Each re-score depends on row i and the position's own row only, so step 2 is: re-score all positions in parallel, then put the
 // rows where the serial swap-with-last walk leaves them (positions decide later ties): with N' = N - #removed, survivors below N'
 // stay, and the holes below N', in ascending order, receive the surviving rows at positions >= N' in DESCENDING order (the walk
 // pulls row N - 1, N - 2, ... into the current hole, dropping the pulled rows that die there).  tests/test_soft_nms_cpu.py pins
 // this restatement to dat_soft_nms_host on tie-heavy inputs.
-// Every loop is bounded by the row count read once at entry (<= SOFT_NMS_CAP, checked on the host): a wrong arrangement is a
+// Every loop is bounded by the row count read once at entry (<= the rows in LDS, checked on the host): a wrong arrangement is a
 // mismatch, never a hang.
 constexpr int SOFT_THREADS = 256;
 constexpr int SOFT_WAVES = SOFT_THREADS / 64;
-constexpr int SOFT_NMS_CAP = DAT_SOFT_NMS_MAX_BOXES;     // 6 words + 1 flag byte + a 2-byte hole slot per row = 27 B: 54 KB of the 64 KB a block may declare
+constexpr int SOFT_NMS_CAP = DAT_SOFT_NMS_MAX_BOXES;
 
 struct SoftParams {
-    const float* dets;      // rows [n, 5]; block (img, c) reads dets + img * img_stride bytes + c * cls_stride floats
+    const float* dets;      // rows [n, 4T+1]; block (img, c) reads dets + img * img_stride bytes + c * cls_stride floats
     const int* n_dev;       // device row counts (n_dev + img * img_stride bytes + c), or nullptr: n_host rows
     float* out;             // re-scored rows in selection order, same addressing as dets
     int* inds;              // original row of every output row (nullable), [cap] per class
@@ -258,6 +259,8 @@ struct SoftParams {
     size_t img_stride;
     int cls_stride, cap, n_host, method;
     float sigma, Nt, threshold;
+    int T;
+    int lds_rows;           // rows the launch's dynamic LDS holds (a multiple of 64, >= every row count the block may meet)
 };
 
 struct SoftBest { float s; int pos; };
@@ -265,33 +268,93 @@ __device__ inline SoftBest soft_better(SoftBest a, SoftBest b) {       // larger
     return (b.s > a.s || (b.s == a.s && b.pos < a.pos)) ? b : a;
 }
 
+// The overlap of the current maximum row a and a row b: per frame the IoU of cython_nms.pyx:146-160 (`+ 1` is a DOUBLE constant in
+// the C that Cython emits: see dat_soft_nms_tubes_host), the T values added in float32 in frame order from 0, divided by (float)T.
+// At T = 1 this is the reference's `ov` bit for bit ((0 + x) / 1 == x).  A and B read coordinate c of the two rows.
+template <typename A, typename B>
+__device__ __forceinline__ float tube_overlap(int T, A a, B b) {
+    float sum = 0.f;
+    for (int t = 0; t < T; ++t) {
+        const float tx1 = a(4 * t + 0), ty1 = a(4 * t + 1), tx2 = a(4 * t + 2), ty2 = a(4 * t + 3);
+        const float x1 = b(4 * t + 0), y1 = b(4 * t + 1), x2 = b(4 * t + 2), y2 = b(4 * t + 3);
+        const double tarea = ((double)(tx2 - tx1) + 1.0) * ((double)(ty2 - ty1) + 1.0);
+        const float area = (float)(((double)(x2 - x1) + 1.0) * ((double)(y2 - y1) + 1.0));
+        const float iw = (float)((double)(fminf(tx2, x2) - fmaxf(tx1, x1)) + 1.0);
+        const float ih = (float)((double)(fminf(ty2, y2) - fmaxf(ty1, y1)) + 1.0);
+        float iou = 0.f;
+        if (iw > 0 && ih > 0) {
+            const float ua = (float)((tarea + (double)area) - (double)(iw * ih));
+            iou = iw * ih / ua;
+        }
+        sum = sum + iou;
+    }
+    return sum / (float)T;
+}
+
+// Row s of the [words][stride] image to row d != s.  The two rows share no word, which `__restrict__` tells the compiler: it may load
+// every word before it stores the first, instead of waiting for each load in turn.
+__device__ __forceinline__ void soft_copy_row(float* __restrict__ d, const float* __restrict__ s, int words, int stride) {
+    for (int w = 0; w < words; ++w) d[w * stride] = s[w * stride];
+}
+
+// Dynamic LDS of soft_nms_kernel for `rows` rows (a multiple of 64): ROWS [4T+2][rows + 1] words (4T coordinates, the score, the
+// original index), HOLE [rows] shorts, DEAD [rows] bytes = 16T + 11 bytes a row, and the stage of the swap: row `rows` of ROWS and
+// SOFT_WAVES more rows of 4T + 2 words.  The capacity rule counts the rows alone against SOFT_LDS_BUDGET; the 512 bytes it leaves
+// of the 160 KB a gfx950 workgroup gets hold the kernel's static LDS and, at the one T whose rows come that close (T = 5: 768
+// bytes left), the stage's 440 bytes.
+constexpr int SOFT_LDS_BUDGET = 160 * 1024 - 512;
+constexpr int SOFT_LDS_STATIC = 304;        // at least the static LDS the compiler reports for soft_nms_kernel
+constexpr int SOFT_LDS_DYNAMIC_MAX = 160 * 1024 - SOFT_LDS_STATIC;
+constexpr int soft_tube_capacity(int T) {
+    if (T < 1 || T > DET_MAX_T) return 0;
+    const int rows = SOFT_LDS_BUDGET / (16 * T + 11) / 64 * 64;
+    return rows < SOFT_NMS_CAP ? rows : SOFT_NMS_CAP;
+}
+constexpr int soft_lds_bytes(int rows, int T) { return rows * (16 * T + 11) + (SOFT_WAVES + 1) * (4 * T + 2) * 4; }
+constexpr bool soft_lds_fits() {
+    for (int T = 1; T <= DET_MAX_T; ++T)
+        if (soft_lds_bytes(soft_tube_capacity(T), T) > SOFT_LDS_DYNAMIC_MAX) return false;
+    return true;
+}
+static_assert(soft_lds_fits(), "the rows at capacity, the stage and the static LDS exceed a workgroup's 160 KB for some T");
+
+// TC: the frame count at compile time -- 1: rows of five columns, where the loops over a row's words unroll and the mean of one
+// IoU folds away; 0: p.T (as det_select_kernel's TM).  The body is the same for both.
+template <int TC>
 __global__ __launch_bounds__(SOFT_THREADS) void soft_nms_kernel(const SoftParams p) {
-    __shared__ float X1[SOFT_NMS_CAP], Y1[SOFT_NMS_CAP], X2[SOFT_NMS_CAP], Y2[SOFT_NMS_CAP], SC[SOFT_NMS_CAP];
-    __shared__ int IDX[SOFT_NMS_CAP];
-    __shared__ unsigned short HOLE[SOFT_NMS_CAP];
-    __shared__ unsigned char DEAD[SOFT_NMS_CAP];
-    __shared__ float w_row[SOFT_WAVES][5];
-    __shared__ int w_idx[SOFT_WAVES], w_pos[SOFT_WAVES];
+    extern __shared__ __attribute__((aligned(16))) unsigned char soft_lds[];
+    __shared__ int w_pos[SOFT_WAVES];
     __shared__ unsigned w_scan[SOFT_WAVES];
+    const int T = TC ? TC : max(1, min(p.T, DET_MAX_T)), C4 = 4 * T, cols = C4 + 1, RW = C4 + 2;
+    const int L = p.lds_rows, S = L + 1;
+    // word w of row r is ROWS[w * S + r], so lane q reads consecutive words of every column.  Row L is no position of the loop: it
+    // holds row i as it is before the swap.  The index travels as the bits of a float: it is only ever loaded and stored
+    float* ROWS = (float*)soft_lds;
+    float* SC = ROWS + (size_t)C4 * S;
+    float* IDX = SC + S;
+    unsigned short* HOLE = (unsigned short*)(IDX + S);
+    unsigned char* DEAD = (unsigned char*)(HOLE + L);
+    float* STAGE = (float*)(DEAD + L);                      // [SOFT_WAVES][RW]: every wave's arg-max row
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the block's last RW threads move the words of row i, one each (the re-score loop's odd trip goes to the first threads)
+    const int col = tid - (SOFT_THREADS - RW);
     const int img = blockIdx.x, c = blockIdx.y;
     const size_t ioff = (size_t)img * p.img_stride;
     const float* src = (const float*)((const char*)p.dets + ioff) + (size_t)c * p.cls_stride;
     float* dst = (float*)((char*)p.out + ioff) + (size_t)c * p.cls_stride;
     int n = p.n_dev ? ((const int*)((const char*)p.n_dev + ioff))[c] : p.n_host;
-    n = max(0, min(n, min(p.cap, SOFT_NMS_CAP)));
-    for (int r = tid; r < n; r += SOFT_THREADS) {
-        X1[r] = src[r * 5 + 0]; Y1[r] = src[r * 5 + 1]; X2[r] = src[r * 5 + 2]; Y2[r] = src[r * 5 + 3]; SC[r] = src[r * 5 + 4];
-        IDX[r] = r;
+    n = max(0, min(n, min(p.cap, min(L, SOFT_NMS_CAP))));
+    for (int e = tid; e < n * cols; e += SOFT_THREADS) {
+        const int r = e / cols, w = e - r * cols;
+        ROWS[w * S + r] = src[e];
     }
+    for (int r = tid; r < n; r += SOFT_THREADS) IDX[r] = __int_as_float(r);
     __syncthreads();
     int N = n;
     for (int i = 0; i < n; ++i) {              // (N only shrinks; every thread holds the same N)
         if (i >= N) break;
-        // row i as it is before the swap: the row that moves to the arg-max position
-        const float ix1 = X1[i], iy1 = Y1[i], ix2 = X2[i], iy2 = Y2[i], is = SC[i];
-        const int ii = IDX[i];
-        SoftBest b = {is, i};
+        const float old_w = col >= 0 ? ROWS[col * S + i] : 0.f;
+        SoftBest b = {SC[i], i};
         for (int q = i + 1 + tid; q < N; q += SOFT_THREADS) {
             const float s = SC[q];
             if (b.s < s) { b.s = s; b.pos = q; }       // ascending q per thread: the strict `<` of the reference
@@ -301,58 +364,48 @@ __global__ __launch_bounds__(SOFT_THREADS) void soft_nms_kernel(const SoftParams
             SoftBest o = {__shfl_xor(b.s, off), __shfl_xor(b.pos, off)};
             b = soft_better(b, o);
         }
-        if (lane == 0) {
-            const int m = b.pos;
-            w_row[wave][0] = X1[m]; w_row[wave][1] = Y1[m]; w_row[wave][2] = X2[m]; w_row[wave][3] = Y2[m]; w_row[wave][4] = SC[m];
-            w_idx[wave] = IDX[m]; w_pos[wave] = m;
-        }
+        // The swap of rows i and maxpos costs no barrier of its own: every wave stages its arg-max row and the last RW threads stage
+        // row i, one word each, before the barrier of the block's arg-max.  Behind it the winning wave's stage IS the current row,
+        // the same threads put it at position i and their word of the old row i at maxpos, and the one thread that visits maxpos
+        // reads the old row i from its staged copy, row L, instead (and stores its score, re-scored, itself)
+        for (int w = lane; w < RW; w += 64) STAGE[wave * RW + w] = ROWS[w * S + b.pos];
+        if (lane == 0) w_pos[wave] = b.pos;
+        if (col >= 0) ROWS[col * S + L] = old_w;
         __syncthreads();
         int bw = 0;
-        SoftBest best = {w_row[0][4], w_pos[0]};
+        SoftBest best = {STAGE[C4], w_pos[0]};
 #pragma unroll
         for (int w = 1; w < SOFT_WAVES; ++w) {
-            const SoftBest o = {w_row[w][4], w_pos[w]};
+            const SoftBest o = {STAGE[w * RW + C4], w_pos[w]};
             const SoftBest r = soft_better(best, o);
             if (r.pos != best.pos) bw = w;
             best = r;
         }
-        const int maxpos = best.pos;
-        const float tx1 = w_row[bw][0], ty1 = w_row[bw][1], tx2 = w_row[bw][2], ty2 = w_row[bw][3];
-        if (tid == 0) {                        // nobody reads position i again in this iteration
-            X1[i] = tx1; Y1[i] = ty1; X2[i] = tx2; Y2[i] = ty2; SC[i] = w_row[bw][4]; IDX[i] = w_idx[bw];
+        const int maxpos = best.pos;           // i <= maxpos < N
+        const float* cur = STAGE + bw * RW;
+        if (col >= 0) {
+            ROWS[col * S + i] = cur[col];      // nobody reads position i again in this iteration
+            if (col != C4) ROWS[col * S + maxpos] = old_w;     // (maxpos == i: the same word again)
         }
-        const double tarea = ((double)(tx2 - tx1) + 1.0) * ((double)(ty2 - ty1) + 1.0);
         int ndead_local = 0;                   // (a flag: did this thread remove a row)
         for (int q = i + 1 + tid; q < N; q += SOFT_THREADS) {
-            float x1, y1, x2, y2, s;
-            if (q == maxpos) {                 // the swap: this position now holds the old row i
-                x1 = ix1; y1 = iy1; x2 = ix2; y2 = iy2; s = is;
-                X1[q] = x1; Y1[q] = y1; X2[q] = x2; Y2[q] = y2; IDX[q] = ii;
-            } else {
-                x1 = X1[q]; y1 = Y1[q]; x2 = X2[q]; y2 = Y2[q]; s = SC[q];
-            }
-            // (`+ 1` is a DOUBLE constant in the C that Cython emits: see dat_soft_nms_host)
-            const float area = (float)(((double)(x2 - x1) + 1.0) * ((double)(y2 - y1) + 1.0));
-            const float iw = (float)((double)(fminf(tx2, x2) - fmaxf(tx1, x1)) + 1.0);
+            const int r = q == maxpos ? L : q;                 // where the row now at q is read from
+            float s = SC[r];
+            const float ov = tube_overlap(T, [&](int cc) { return cur[cc]; }, [&](int cc) { return ROWS[cc * S + r]; });
             bool dead = false;
-            if (iw > 0) {
-                const float ih = (float)((double)(fminf(ty2, y2) - fmaxf(ty1, y1)) + 1.0);
-                if (ih > 0) {
-                    const float ua = (float)((tarea + (double)area) - (double)(iw * ih));
-                    const float ov = iw * ih / ua;
-                    float weight;
-                    if (p.method == 1) weight = ov > p.Nt ? (float)(1.0 - (double)ov) : 1.f;
-                    else if (p.method == 2) weight = (float)exp((double)(-(ov * ov) / p.sigma));
-                    else weight = ov > p.Nt ? 0.f : 1.f;
-                    s = weight * s;
-                    dead = s < p.threshold;
-                }
+            if (ov > 0) {                      // (T = 1: iw > 0 && ih > 0 -- there ua >= both areas > 0 and iw * ih > 0)
+                float weight;
+                if (p.method == 1) weight = ov > p.Nt ? (float)(1.0 - (double)ov) : 1.f;
+                else if (p.method == 2) weight = (float)exp((double)(-(ov * ov) / p.sigma));
+                else weight = ov > p.Nt ? 0.f : 1.f;
+                s = weight * s;
+                dead = s < p.threshold;
             }
             SC[q] = s;
             DEAD[q] = dead ? 1 : 0;
             ndead_local |= dead ? 1 : 0;
         }
-        // (the barrier also orders this iteration's LDS writes before the next iteration's reads)
+        // (the barrier also orders this iteration's LDS accesses, the stage's included, before the next iteration's)
         if (!__syncthreads_or(ndead_local)) continue;
         // ---- compaction: holes below N' (ascending) <- survivors at >= N' (descending).  One block scan of the removed flags gives
         // every removed row its ascending rank r (the holes below N' are the ranks 0 .. #holes - 1) and every survivor at q >= N'
@@ -390,290 +443,67 @@ __global__ __launch_bounds__(SOFT_THREADS) void soft_nms_kernel(const SoftParams
         for (int q = lo; q < hi; ++q) {
             if (DEAD[q]) { ++rank; continue; }
             if (q >= N2) {
-                const int h = HOLE[(N - 1 - q) - (ndead - rank)];      // the highest survivor fills the lowest hole
-                X1[h] = X1[q]; Y1[h] = Y1[q]; X2[h] = X2[q]; Y2[h] = Y2[q]; SC[h] = SC[q]; IDX[h] = IDX[q];
-            }
-        }
-        N = N2;
-        __syncthreads();
-    }
-    for (int r = tid; r < N; r += SOFT_THREADS) {
-        dst[r * 5 + 0] = X1[r]; dst[r * 5 + 1] = Y1[r]; dst[r * 5 + 2] = X2[r]; dst[r * 5 + 3] = Y2[r]; dst[r * 5 + 4] = SC[r];
-        if (p.inds) ((int*)((char*)p.inds + ioff))[(size_t)c * p.cap + r] = IDX[r];
-        if (p.ident) ((int*)((char*)p.ident + ioff))[(size_t)c * p.cap + r] = r;
-    }
-    if (tid == 0) ((int*)((char*)p.n_out + ioff))[c] = N;
-}
-
-// ---- box voting on the device (lib/utils/boxes.py:294-310): every kept row's coordinates become the score-weighted mean of the
-// class's selected rows (before NMS, original scores) whose IoU with it (lib/utils/cython_bbox.pyx:16-57 in the C float order
-// utils/boxes._iou_matrix restates) is >= thresh; the row's score stays.  One wave per kept row: lane l visits rows l, l + 64, ...
-// and accumulates its five sums in double in that order, then a butterfly adds the lanes -- a fixed order, so runs repeat bit for
-// bit -- and the mean is rounded to float once.
-constexpr int VOTE_THREADS = 256;
-constexpr int VOTE_BLOCKS = 8;
-
-struct VoteParams {
-    const float* top;       // kept rows [., 5]: row k is top[keep ? keep[k] : k]; addressing as SoftParams
-    const int* keep;        // nullable, [cap] per class
-    const int* n_top;       // device counts (nullable: n_top_host)
-    const float* all;       // the class's selected rows [., 5]
-    const int* n_all;       // device counts (nullable: n_all_host)
-    float* out;             // [., 5] voted rows, row k (may alias top when keep == nullptr)
-    int* ident;             // nullable: ident[k] = k
-    size_t img_stride;
-    int cls_stride, cap, n_top_host, n_all_host;
-    float thresh;
-};
-
-__global__ __launch_bounds__(VOTE_THREADS) void box_vote_kernel(const VoteParams p) {
-    const int lane = threadIdx.x & 63;
-    const int img = blockIdx.x, c = blockIdx.y;
-    const size_t ioff = (size_t)img * p.img_stride;
-    const size_t coff = (size_t)c * p.cls_stride;
-    const float* top = (const float*)((const char*)p.top + ioff) + coff;
-    const float* all = (const float*)((const char*)p.all + ioff) + coff;
-    float* out = (float*)((char*)p.out + ioff) + coff;
-    const int n_top = p.n_top ? ((const int*)((const char*)p.n_top + ioff))[c] : p.n_top_host;
-    const int n_all = p.n_all ? ((const int*)((const char*)p.n_all + ioff))[c] : p.n_all_host;
-    const int* keep = p.keep ? (const int*)((const char*)p.keep + ioff) + (size_t)c * p.cap : nullptr;
-    int* ident = p.ident ? (int*)((char*)p.ident + ioff) + (size_t)c * p.cap : nullptr;
-    const int wpb = VOTE_THREADS / 64;
-    for (int k = blockIdx.z * wpb + (threadIdx.x >> 6); k < n_top; k += gridDim.z * wpb) {
-        const float* t = top + (size_t)(keep ? keep[k] : k) * 5;
-        const float b0 = t[0], b1 = t[1], b2 = t[2], b3 = t[3], bs = t[4];
-        const double barea = ((double)(b2 - b0) + 1.0) * ((double)(b3 - b1) + 1.0);
-        double sw = 0., s0 = 0., s1 = 0., s2 = 0., s3 = 0.;
-        for (int m = lane; m < n_all; m += 64) {
-            const float* q = all + (size_t)m * 5;
-            const float q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], w = q[4];
-            const float iw = (float)((double)(fminf(b2, q2) - fmaxf(b0, q0)) + 1.0);
-            const float ih = (float)((double)(fminf(b3, q3) - fmaxf(b1, q1)) + 1.0);
-            float iou = 0.f;
-            if (iw > 0 && ih > 0) {
-                const float qa = (float)(((double)(q2 - q0) + 1.0) * ((double)(q3 - q1) + 1.0));
-                const float inter = iw * ih;
-                const float ua = (float)((barea + (double)qa) - (double)inter);
-                iou = inter / ua;
-            }
-            if (iou >= p.thresh) {
-                const double dw = (double)w;
-                sw += dw; s0 += dw * (double)q0; s1 += dw * (double)q1; s2 += dw * (double)q2; s3 += dw * (double)q3;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            sw += __shfl_xor(sw, off); s0 += __shfl_xor(s0, off); s1 += __shfl_xor(s1, off);
-            s2 += __shfl_xor(s2, off); s3 += __shfl_xor(s3, off);
-        }
-        // In-place use: `out` may be `top` (Soft-NMS + voting) and `ident` may be `keep` (NMS + voting).  Only this wave touches row k of
-        // either, every lane has loaded t[] and keep[k] above, and the butterfly between those loads and the stores below keeps the
-        // wave in step, so lane 0's stores cannot overtake another lane's load.
-        if (lane == 0) {
-            float* o = out + (size_t)k * 5;
-            o[0] = (float)(s0 / sw); o[1] = (float)(s1 / sw); o[2] = (float)(s2 / sw); o[3] = (float)(s3 / sw); o[4] = bs;
-            if (ident) ident[k] = k;
-        }
-    }
-}
-
-// ---- Soft-NMS and box voting for tubes (rows of 4T coordinates + score; include/dat_hip.h) -------------
-// The tube overlap of the current maximum row a (positions a0 .. of the caller) and a row b: per frame the IoU of soft_nms_kernel,
-// the T values added in float32 in frame order from 0, divided by (float)T.  At T = 1 this is soft_nms_kernel's `ov` bit for bit
-// ((0 + x) / 1 == x).  A and B read coordinate c of the two rows.
-template <typename A, typename B>
-__device__ __forceinline__ float tube_overlap(int T, A a, B b) {
-    float sum = 0.f;
-    for (int t = 0; t < T; ++t) {
-        const float tx1 = a(4 * t + 0), ty1 = a(4 * t + 1), tx2 = a(4 * t + 2), ty2 = a(4 * t + 3);
-        const float x1 = b(4 * t + 0), y1 = b(4 * t + 1), x2 = b(4 * t + 2), y2 = b(4 * t + 3);
-        const double tarea = ((double)(tx2 - tx1) + 1.0) * ((double)(ty2 - ty1) + 1.0);
-        const float area = (float)(((double)(x2 - x1) + 1.0) * ((double)(y2 - y1) + 1.0));
-        const float iw = (float)((double)(fminf(tx2, x2) - fmaxf(tx1, x1)) + 1.0);
-        const float ih = (float)((double)(fminf(ty2, y2) - fmaxf(ty1, y1)) + 1.0);
-        float iou = 0.f;
-        if (iw > 0 && ih > 0) {
-            const float ua = (float)((tarea + (double)area) - (double)(iw * ih));
-            iou = iw * ih / ua;
-        }
-        sum = sum + iou;
-    }
-    return sum / (float)T;
-}
-
-// Dynamic LDS of soft_nms_tubes_kernel for `rows` rows (a multiple of 64): COORD [4T][rows] and SC [rows] floats, IDX [rows] ints,
-// HOLE [rows] shorts, DEAD [rows] bytes = 16T + 11 bytes a row; the per-wave arrays of the reductions are static (the compiler
-// reports 304 bytes of static LDS for the kernel).
-constexpr int SOFT_TUBE_LDS_BUDGET = 160 * 1024 - 512;      // what a gfx950 workgroup gets, less the static arrays rounded up
-inline size_t soft_tube_lds_bytes(int rows, int T) { return (size_t)rows * (16 * T + 11); }
-inline int soft_tube_capacity(int T) {
-    if (T < 1 || T > DET_MAX_T) return 0;
-    const int rows = SOFT_TUBE_LDS_BUDGET / (16 * T + 11) / 64 * 64;
-    return rows < SOFT_NMS_CAP ? rows : SOFT_NMS_CAP;
-}
-
-struct SoftTubeParams {
-    SoftParams s;           // rows [n, 4T+1]; cls_stride in floats, cap = rows per class of inds / ident
-    int T;
-    int lds_rows;           // rows the launch's dynamic LDS holds (a multiple of 64, >= every row count the block may meet)
-};
-
-// soft_nms_kernel for 4T coordinates: the same arg-max reduction, re-score and compaction; the rows live in dynamic LDS as a
-// structure of arrays [4T][lds_rows], so lane q reads consecutive words of every coordinate.  The swap of row i with the arg-max
-// row is done in LDS (one thread per column) before the re-score, which then reads row i by broadcast.
-__global__ __launch_bounds__(SOFT_THREADS) void soft_nms_tubes_kernel(const SoftTubeParams tp) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char soft_tube_lds[];
-    __shared__ float w_s[SOFT_WAVES];
-    __shared__ int w_pos[SOFT_WAVES];
-    __shared__ unsigned w_scan[SOFT_WAVES];
-    const SoftParams& p = tp.s;
-    const int T = max(1, min(tp.T, DET_MAX_T)), C4 = 4 * T, cols = C4 + 1;
-    const int L = tp.lds_rows;
-    float* COORD = (float*)soft_tube_lds;                   // [C4][L]
-    float* SC = COORD + (size_t)C4 * L;
-    int* IDX = (int*)(SC + L);
-    unsigned short* HOLE = (unsigned short*)(IDX + L);
-    unsigned char* DEAD = (unsigned char*)(HOLE + L);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int img = blockIdx.x, c = blockIdx.y;
-    const size_t ioff = (size_t)img * p.img_stride;
-    const float* src = (const float*)((const char*)p.dets + ioff) + (size_t)c * p.cls_stride;
-    float* dst = (float*)((char*)p.out + ioff) + (size_t)c * p.cls_stride;
-    int n = p.n_dev ? ((const int*)((const char*)p.n_dev + ioff))[c] : p.n_host;
-    n = max(0, min(n, min(p.cap, min(L, SOFT_NMS_CAP))));
-    for (int e = tid; e < n * cols; e += SOFT_THREADS) {
-        const int r = e / cols, cc = e - r * cols;
-        const float v = src[e];
-        if (cc < C4) COORD[cc * L + r] = v;
-        else SC[r] = v;
-    }
-    for (int r = tid; r < n; r += SOFT_THREADS) IDX[r] = r;
-    __syncthreads();
-    int N = n;
-    for (int i = 0; i < n; ++i) {              // (N only shrinks; every thread holds the same N)
-        if (i >= N) break;
-        SoftBest b = {SC[i], i};
-        for (int q = i + 1 + tid; q < N; q += SOFT_THREADS) {
-            const float s = SC[q];
-            if (b.s < s) { b.s = s; b.pos = q; }       // ascending q per thread: the strict `<` of the reference
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            SoftBest o = {__shfl_xor(b.s, off), __shfl_xor(b.pos, off)};
-            b = soft_better(b, o);
-        }
-        if (lane == 0) { w_s[wave] = b.s; w_pos[wave] = b.pos; }
-        __syncthreads();
-        SoftBest best = {w_s[0], w_pos[0]};
-#pragma unroll
-        for (int w = 1; w < SOFT_WAVES; ++w) {
-            const SoftBest o = {w_s[w], w_pos[w]};
-            best = soft_better(best, o);
-        }
-        const int maxpos = best.pos;           // i <= maxpos < N
-        // the swap of rows i and maxpos: one thread per column (4T coordinates, the score, the index)
-        if (maxpos != i) {
-            if (tid < C4) {
-                const float a = COORD[tid * L + i], m = COORD[tid * L + maxpos];
-                COORD[tid * L + i] = m; COORD[tid * L + maxpos] = a;
-            } else if (tid == C4) {
-                const float a = SC[i], m = SC[maxpos];
-                SC[i] = m; SC[maxpos] = a;
-            } else if (tid == C4 + 1) {
-                const int a = IDX[i], m = IDX[maxpos];
-                IDX[i] = m; IDX[maxpos] = a;
-            }
-        }
-        __syncthreads();                       // (also: w_s / w_pos are not written again before every thread has read them)
-        int ndead_local = 0;                   // (a flag: did this thread remove a row)
-        for (int q = i + 1 + tid; q < N; q += SOFT_THREADS) {
-            float s = SC[q];
-            const float ov = tube_overlap(T, [&](int cc) { return COORD[cc * L + i]; }, [&](int cc) { return COORD[cc * L + q]; });
-            bool dead = false;
-            if (ov > 0) {                      // (T = 1: iw > 0 && ih > 0 -- there ua >= both areas > 0 and iw * ih > 0)
-                float weight;
-                if (p.method == 1) weight = ov > p.Nt ? (float)(1.0 - (double)ov) : 1.f;
-                else if (p.method == 2) weight = (float)exp((double)(-(ov * ov) / p.sigma));
-                else weight = ov > p.Nt ? 0.f : 1.f;
-                s = weight * s;
-                dead = s < p.threshold;
-            }
-            SC[q] = s;
-            DEAD[q] = dead ? 1 : 0;
-            ndead_local |= dead ? 1 : 0;
-        }
-        // (the barrier also orders this iteration's LDS writes before the next iteration's reads)
-        if (!__syncthreads_or(ndead_local)) continue;
-        // ---- compaction, as in soft_nms_kernel: holes below N' (ascending) <- survivors at >= N' (descending)
-        const int span = N - (i + 1);
-        const int per = (span + SOFT_THREADS - 1) / SOFT_THREADS;
-        const int lo = min(N, i + 1 + tid * per), hi = min(N, lo + per);
-        unsigned cnt = 0;
-        for (int q = lo; q < hi; ++q) cnt += DEAD[q];
-        unsigned incl = cnt;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned u = __shfl_up(incl, off);
-            if (lane >= off) incl += u;
-        }
-        if (lane == 63) w_scan[wave] = incl;
-        __syncthreads();
-        unsigned before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < SOFT_WAVES; ++w) {
-            if (w < wave) before += w_scan[w];
-            total += w_scan[w];
-        }
-        const int ndead = (int)total;
-        const int N2 = N - ndead;
-        int rank = (int)(before + incl - cnt);             // removed rows before position lo
-        for (int q = lo; q < hi; ++q) {
-            if (DEAD[q]) {
-                if (q < N2) HOLE[rank] = (unsigned short)q;
-                ++rank;
-            }
-        }
-        __syncthreads();
-        rank = (int)(before + incl - cnt);
-        for (int q = lo; q < hi; ++q) {
-            if (DEAD[q]) { ++rank; continue; }
-            if (q >= N2) {
                 // the highest survivor fills the lowest hole; the slot index is in [0, #holes) for every consistent arrangement and
                 // is clamped to the rows in LDS for any other
                 const int slot = min(max((N - 1 - q) - (ndead - rank), 0), L - 1);
                 const int h = min((int)HOLE[slot], L - 1);
-                for (int cc = 0; cc < C4; ++cc) COORD[cc * L + h] = COORD[cc * L + q];
-                SC[h] = SC[q]; IDX[h] = IDX[q];
+                soft_copy_row(ROWS + h, ROWS + q, RW, S);
             }
         }
         N = N2;
         __syncthreads();
     }
     for (int e = tid; e < N * cols; e += SOFT_THREADS) {
-        const int r = e / cols, cc = e - r * cols;
-        dst[e] = cc < C4 ? COORD[cc * L + r] : SC[r];
+        const int r = e / cols, w = e - r * cols;
+        dst[e] = ROWS[w * S + r];
     }
     for (int r = tid; r < N; r += SOFT_THREADS) {
-        if (p.inds) ((int*)((char*)p.inds + ioff))[(size_t)c * p.cap + r] = IDX[r];
+        if (p.inds) ((int*)((char*)p.inds + ioff))[(size_t)c * p.cap + r] = __float_as_int(IDX[r]);
         if (p.ident) ((int*)((char*)p.ident + ioff))[(size_t)c * p.cap + r] = r;
     }
     if (tid == 0) ((int*)((char*)p.n_out + ioff))[c] = N;
 }
 
-// box_vote_kernel for 4T coordinates: one wave per kept row, whose coordinate l stays in lane l's register for the whole row (the
-// overlap reads it by a lane broadcast), so the row may be overwritten in place.  The 4T + 1 double sums are formed VOTE_CHUNK
-// frames at a time (16 coordinate sums + the weight sum in registers); a row of more than VOTE_CHUNK frames walks the voters once
-// per chunk and finds the same voter set each time (the overlap depends on registers and on `all` only).
+// max_rows: the most rows a block of this launch may meet (checked against the capacity by the callers)
+int launch_soft_nms(dat_ctx* ctx, hipStream_t st, SoftParams sp, int T, int max_rows, dim3 grid) {
+    sp.T = T;
+    sp.lds_rows = min(soft_tube_capacity(T), max(64, (max_rows + 63) / 64 * 64));
+    const auto kern = T == 1 ? soft_nms_kernel<1> : soft_nms_kernel<0>;
+    const int rc = dat_ensure_lds(ctx, (const void*)kern, SOFT_LDS_DYNAMIC_MAX);
+    if (rc != DAT_OK) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(SOFT_THREADS), soft_lds_bytes(sp.lds_rows, T), st, sp);
+    return DAT_OK;
+}
+
+// ---- box voting on the device (lib/utils/boxes.py:294-310; rows of 4T coordinates + score): every kept row's coordinates become
+// the score-weighted mean of the class's selected rows (before NMS, original scores) whose overlap with it (tube_overlap; at T = 1
+// lib/utils/cython_bbox.pyx:16-57 in the C float order utils/boxes._iou_matrix restates) is >= thresh; the row's score stays.  One
+// wave per kept row, whose coordinate l stays in lane l's register for the whole row (the overlap reads it by a lane broadcast),
+// so the row may be overwritten in place.  Lane l visits rows l, l + 64, ... and accumulates its sums in double in that order, then a
+// butterfly adds the lanes -- a fixed order, so runs repeat bit for bit -- and the mean is rounded to float once.  The 4T + 1 sums
+// are formed VOTE_CHUNK frames at a time (16 coordinate sums + the weight sum in registers); a row of more than VOTE_CHUNK frames
+// walks the voters once per chunk and finds the same voter set each time (the overlap depends on registers and on `all` only).
+constexpr int VOTE_THREADS = 256;
+constexpr int VOTE_BLOCKS = 16;
 constexpr int VOTE_CHUNK = 4;
 
-struct VoteTubeParams {
-    VoteParams v;           // rows [., 4T+1]
+struct VoteParams {
+    const float* top;       // kept rows [., 4T+1]: row k is top[keep ? keep[k] : k]; addressing as SoftParams
+    const int* keep;        // nullable, [cap] per class
+    const int* n_top;       // device counts (nullable: n_top_host)
+    const float* all;       // the class's selected rows [., 4T+1]
+    const int* n_all;       // device counts (nullable: n_all_host)
+    float* out;             // [., 4T+1] voted rows, row k (may alias top when keep == nullptr)
+    int* ident;             // nullable: ident[k] = k
+    size_t img_stride;
+    int cls_stride, cap, n_top_host, n_all_host;
+    float thresh;
     int T;
 };
 
-__global__ __launch_bounds__(VOTE_THREADS) void box_vote_tubes_kernel(const VoteTubeParams tp) {
-    const VoteParams& p = tp.v;
-    const int T = max(1, min(tp.T, DET_MAX_T)), C4 = 4 * T, cols = C4 + 1;
+template <int TC>       // (TC: as soft_nms_kernel's)
+__global__ __launch_bounds__(VOTE_THREADS) void box_vote_kernel(const VoteParams p) {
+    const int T = TC ? TC : max(1, min(p.T, DET_MAX_T)), C4 = 4 * T, cols = C4 + 1;
     const int lane = threadIdx.x & 63;
     const int img = blockIdx.x, c = blockIdx.y;
     const size_t ioff = (size_t)img * p.img_stride;
@@ -695,14 +525,12 @@ __global__ __launch_bounds__(VOTE_THREADS) void box_vote_tubes_kernel(const Vote
             double sw = 0., sc[4 * VOTE_CHUNK];
 #pragma unroll
             for (int j = 0; j < 4 * VOTE_CHUNK; ++j) sc[j] = 0.;
-            // every lane runs every trip (the broadcasts below read all lanes); a lane past n_all votes with nothing
-            for (int m0 = 0; m0 < n_all; m0 += 64) {
-                const int m = m0 + lane;
-                const bool valid = m < n_all;
-                const float* q = all + (size_t)(valid ? m : 0) * cols;
-                const float ov = tube_overlap(T, [&](int cc) { return __shfl(mine, cc); }, [&](int cc) { return q[cc]; });
-                if (valid && ov >= p.thresh) {
-                    const double dw = (double)q[C4];
+            for (int m = lane; m < n_all; m += 64) {
+                const float* q = all + (size_t)m * cols;
+                const double dw = (double)q[C4];
+                const float ov = tube_overlap(T, [&](int cc) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), cc)); },
+                                              [&](int cc) { return q[cc]; });
+                if (ov >= p.thresh) {
                     sw += dw;
 #pragma unroll
                     for (int j = 0; j < 4 * VOTE_CHUNK; ++j)
@@ -715,8 +543,9 @@ __global__ __launch_bounds__(VOTE_THREADS) void box_vote_tubes_kernel(const Vote
 #pragma unroll
                 for (int j = 0; j < 4 * VOTE_CHUNK; ++j) sc[j] += __shfl_xor(sc[j], off);
             }
-            // In-place use, as in box_vote_kernel: `out` may be `top` and `ident` may be `keep`.  Only this wave touches row k of either,
-            // every lane has loaded its word of t[] and keep[k] before the first butterfly, and no later chunk reads t[] again.
+            // In-place use: `out` may be `top` (Soft-NMS + voting) and `ident` may be `keep` (NMS + voting).  Only this wave touches row k
+            // of either, every lane has loaded its word of t[] and keep[k] before the first butterfly, which keeps the wave in step, so
+            // lane 0's stores cannot overtake another lane's load; and no later chunk reads t[] again.
             if (lane == 0) {
                 float* o = out + (size_t)k * cols;
 #pragma unroll
@@ -731,15 +560,8 @@ __global__ __launch_bounds__(VOTE_THREADS) void box_vote_tubes_kernel(const Vote
     }
 }
 
-// max_rows: the most rows a block of this launch may meet (checked against the capacity by the callers)
-int launch_soft_nms_tubes(dat_ctx* ctx, hipStream_t st, const SoftParams& sp, int T, int max_rows, dim3 grid) {
-    SoftTubeParams tp;
-    tp.s = sp; tp.T = T;
-    tp.lds_rows = min(soft_tube_capacity(T), max(64, (max_rows + 63) / 64 * 64));
-    const int rc = dat_ensure_lds(ctx, (const void*)soft_nms_tubes_kernel, SOFT_TUBE_LDS_BUDGET);
-    if (rc != DAT_OK) return rc;
-    hipLaunchKernelGGL(soft_nms_tubes_kernel, grid, dim3(SOFT_THREADS), soft_tube_lds_bytes(tp.lds_rows, T), st, tp);
-    return DAT_OK;
+void launch_box_vote(hipStream_t st, const VoteParams& vp, dim3 grid) {
+    hipLaunchKernelGGL(vp.T == 1 ? box_vote_kernel<1> : box_vote_kernel<0>, grid, dim3(VOTE_THREADS), 0, st, vp);
 }
 
 }  // namespace
@@ -822,8 +644,7 @@ static int box_results_impl(dat_ctx* ctx, dat_stream s, const float* rois, const
         sp.dets = dets; sp.n_dev = n_sel; sp.out = rows2; sp.ident = keep; sp.n_out = n_keep; sp.img_stride = img_ws;
         sp.cls_stride = roi_cap * cols; sp.cap = roi_cap; sp.method = o->soft_nms_method; sp.sigma = o->soft_nms_sigma;
         sp.Nt = d->nms_thresh; sp.threshold = o->soft_nms_score_thresh;
-        if (T == 1) hipLaunchKernelGGL(soft_nms_kernel, dim3(ni, nc), dim3(SOFT_THREADS), 0, st, sp);
-        else if (int rc = launch_soft_nms_tubes(ctx, st, sp, T, roi_cap, dim3(ni, nc))) return rc;
+        if (int rc = launch_soft_nms(ctx, st, sp, T, roi_cap, dim3(ni, nc))) return rc;
     }
     if (vote) {
         // (test.py:776-779) the kept rows -- dets[keep] after the NMS, rows2 after Soft-NMS -- voted by the class's selected rows
@@ -831,13 +652,8 @@ static int box_results_impl(dat_ctx* ctx, dat_stream s, const float* rois, const
         memset(&vp, 0, sizeof(vp));
         vp.top = soft ? rows2 : dets; vp.keep = soft ? nullptr : keep; vp.n_top = n_keep; vp.all = dets; vp.n_all = n_sel;
         vp.out = rows2; vp.ident = soft ? nullptr : keep; vp.img_stride = img_ws; vp.cls_stride = roi_cap * cols; vp.cap = roi_cap;
-        vp.thresh = o->bbox_vote_thresh;
-        if (T == 1) hipLaunchKernelGGL(box_vote_kernel, dim3(ni, nc, VOTE_BLOCKS), dim3(VOTE_THREADS), 0, st, vp);
-        else {
-            VoteTubeParams vt;
-            vt.v = vp; vt.T = T;
-            hipLaunchKernelGGL(box_vote_tubes_kernel, dim3(ni, nc, VOTE_BLOCKS), dim3(VOTE_THREADS), 0, st, vt);
-        }
+        vp.thresh = o->bbox_vote_thresh; vp.T = T;
+        launch_box_vote(st, vp, dim3(ni, nc, VOTE_BLOCKS));
     }
     e.dets = (soft || vote) ? rows2 : dets; e.keep = keep; e.n_keep = n_keep; e.K = d->num_classes; e.T = T; e.cap = roi_cap; e.D = d->detections_per_im;
     e.out_cap = out_cap; e.img_ws = img_ws; e.dets_out = dets_out; e.kp_rois = keypoint_rois; e.n_out = n_out;
@@ -862,71 +678,62 @@ int dat_box_results_ex(dat_ctx* ctx, dat_stream s, const float* rois, const int*
                             out_cap, dets_out, keypoint_rois, n_out);
 }
 
-// Soft-NMS of n <= DAT_SOFT_NMS_MAX_BOXES device rows [n, 5]: the device twin of dat_soft_nms_host below.
-int dat_soft_nms(dat_ctx* ctx, dat_stream s, const float* dets, int n, float sigma, float Nt, float threshold, int method, float* dets_out,
-                 int* inds_out, int* n_out) {
-    DAT_ENFORCE(ctx, dets_out && inds_out && n_out && (dets || n == 0), "soft_nms: null argument");
-    DAT_ENFORCE(ctx, n >= 0 && n <= SOFT_NMS_CAP, "soft_nms: %d boxes (0..%d: the rows stay in LDS)", n, SOFT_NMS_CAP);
-    DAT_ENFORCE(ctx, method >= 0 && method <= 2, "soft_nms: method %d (0 hard, 1 linear, 2 gaussian)", method);
-    SoftParams sp;
-    memset(&sp, 0, sizeof(sp));
-    sp.dets = dets; sp.n_host = n; sp.out = dets_out; sp.inds = inds_out; sp.n_out = n_out; sp.cap = SOFT_NMS_CAP;
-    sp.method = method; sp.sigma = sigma; sp.Nt = Nt; sp.threshold = threshold;
-    hipLaunchKernelGGL(soft_nms_kernel, dim3(1, 1), dim3(SOFT_THREADS), 0, (hipStream_t)s, sp);
-    DAT_CHECK_LAUNCH(ctx, "soft_nms");
-    return DAT_OK;
-}
-
-// Box voting of n_top device rows [n_top, 5] by n_all device rows [n_all, 5] -> out [n_top, 5] (out may be top_dets).
-int dat_box_voting(dat_ctx* ctx, dat_stream s, const float* top_dets, int n_top, const float* all_dets, int n_all, float thresh, float* out) {
-    DAT_ENFORCE(ctx, n_top >= 0 && n_all >= 0 && (n_top == 0 || (top_dets && all_dets && out)), "box_voting: null argument or negative count");
-    if (n_top == 0) return DAT_OK;
-    DAT_ENFORCE(ctx, n_all >= 1, "box_voting: %d rows to refine and no row to vote with (the weight sum would be zero)", n_top);
-    VoteParams vp;
-    memset(&vp, 0, sizeof(vp));
-    vp.top = top_dets; vp.all = all_dets; vp.out = out; vp.n_top_host = n_top; vp.n_all_host = n_all; vp.thresh = thresh;
-    const int blocks = min((n_top + VOTE_THREADS / 64 - 1) / (VOTE_THREADS / 64), 1024);
-    hipLaunchKernelGGL(box_vote_kernel, dim3(1, 1, blocks), dim3(VOTE_THREADS), 0, (hipStream_t)s, vp);
-    DAT_CHECK_LAUNCH(ctx, "box_voting");
-    return DAT_OK;
-}
-
-int dat_soft_nms_tubes_max_boxes(int T) { return soft_tube_capacity(T); }
-
 // Soft-NMS of n <= dat_soft_nms_tubes_max_boxes(T) device rows [n, 4T+1]: the device twin of dat_soft_nms_tubes_host below.
-int dat_soft_nms_tubes(dat_ctx* ctx, dat_stream s, const float* dets, int n, int T, float sigma, float Nt, float threshold, int method,
-                       float* dets_out, int* inds_out, int* n_out) {
-    DAT_ENFORCE(ctx, dets_out && inds_out && n_out && (dets || n == 0), "soft_nms_tubes: null argument");
-    DAT_ENFORCE(ctx, T >= 1 && T <= DET_MAX_T, "soft_nms_tubes: T %d (1..%d)", T, DET_MAX_T);
-    DAT_ENFORCE(ctx, n >= 0 && n <= soft_tube_capacity(T), "soft_nms_tubes: %d tubes of %d frames (0..%d: the rows stay in LDS)", n, T,
+// `who`: the entry point the caller used, for the error texts.
+static int soft_nms_impl(dat_ctx* ctx, const char* who, dat_stream s, const float* dets, int n, int T, float sigma, float Nt, float threshold,
+                         int method, float* dets_out, int* inds_out, int* n_out) {
+    DAT_ENFORCE(ctx, dets_out && inds_out && n_out && (dets || n == 0), "%s: null argument", who);
+    DAT_ENFORCE(ctx, T >= 1 && T <= DET_MAX_T, "%s: T %d (1..%d)", who, T, DET_MAX_T);
+    DAT_ENFORCE(ctx, n >= 0 && n <= soft_tube_capacity(T), "%s: %d rows of %d frames (0..%d: the rows stay in LDS)", who, n, T,
                 soft_tube_capacity(T));
-    DAT_ENFORCE(ctx, method >= 0 && method <= 2, "soft_nms_tubes: method %d (0 hard, 1 linear, 2 gaussian)", method);
+    DAT_ENFORCE(ctx, method >= 0 && method <= 2, "%s: method %d (0 hard, 1 linear, 2 gaussian)", who, method);
     SoftParams sp;
     memset(&sp, 0, sizeof(sp));
     sp.dets = dets; sp.n_host = n; sp.out = dets_out; sp.inds = inds_out; sp.n_out = n_out; sp.cap = soft_tube_capacity(T);
     sp.method = method; sp.sigma = sigma; sp.Nt = Nt; sp.threshold = threshold;
-    const int rc = launch_soft_nms_tubes(ctx, (hipStream_t)s, sp, T, n, dim3(1, 1));
+    const int rc = launch_soft_nms(ctx, (hipStream_t)s, sp, T, n, dim3(1, 1));
     if (rc != DAT_OK) return rc;
-    DAT_CHECK_LAUNCH(ctx, "soft_nms_tubes");
+    DAT_CHECK_LAUNCH(ctx, who);
     return DAT_OK;
 }
 
 // Voting of n_top device rows [n_top, 4T+1] by n_all device rows [n_all, 4T+1] -> out [n_top, 4T+1] (out may be top_dets).
-int dat_box_voting_tubes(dat_ctx* ctx, dat_stream s, const float* top_dets, int n_top, const float* all_dets, int n_all, int T, float thresh,
-                         float* out) {
-    DAT_ENFORCE(ctx, n_top >= 0 && n_all >= 0 && (n_top == 0 || (top_dets && all_dets && out)), "box_voting_tubes: null argument or negative count");
-    DAT_ENFORCE(ctx, T >= 1 && T <= DET_MAX_T, "box_voting_tubes: T %d (1..%d)", T, DET_MAX_T);
+static int box_voting_impl(dat_ctx* ctx, const char* who, dat_stream s, const float* top_dets, int n_top, const float* all_dets, int n_all,
+                           int T, float thresh, float* out) {
+    DAT_ENFORCE(ctx, n_top >= 0 && n_all >= 0 && (n_top == 0 || (top_dets && all_dets && out)), "%s: null argument or negative count", who);
+    DAT_ENFORCE(ctx, T >= 1 && T <= DET_MAX_T, "%s: T %d (1..%d)", who, T, DET_MAX_T);
     if (n_top == 0) return DAT_OK;
-    DAT_ENFORCE(ctx, n_all >= 1, "box_voting_tubes: %d rows to refine and no row to vote with (the weight sum would be zero)", n_top);
-    VoteTubeParams vt;
-    memset(&vt, 0, sizeof(vt));
-    vt.v.top = top_dets; vt.v.all = all_dets; vt.v.out = out; vt.v.n_top_host = n_top; vt.v.n_all_host = n_all; vt.v.thresh = thresh;
-    vt.T = T;
+    DAT_ENFORCE(ctx, n_all >= 1, "%s: %d rows to refine and no row to vote with (the weight sum would be zero)", who, n_top);
+    VoteParams vp;
+    memset(&vp, 0, sizeof(vp));
+    vp.top = top_dets; vp.all = all_dets; vp.out = out; vp.n_top_host = n_top; vp.n_all_host = n_all; vp.thresh = thresh; vp.T = T;
     const int blocks = min((n_top + VOTE_THREADS / 64 - 1) / (VOTE_THREADS / 64), 1024);
-    hipLaunchKernelGGL(box_vote_tubes_kernel, dim3(1, 1, blocks), dim3(VOTE_THREADS), 0, (hipStream_t)s, vt);
-    DAT_CHECK_LAUNCH(ctx, "box_voting_tubes");
+    launch_box_vote((hipStream_t)s, vp, dim3(1, 1, blocks));
+    DAT_CHECK_LAUNCH(ctx, who);
     return DAT_OK;
 }
+
+// (include/dat_hip.h) the box entry points are the tube ones at T = 1
+int dat_soft_nms(dat_ctx* ctx, dat_stream s, const float* dets, int n, float sigma, float Nt, float threshold, int method, float* dets_out,
+                 int* inds_out, int* n_out) {
+    return soft_nms_impl(ctx, "soft_nms", s, dets, n, 1, sigma, Nt, threshold, method, dets_out, inds_out, n_out);
+}
+
+int dat_soft_nms_tubes(dat_ctx* ctx, dat_stream s, const float* dets, int n, int T, float sigma, float Nt, float threshold, int method,
+                       float* dets_out, int* inds_out, int* n_out) {
+    return soft_nms_impl(ctx, "soft_nms_tubes", s, dets, n, T, sigma, Nt, threshold, method, dets_out, inds_out, n_out);
+}
+
+int dat_box_voting(dat_ctx* ctx, dat_stream s, const float* top_dets, int n_top, const float* all_dets, int n_all, float thresh, float* out) {
+    return box_voting_impl(ctx, "box_voting", s, top_dets, n_top, all_dets, n_all, 1, thresh, out);
+}
+
+int dat_box_voting_tubes(dat_ctx* ctx, dat_stream s, const float* top_dets, int n_top, const float* all_dets, int n_all, int T, float thresh,
+                         float* out) {
+    return box_voting_impl(ctx, "box_voting_tubes", s, top_dets, n_top, all_dets, n_all, T, thresh, out);
+}
+
+int dat_soft_nms_tubes_max_boxes(int T) { return soft_tube_capacity(T); }
 
 int dat_box_results(dat_ctx* ctx, dat_stream s, const float* rois, const int* n_rois, int roi_cap, const float* cls_prob, int prob_ld,
                     const float* bbox_pred, int pred_ld, const dat_det_desc* d, void* workspace, int out_cap, float* dets_out,
@@ -935,64 +742,13 @@ int dat_box_results(dat_ctx* ctx, dat_stream s, const float* rois, const int* n_
                                  keypoint_rois, n_out);
 }
 
-// Soft-NMS on the HOST (lib/utils/cython_nms.pyx:98-203; caller lib/core/nms_wrapper.py:29-46, lib/core/test.py:766-772): the
-// greedy in-place re-scoring loop in C float arithmetic, statement for statement what Cython emits for the reference's .pyx
-// (differences in float, `+ 1` and the area products in double, the Gaussian weight through a double exp, the
-// discard-by-swap-with-last that makes the result order-dependent).  Plain host code: the comparison path of dat_soft_nms (soft_nms_kernel above) and what core/nms_wrapper.soft_nms runs for host arrays.
-int dat_soft_nms_host(const float* boxes_in, int n, float sigma, float Nt, float threshold, int method, float* boxes_out,
-                      int* inds_out, int* n_out) {
-    if (!boxes_in || !boxes_out || !inds_out || !n_out || n < 0 || method < 0 || method > 2) return DAT_ERR_ARG;
-    float* b = boxes_out;
-    memcpy(b, boxes_in, (size_t)n * 5 * sizeof(float));
-    for (int i = 0; i < n; ++i) inds_out[i] = i;
-    int N = n;
-    for (int i = 0; i < N; ++i) {
-        float maxscore = b[i * 5 + 4];
-        int maxpos = i;
-        float tx1 = b[i * 5 + 0], ty1 = b[i * 5 + 1], tx2 = b[i * 5 + 2], ty2 = b[i * 5 + 3], ts = b[i * 5 + 4];
-        const int ti = inds_out[i];
-        for (int pos = i + 1; pos < N; ++pos)
-            if (maxscore < b[pos * 5 + 4]) { maxscore = b[pos * 5 + 4]; maxpos = pos; }
-        for (int c = 0; c < 5; ++c) b[i * 5 + c] = b[maxpos * 5 + c];
-        inds_out[i] = inds_out[maxpos];
-        b[maxpos * 5 + 0] = tx1; b[maxpos * 5 + 1] = ty1; b[maxpos * 5 + 2] = tx2; b[maxpos * 5 + 3] = ty2; b[maxpos * 5 + 4] = ts;
-        inds_out[maxpos] = ti;
-        tx1 = b[i * 5 + 0]; ty1 = b[i * 5 + 1]; tx2 = b[i * 5 + 2]; ty2 = b[i * 5 + 3];
-        int pos = i + 1;
-        while (pos < N) {
-            const float x1 = b[pos * 5 + 0], y1 = b[pos * 5 + 1], x2 = b[pos * 5 + 2], y2 = b[pos * 5 + 3];
-            // (`+ 1` is a DOUBLE constant in the C that Cython emits for the .pyx: sums and the area products are formed in double and
-            //  rounded once to float where the .pyx assigns a `cdef float`)
-            const float area = (float)(((double)(x2 - x1) + 1.0) * ((double)(y2 - y1) + 1.0));
-            const float iw = (float)((double)(fminf(tx2, x2) - fmaxf(tx1, x1)) + 1.0);
-            if (iw > 0) {
-                const float ih = (float)((double)(fminf(ty2, y2) - fmaxf(ty1, y1)) + 1.0);
-                if (ih > 0) {
-                    const float ua = (float)((((double)(tx2 - tx1) + 1.0) * ((double)(ty2 - ty1) + 1.0) + (double)area) - (double)(iw * ih));
-                    const float ov = iw * ih / ua;
-                    float weight;
-                    if (method == 1) weight = ov > Nt ? (float)(1.0 - (double)ov) : 1.f;
-                    else if (method == 2) weight = (float)exp((double)(-(ov * ov) / sigma));
-                    else weight = ov > Nt ? 0.f : 1.f;
-                    b[pos * 5 + 4] = weight * b[pos * 5 + 4];
-                    if (b[pos * 5 + 4] < threshold) {   // discard: swap with the last box, shrink N, revisit this slot
-                        for (int c = 0; c < 5; ++c) b[pos * 5 + c] = b[(N - 1) * 5 + c];
-                        inds_out[pos] = inds_out[N - 1];
-                        --N;
-                        --pos;
-                    }
-                }
-            }
-            ++pos;
-        }
-    }
-    *n_out = N;
-    return DAT_OK;
-}
-
-// dat_soft_nms_host for rows [n, 4T+1] (include/dat_hip.h): the same serial loop, the per-pair overlap being the float32 mean of the
-// per-frame IoUs in frame order, and a pair re-scored iff that overlap is > 0.  Plain host code: the comparison path of
-// dat_soft_nms_tubes and what core/nms_wrapper.soft_nms runs for tube rows with HIP.TUBE_SOFT_NMS.
+// Soft-NMS on the HOST for rows [n, 4T+1] (include/dat_hip.h).  At T = 1 it is lib/utils/cython_nms.pyx:98-203 (caller
+// lib/core/nms_wrapper.py:29-46, lib/core/test.py:766-772): the greedy in-place re-scoring loop in C float arithmetic, statement for
+// statement what Cython emits for the reference's .pyx (differences in float, `+ 1` and the area products in double, the Gaussian
+// weight through a double exp, the discard-by-swap-with-last that makes the result order-dependent).  For tubes the per-pair overlap
+// is the float32 mean of the per-frame IoUs in frame order, and a pair is re-scored iff that overlap is > 0 (at T = 1: iff iw > 0 and
+// ih > 0, as the .pyx nests it).  Plain host code: the comparison path of soft_nms_kernel above and what core/nms_wrapper.soft_nms
+// runs for host arrays (tube rows with HIP.TUBE_SOFT_NMS).
 int dat_soft_nms_tubes_host(const float* boxes_in, int n, int T, float sigma, float Nt, float threshold, int method, float* boxes_out,
                             int* inds_out, int* n_out) {
     if (!boxes_in || !boxes_out || !inds_out || !n_out || n < 0 || method < 0 || method > 2 || T < 1 || T > DET_MAX_T) return DAT_ERR_ARG;
@@ -1021,6 +777,8 @@ int dat_soft_nms_tubes_host(const float* boxes_in, int n, int T, float sigma, fl
             for (int t = 0; t < T; ++t) {
                 const float tx1 = a[4 * t], ty1 = a[4 * t + 1], tx2 = a[4 * t + 2], ty2 = a[4 * t + 3];
                 const float x1 = r[4 * t], y1 = r[4 * t + 1], x2 = r[4 * t + 2], y2 = r[4 * t + 3];
+                // (`+ 1` is a DOUBLE constant in the C that Cython emits for the .pyx: sums and the area products are formed in double and
+                //  rounded once to float where the .pyx assigns a `cdef float`)
                 const float area = (float)(((double)(x2 - x1) + 1.0) * ((double)(y2 - y1) + 1.0));
                 const float iw = (float)((double)(fminf(tx2, x2) - fmaxf(tx1, x1)) + 1.0);
                 float iou = 0.f;
@@ -1052,6 +810,11 @@ int dat_soft_nms_tubes_host(const float* boxes_in, int n, int T, float sigma, fl
     }
     *n_out = N;
     return DAT_OK;
+}
+
+int dat_soft_nms_host(const float* boxes_in, int n, float sigma, float Nt, float threshold, int method, float* boxes_out,
+                      int* inds_out, int* n_out) {
+    return dat_soft_nms_tubes_host(boxes_in, n, 1, sigma, Nt, threshold, method, boxes_out, inds_out, n_out);
 }
 
 }  // extern "C"

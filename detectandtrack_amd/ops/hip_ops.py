@@ -1161,34 +1161,49 @@ SOFT_NMS_METHODS = {'hard': 0, 'linear': 1, 'gaussian': 2}
 SOFT_NMS_MAX_BOXES = 2048      # DAT_SOFT_NMS_MAX_BOXES: a class's rows stay in LDS
 
 
+def _soft_nms(entry, extra, dets, sigma, overlap_thresh, score_thresh, method):
+    """The output buffers, the method lookup and the call of `entry` (dat_soft_nms / dat_soft_nms_tubes; extra: the arguments between
+    n and sigma)."""
+    assert dets.dtype == torch.float32
+    m = SOFT_NMS_METHODS[method] if isinstance(method, str) else int(method)
+    n = int(dets.shape[0])
+    out = torch.empty((max(n, 1), dets.shape[1]), dtype=torch.float32, device=dets.device)
+    inds = torch.empty((max(n, 1),), dtype=torch.int32, device=dets.device)
+    cnt = torch.empty((1,), dtype=torch.int32, device=dets.device)
+    ctx().call(entry, _stream(), _ptr(dets.contiguous()), n, *extra, C.c_float(sigma), C.c_float(overlap_thresh), C.c_float(score_thresh), m,
+               _ptr(out), _ptr(inds), _ptr(cnt))
+    return out[:n], inds[:n], cnt
+
+
 def soft_nms(dets, sigma=0.5, overlap_thresh=0.3, score_thresh=0.001, method='linear'):
     """dat_soft_nms (lib/utils/cython_nms.pyx:98-203 on the device): dets CUDA fp32 [n <= SOFT_NMS_MAX_BOXES, 5]; returns
     (re-scored rows [n, 5], original row indices int32 [n], count int32[1]) on the device -- the first count[0] rows are the result,
     in the order the greedy loop leaves them; no host synchronisation."""
     if dets.dim() != 2 or dets.shape[1] != 5:
         raise NotImplementedError('Need to handle tubes..')       # (lib/core/nms_wrapper.py:34-35)
-    assert dets.dtype == torch.float32
-    m = SOFT_NMS_METHODS[method] if isinstance(method, str) else int(method)
-    n = int(dets.shape[0])
-    out = torch.empty((max(n, 1), 5), dtype=torch.float32, device=dets.device)
-    inds = torch.empty((max(n, 1),), dtype=torch.int32, device=dets.device)
-    cnt = torch.empty((1,), dtype=torch.int32, device=dets.device)
-    ctx().call('dat_soft_nms', _stream(), _ptr(dets.contiguous()), n, C.c_float(sigma), C.c_float(overlap_thresh), C.c_float(score_thresh), m,
-               _ptr(out), _ptr(inds), _ptr(cnt))
-    return out[:n], inds[:n], cnt
+    return _soft_nms('dat_soft_nms', (), dets, sigma, overlap_thresh, score_thresh, method)
+
+
+def _box_voting(entry, extra, top_dets, all_dets, thresh, out=None):
+    """The destination and the call of `entry` (dat_box_voting / dat_box_voting_tubes; extra: the arguments between n_all and thresh)."""
+    assert top_dets.dtype == all_dets.dtype == torch.float32
+    top_dets = top_dets.contiguous()
+    if out is None:
+        out = torch.empty_like(top_dets)
+    assert out.is_contiguous() and out.shape == top_dets.shape and out.dtype == torch.float32
+    ctx().call(entry, _stream(), _ptr(top_dets), int(top_dets.shape[0]), _ptr(all_dets.contiguous()), int(all_dets.shape[0]), *extra,
+               C.c_float(thresh), _ptr(out))
+    return out
 
 
 def box_voting(top_dets, all_dets, thresh):
     """dat_box_voting (lib/utils/boxes.py:294-310 on the device): CUDA fp32 [n_top, 5], [n_all, 5] -> voted rows [n_top, 5]."""
-    assert top_dets.dtype == all_dets.dtype == torch.float32 and top_dets.shape[1] == 5 and all_dets.shape[1] == 5
-    out = torch.empty_like(top_dets, memory_format=torch.contiguous_format)
-    ctx().call('dat_box_voting', _stream(), _ptr(top_dets.contiguous()), int(top_dets.shape[0]), _ptr(all_dets.contiguous()),
-               int(all_dets.shape[0]), C.c_float(thresh), _ptr(out))
-    return out
+    assert top_dets.shape[1] == 5 and all_dets.shape[1] == 5
+    return _box_voting('dat_box_voting', (), top_dets, all_dets, thresh)
 
 
 def soft_nms_tubes_max_boxes(T):
-    """dat_soft_nms_tubes_max_boxes: the rows of 4T coordinates the tube Soft-NMS kernel holds in LDS (2048 for T <= 4, falling with T;
+    """dat_soft_nms_tubes_max_boxes: the rows of 4T coordinates the Soft-NMS kernel holds in LDS (2048 for T <= 4, falling with T;
     0 for T outside 1..16)."""
     return int(L.lib().dat_soft_nms_tubes_max_boxes(int(T)))
 
@@ -1198,29 +1213,16 @@ def soft_nms_tubes(dets, T, sigma=0.5, overlap_thresh=0.3, score_thresh=0.001, m
     [n <= soft_nms_tubes_max_boxes(T), 4T+1]; returns (re-scored rows [n, 4T+1], original row indices int32 [n], count int32[1]) on the
     device, as soft_nms does."""
     T = int(T)
-    assert dets.dim() == 2 and dets.shape[1] == 4 * T + 1 and dets.dtype == torch.float32
-    m = SOFT_NMS_METHODS[method] if isinstance(method, str) else int(method)
-    n = int(dets.shape[0])
-    out = torch.empty((max(n, 1), 4 * T + 1), dtype=torch.float32, device=dets.device)
-    inds = torch.empty((max(n, 1),), dtype=torch.int32, device=dets.device)
-    cnt = torch.empty((1,), dtype=torch.int32, device=dets.device)
-    ctx().call('dat_soft_nms_tubes', _stream(), _ptr(dets.contiguous()), n, T, C.c_float(sigma), C.c_float(overlap_thresh),
-               C.c_float(score_thresh), m, _ptr(out), _ptr(inds), _ptr(cnt))
-    return out[:n], inds[:n], cnt
+    assert dets.dim() == 2 and dets.shape[1] == 4 * T + 1
+    return _soft_nms('dat_soft_nms_tubes', (T,), dets, sigma, overlap_thresh, score_thresh, method)
 
 
 def box_voting_tubes(top_dets, all_dets, T, thresh, out=None):
     """dat_box_voting_tubes: CUDA fp32 [n_top, 4T+1], [n_all, 4T+1] -> voted rows [n_top, 4T+1] (all 4T coordinates; the score stays).
     out: optional destination; it may be top_dets itself (in place)."""
     T = int(T)
-    assert top_dets.dtype == all_dets.dtype == torch.float32 and top_dets.shape[1] == all_dets.shape[1] == 4 * T + 1
-    top_dets = top_dets.contiguous()
-    if out is None:
-        out = torch.empty_like(top_dets)
-    assert out.is_contiguous() and out.shape == top_dets.shape and out.dtype == torch.float32
-    ctx().call('dat_box_voting_tubes', _stream(), _ptr(top_dets), int(top_dets.shape[0]), _ptr(all_dets.contiguous()),
-               int(all_dets.shape[0]), T, C.c_float(thresh), _ptr(out))
-    return out
+    assert top_dets.shape[1] == all_dets.shape[1] == 4 * T + 1
+    return _box_voting('dat_box_voting_tubes', (T,), top_dets, all_dets, thresh, out)
 
 
 def box_results(rois, n_rois, cls_prob, bbox_pred, num_classes, T, im_scale, im_shape, reg_weights, xform_clip, score_thresh,
@@ -1232,7 +1234,7 @@ def box_results(rois, n_rois, cls_prob, bbox_pred, num_classes, T, im_scale, im_
     [n_images * out_cap, 4T+1] (col 0 = image index) and n_out int32[n_images, 2].
     soft_nms: None | dict(method='hard'|'linear'|'gaussian', sigma, score_thresh) -- TEST.SOFT_NMS in place of the NMS (overlap
     threshold = nms_thresh; detections carry the re-scored scores); bbox_vote: None | the voting IoU threshold (TEST.BBOX_VOTE).
-    Either one routes to dat_box_results_ex (T == 1, or any T with tubes=True -- cfg.HIP.TUBE_SOFT_NMS: the tube kernels)."""
+    Either one routes to dat_box_results_ex (T == 1, or any T with tubes=True -- cfg.HIP.TUBE_SOFT_NMS; the same kernels for every T)."""
     ni = int(n_images)
     cap = int(rois.shape[0]) // ni
     assert cap * ni == int(rois.shape[0])

@@ -362,9 +362,10 @@ int dat_box_results_batch(dat_ctx* ctx, dat_stream s, const float* rois, const i
 
 /* ---- Soft-NMS and box voting on the device (lib/core/test.py:766-779) ----------------------------------------------------------
  * Soft-NMS keeps a class's rows in LDS for the whole greedy loop (one block per image and class), so it accepts at most
- * DAT_SOFT_NMS_MAX_BOXES rows (2048 x 27 bytes = 54 KB of the 64 KB a block may declare; the reference's TEST.RPN_POST_NMS_TOP_N
- * is 1000); more is a DAT_ERR_ARG.  These entry points take boxes only (T = 1): the reference has no Soft-NMS for tubes
- * (lib/core/nms_wrapper.py:34-35); this project's definition for tubes has entry points of its own, further below. */
+ * DAT_SOFT_NMS_MAX_BOXES rows (= dat_soft_nms_tubes_max_boxes(1); the reference's TEST.RPN_POST_NMS_TOP_N is 1000); more is a
+ * DAT_ERR_ARG.  These entry points take boxes only: the reference has no Soft-NMS for tubes (lib/core/nms_wrapper.py:34-35).  They
+ * are the tube entry points further below at T = 1 -- one kernel and one host loop serve both -- and keep their own names in the
+ * error texts. */
 #define DAT_SOFT_NMS_MAX_BOXES 2048
 /* The device twin of dat_soft_nms_host: dets fp32 [n, 5] -> dets_out [*n_out <= n, 5] (re-scored, in the order the greedy loop leaves
  * them), inds_out (rows of dets), n_out int32[1]; all DEVICE pointers, buffers of n rows, no host synchronisation.  method 0 = hard,
@@ -382,7 +383,7 @@ int dat_box_voting(dat_ctx* ctx, dat_stream s, const float* top_dets, int n_top,
  * dat_det_desc.nms_thresh, as the reference passes TEST.NMS) and the detections carry the RE-SCORED scores, on which the
  * DETECTIONS_PER_IM rule (and n_out[1]) then works; voting replaces the kept boxes' coordinates, and keypoint_rois are formed from
  * the voted boxes.  With both switches off this IS dat_box_results_batch (same code, same workspace size, byte-identical outputs).
- * Requires T == 1 when a switch is on unless tubes_enabled is set (then T <= 16 and the tube kernels below run), and
+ * Requires T == 1 when a switch is on unless tubes_enabled is set (then T <= 16; the kernels are the same for every T), and
  * roi_cap <= dat_soft_nms_tubes_max_boxes(T) with Soft-NMS (= DAT_SOFT_NMS_MAX_BOXES for T <= 4).  workspace: n_images x
  * dat_box_results_ex_workspace_bytes. */
 typedef struct {
@@ -401,7 +402,8 @@ int dat_box_results_ex(dat_ctx* ctx, dat_stream s, const float* rois, const int*
 
 /* Soft-NMS, HOST pointers, host arithmetic (lib/utils/cython_nms.pyx:98-203 statement for statement in C float): boxes_in
  * [n, 5] -> boxes_out [*n_out <= n, 5] (re-scored, in the order the greedy loop leaves them) and inds_out (rows of boxes_in).
- * method 0 = hard, 1 = linear, 2 = gaussian (nms_wrapper.py:37).  Buffers hold n rows.  The comparison path of dat_soft_nms. */
+ * method 0 = hard, 1 = linear, 2 = gaussian (nms_wrapper.py:37).  Buffers hold n rows.  The comparison path of dat_soft_nms;
+ * dat_soft_nms_tubes_host with T = 1. */
 int dat_soft_nms_host(const float* boxes_in, int n, float sigma, float Nt, float threshold, int method, float* boxes_out,
                       int* inds_out, int* n_out);
 
@@ -414,7 +416,8 @@ int dat_soft_nms_host(const float* boxes_in, int n, float sigma, float Nt, float
  * for bit, and with method 0 it keeps the rows py_cpu_nms_tubes keeps, in its order.  Voting replaces ALL 4T coordinates of a
  * kept row by the score-weighted means over the rows whose ov with it (the kept row in a's role) is >= thresh.
  *
- * The device kernel keeps a class's rows in dynamic LDS, 16T + 11 bytes each, within the 160 KB of a gfx950 workgroup:
+ * The device kernel (the one dat_soft_nms runs at T = 1) keeps a class's rows in dynamic LDS, 16T + 11 bytes each, within the
+ * 160 KB of a gfx950 workgroup:
  * dat_soft_nms_tubes_max_boxes(T) = the largest multiple of 64 that fits, at most DAT_SOFT_NMS_MAX_BOXES (2048 for T <= 4, 1792 for
  * T = 5, 1024 for T = 9, 576 for T = 16); 0 for T outside 1..16. */
 int dat_soft_nms_tubes_max_boxes(int T);

@@ -1,5 +1,5 @@
-"""GPU tests of Soft-NMS and box voting for tubes (cfg.HIP.TUBE_SOFT_NMS; csrc/detections.hip: soft_nms_tubes_kernel,
-box_vote_tubes_kernel, dat_box_results_ex with tubes_enabled) and of the engine paths the switch opens for tube models."""
+"""GPU tests of Soft-NMS and box voting for tubes (cfg.HIP.TUBE_SOFT_NMS; csrc/detections.hip: soft_nms_kernel,
+box_vote_kernel, dat_box_results_ex with tubes_enabled) and of the engine paths the switch opens for tube models."""
 import ctypes as C
 import os
 
@@ -40,7 +40,7 @@ def _assert_exercised(dets, ref_d, ref_i, name, rescored=True):
 
 # ---- dat_soft_nms_tubes ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('method', ['hard', 'linear'])
-@pytest.mark.parametrize('T', [2, 3])
+@pytest.mark.parametrize('T', [1, 2, 3])
 def test_soft_nms_tubes_hard_and_linear_are_bit_identical_to_the_host_twin(ops, T, method):
     """Methods 0 and 1 have no transcendental: rows, order, indices and scores of dat_soft_nms_tubes equal dat_soft_nms_tubes_host bit
     for bit, from no row to the capacity, across the wave and block boundaries (63 / 64 / 65, 257), on dense continuous inputs and
@@ -100,7 +100,7 @@ def test_soft_nms_tubes_gaussian_matches_the_host_twin(ops):
 
 
 # ---- dat_box_voting_tubes ----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('T', [2, 3])
+@pytest.mark.parametrize('T', [1, 2, 3])
 def test_box_voting_tubes_is_the_float64_mean_and_repeats_bit_for_bit(ops, T):
     """All 4T coordinates within one float32 ulp of the float64 score-weighted mean over the voters the float32 tube overlap selects;
     scores untouched; two runs bit-identical (fixed summation order); in place (out is top) equals out of place."""

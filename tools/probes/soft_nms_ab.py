@@ -1,7 +1,7 @@
 """Soft-NMS / box voting on the device: what they cost.
 
     python tools/probes/soft_nms_ab.py [rois per image] [images per launch] [frames per tube]
-        (frames per tube > 1: tube detections through the kernels of HIP.TUBE_SOFT_NMS)
+        (frames per tube > 1: tube detections, HIP.TUBE_SOFT_NMS; soft_nms_kernel / box_vote_kernel for every T)
         ops.box_results (select + decode, NMS or Soft-NMS, voting, limit + emit) with each Soft-NMS method and with voting against
         hard NMS on the same clustered synthetic proposals: hip events, median of 50 launches after 10 warm-up launches.
     python tools/probes/soft_nms_ab.py e2e <tree> [cfg opts ...]
