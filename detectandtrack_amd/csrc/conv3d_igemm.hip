@@ -45,6 +45,10 @@ namespace {
 // s_load + s_waitcnt lgkmcnt(0) they cost per tap also drained the LDS queue), the weight pointer advances by a scalar add, and the
 // per-lane source offsets of the patch LDS-DMA are kept in registers across reloads.  NTAP = 0: the generic table-driven loop
 // (strided 3x3 convs with their stride-parity planes, other kernel shapes).
+// NTAP = 19: the NTAP = 9 variant for DILATED 3x3 layers on linear strips -- the one place where a kernel has to know the dilation: "the
+// neighbour left my map" is decided d rows / columns away, d read from the tap table (tab_rowoff[1], the offset of tap (0, 1)).  Its own
+// instantiations, so the NTAP = 9 ones compile as they always did.  (On 2-D tiles a dilated layer runs the NTAP = 9 / NTAP = 0 variants
+// themselves: the dilation is all in the host-built patch geometry.)
 // (the unrolled 128-position variants are held to 168 registers -- three blocks per CU -- the 256-position ones to 256)
 template <int BP, int NTAP> struct MinWaves { static constexpr int value = (NTAP > 0 && NTAP != 10 && BP == 128) ? 3 : 2; };
 //
@@ -176,7 +180,8 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
     const char* const wd_lane = p.w + (size_t)((n0 + wave_n * WN) >> 5) * 4096 + lane * 16;
 #define WD_PTR(KT_, CC_, TI_) (wd_lane + ((size_t)((KT_) * ntap + p.tab_tap[(TI_)]) * p.n_cchunks + (CC_)) * wd_cc_stride)
     if constexpr (NTAP > 0) {
-      constexpr int NT = NTAP == 10 ? 9 : NTAP;   // NTAP = 10: the 9 taps of a 3x3 stride-2 conv on ONE dense (2*TH+1) x (2*TW+1) patch
+      constexpr int NT = (NTAP == 10 || NTAP == 19) ? 9 : NTAP;   // NTAP = 10: the 9 taps of a 3x3 stride-2 conv on ONE dense (2*TH+1) x (2*TW+1) patch
+      constexpr bool LIN_DIL = NTAP == 19;        // dilated strips: neighbours are tab_rowoff[1] rows / columns away
       if (total > 0) {
         constexpr int MAXCH = patch_pieces_per_wave(NTAP, BP);   // 1-KiB patch pieces per wave (the launcher checks nchunks <= 4 * MAXCH)
         const int kt_hi_x = kt_lo + n_kt;
@@ -210,7 +215,8 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
                 for (int tp = 0; tp < NT; ++tp) {
                     int row = rowbase[j] + p.tab_rowoff[tp];
                     if (p.lin_w > 0) {   // linear tiling: a tap that leaves the lane's map (row / column / map border) reads the zero row
-                        const int yy = lin_y + tp / 3 - 1, xx = lin_x + tp % 3 - 1;
+                        const int yy = LIN_DIL ? lin_y + (tp / 3 - 1) * p.tab_rowoff[1] : lin_y + tp / 3 - 1;
+                        const int xx = LIN_DIL ? lin_x + (tp % 3 - 1) * p.tab_rowoff[1] : lin_x + tp % 3 - 1;
                         if ((unsigned)yy >= (unsigned)p.lin_h || (unsigned)xx >= (unsigned)p.lin_w) row = p.lin_zero_row;
                     }
                     const unsigned a16 = patch_frag_addr<MF>(row, MF ? lane >> 4 : khalf);
@@ -229,7 +235,8 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<BP, NTAP>::value)) void conv3d_
                         const int gpos = ow0 + wave_p * WP + (MF ? j * 16 + (lane & 15) : j * 32 + (lane & 31));
                         const int rem = gpos % (p.lin_h * p.lin_w);
                         const int y = rem / p.lin_w, x = rem - y * p.lin_w;
-                        const int yy = y + tp / p.KW - p.KH / 2, xx = x + tp % p.KW - p.KW / 2;
+                        const int yy = LIN_DIL ? y + (tp / p.KW - p.KH / 2) * p.tab_rowoff[1] : y + tp / p.KW - p.KH / 2;
+                        const int xx = LIN_DIL ? x + (tp % p.KW - p.KW / 2) * p.tab_rowoff[1] : x + tp % p.KW - p.KW / 2;
                         if ((unsigned)yy >= (unsigned)p.lin_h || (unsigned)xx >= (unsigned)p.lin_w) row = p.lin_zero_row;
                     }
                     const unsigned a16 = patch_frag_addr<MF>(row, MF ? lane >> 4 : khalf);
@@ -758,9 +765,10 @@ static long long linear_tiles(const dat_ctx* ctx, const dat_conv_desc* d, const 
     if (!ctx->dbg_linear || !ctx->dbg_ntap || d->KH != 3 || d->KW != 3 || d->stride_h != 1 || d->stride_w != 1 || d->res_mode == 2 ||
         p.H != p.Ho || p.W != p.Wo)
         return 0;
+    const int dil = conv_dilation(d);            // (H == Ho: the pads are dil; the strip widens by dil * (W + 1) on either side)
     if (d->KT == 1 && (d->pad_t != 0 || d->out_tn > 0)) return 0;
     const long long per = d->KT > 1 ? (long long)p.Ho * p.Wo : (long long)p.frames * p.Ho * p.Wo;
-    const long long nr = bpv + 2 * (p.Wo + 1) + 1;
+    const long long nr = bpv + 2 * dil * (p.Wo + 1) + 1;
     if (((nr * 8 + 63) >> 6) > 4 * patch_pieces_per_wave(9, bpv) || nr * PPITCH >= 65536 ||
         per * std::max(p.Cin, std::max(p.out_cs, p.Cout)) * 4 >= (1ll << 31))
         return 0;
@@ -832,8 +840,10 @@ int conv_set_frame_window(dat_ctx* ctx, const dat_conv_desc* d, ConvParams& p, c
 namespace {
 
 template <int DT, int BN, int BP, int WAVES_N, int NTAP, int ODT, int MF = 0>
-int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ksplit, bool linear = false) {
-    TileChoice tc = choose_tile(p.Ho, p.Wo, bp_log2, p.sh, p.sw, p.KH, p.KW);
+int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ksplit, bool linear = false, int dil = 1) {
+    // dil > 1 (stride 1, checked by the caller): the same loops over a wider patch -- the halo is (K - 1) * dil cells and tap (kh, kw) sits
+    // kh * dil rows and kw * dil columns into it.  Only this host-built geometry knows the dilation; the kernels read it from the table.
+    TileChoice tc = choose_tile(p.Ho, p.Wo, bp_log2, p.sh, p.sw, (p.KH - 1) * dil + 1, (p.KW - 1) * dil + 1);
     p.lin_h = p.lin_w = 0;
     p.lin_zero_row = -1;
     if (linear) {
@@ -848,15 +858,15 @@ int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ks
         // temporal taps differ; the frame / clip bookkeeping of the kernel stays as it is.
         const bool per_frame = p.KT > 1;
         const long long total = per_frame ? (long long)p.Ho * p.Wo : (long long)p.frames * p.Ho * p.Wo;
-        DAT_ENFORCE(ctx, NTAP == 9 && (per_frame || p.pt == 0) && p.sh == 1 && p.sw == 1 && p.H == p.Ho && p.W == p.Wo && p.res_mode != 2 &&
+        DAT_ENFORCE(ctx, ((NTAP == 9 && dil == 1) || (NTAP == 19 && dil > 1)) && (per_frame || p.pt == 0) && p.sh == 1 && p.sw == 1 && p.H == p.Ho && p.W == p.Wo && p.res_mode != 2 &&
                              total * std::max(p.Cin, std::max(p.out_cs, p.Cout)) * 4 < (1ll << 31),
                     "conv3d: linear tiling on an unsupported layer");
         p.lin_h = p.H; p.lin_w = p.W;
-        const int wr = p.W, nr = BP + 2 * (wr + 1) + 1;
+        const int wr = p.W, nr = BP + 2 * dil * (wr + 1) + 1;
         tc = TileChoice{0, bp_log2};
         p.H = p.Ho = 1; p.W = p.Wo = (int)total;
         if (!per_frame) { p.frames = 1; p.T = 1; p.ot0 = 0; p.otn = 1; p.in_lo = 0; p.in_hi = 1; }
-        p.ph = 0; p.pw = wr + 1;
+        p.ph = 0; p.pw = dil * (wr + 1);
         p.lin_zero_row = nr - 1;
         p.th_log2 = 0; p.tw_log2 = bp_log2;
         p.tile_w = BP;
@@ -864,7 +874,7 @@ int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ks
         p.psh = p.psw = 1; p.rsh = p.rsw = 1;
         p.PH = 1; p.PW = nr;
         p.tab_new = 1u; p.tab_n = 9;
-        for (int i = 0; i < 9; ++i) { p.tab_tap[i] = i; p.tab_rowoff[i] = (i / 3) * wr + i % 3; p.tab_dy[i] = p.tab_dx[i] = 0; }
+        for (int i = 0; i < 9; ++i) { p.tab_tap[i] = i; p.tab_rowoff[i] = (i / 3) * dil * wr + (i % 3) * dil; p.tab_dy[i] = p.tab_dx[i] = 0; }
     }
     const int th = 1 << tc.th_log2, tw = 1 << tc.tw_log2;
     if (!linear) {
@@ -876,8 +886,8 @@ int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ks
     p.psh = p.sh;
     p.psw = p.sw;
     p.rsh = p.rsw = 1;
-    p.PH = th + (p.KH - 1) / p.sh;
-    p.PW = tw + (p.KW - 1) / p.sw;
+    p.PH = th + (p.KH - 1) * dil / p.sh;
+    p.PW = tw + (p.KW - 1) * dil / p.sw;
     }
     if (linear) {
     } else if (NTAP == 10) {   // one DENSE patch for all 9 taps of a strided 3x3: neighbouring outputs are `stride` patch cells apart
@@ -895,6 +905,8 @@ int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ks
     } else {
         DAT_ENFORCE(ctx, p.KH * p.KW <= 32, "conv3d: %dx%d spatial kernel exceeds the 32-entry tap table", p.KH, p.KW);
         conv_build_tap_table(p);
+        if (dil > 1)   // (stride 1: one plane, taps in natural order)
+            for (int i = 0; i < p.tab_n; ++i) p.tab_rowoff[i] = (p.tab_tap[i] / p.KW) * dil * p.PW + (p.tab_tap[i] % p.KW) * dil;
     }
     p.pw_magic = conv_pw_magic(p.PW);
     p.n_cchunks = p.x3 ? p.Cin / Mma<DT>::CK / 2 * 3 : p.Cin / Mma<DT>::CK;   // bf16x3: [hi | hi | lo] against [W_hi | W_lo | W_hi]
@@ -928,11 +940,15 @@ int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ks
     p.order = ctx->dbg_order > 0;
     size_t lds = ((size_t)p.PH * p.PW * PPITCH + 1023) & ~(size_t)1023;     // whole 1-KiB DMA pieces
     if (lds < EPI_SLICES_BYTES) lds = EPI_SLICES_BYTES;                     // epilogue staging slices
+    if (lds > 160 * 1024 && dil > 1)
+        DAT_FAIL(ctx, DAT_ERR_UNSUPPORTED, "conv3d: dilation %d is unsupported for this layer: the %dx%d patch of a %dx%d tile takes %zu bytes of LDS (limit 160 KiB)",
+                 dil, p.PH, p.PW, th, tw, lds);
     DAT_ENFORCE(ctx, lds <= 160 * 1024, "conv3d: LDS patch of %zu bytes exceeds 160 KiB (tile %dx%d, stride %dx%d)", lds,
                 th, tw, p.sh, p.sw);
     auto kern = conv3d_igemm_kernel<DT, BN, BP, WAVES_N, 1, NTAP, ODT, MF>;
     if (NTAP > 0) {   // what the unrolled variant assumes (the dispatcher only picks it for these shapes)
-        DAT_ENFORCE(ctx, p.tab_n == (NTAP == 10 ? 9 : NTAP) && p.tab_new == 1u &&
+        DAT_ENFORCE(ctx, NTAP != 19 || linear, "conv3d: the dilated-strip variant runs linear strips only");
+        DAT_ENFORCE(ctx, p.tab_n == (NTAP == 10 || NTAP == 19 ? 9 : NTAP) && p.tab_new == 1u &&
                              (((size_t)p.PH * p.PW * 8 + 63) >> 6) <= (size_t)4 * patch_pieces_per_wave(NTAP, BP) && (NTAP == 10 || (size_t)p.PH * p.PW * PPITCH < 65536),
                     "conv3d: unrolled-tap variant on an unsupported shape (%d taps, patch %dx%d)", p.tab_n, p.PH, p.PW);
         for (int i = 0; i < p.tab_n; ++i) DAT_ENFORCE(ctx, p.tab_tap[i] == i, "conv3d: unrolled-tap variant needs taps in natural order");
@@ -978,8 +994,9 @@ extern "C" {
 
 int dat_conv3d_out_shape(const dat_conv_desc* d, int* Ho, int* Wo) {
     if (!d || d->stride_h < 1 || d->stride_w < 1) return DAT_ERR_ARG;
-    *Ho = (d->H + 2 * d->pad_h - d->KH) / d->stride_h + 1;
-    *Wo = (d->W + 2 * d->pad_w - d->KW) / d->stride_w + 1;
+    const int dl = dat_conv::conv_dilation(d);      // (0 and 1: not dilated)
+    *Ho = (d->H + 2 * d->pad_h - dl * (d->KH - 1) - 1) / d->stride_h + 1;
+    *Wo = (d->W + 2 * d->pad_w - dl * (d->KW - 1) - 1) / d->stride_w + 1;
     return DAT_OK;
 }
 
@@ -1037,6 +1054,8 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
     DAT_ENFORCE(ctx, d->pad_t * 2 + 1 == d->KT || d->out_tn > 0,
                 "conv3d_fwd: temporal pad %d must be (KT-1)/2 for KT %d unless out_t0/out_tn select the output frames",
                 d->pad_t, d->KT);
+    if (const char* why = conv_dilation_refusal(d)) DAT_FAIL(ctx, DAT_ERR_UNSUPPORTED, "conv3d_fwd: %s (dil %dx%d, stride %dx%d)", why, d->dil_h, d->dil_w, d->stride_h, d->stride_w);
+    const int dil = conv_dilation(d);
     ConvParams p;
     memset(&p, 0, sizeof(p));
     p.x = (const char*)x; p.w = (const char*)w_packed; p.scale = scale; p.bias = bias;
@@ -1079,7 +1098,7 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
             if (cand_bp == 256 && !force_bp && ctx->dbg_ntap && !(ctx->dbg_ntap & 4) && d->KH == 3 && d->KW == 3 && d->stride_h == 2 && d->stride_w == 2) continue;
             if (force_bp && cand_bp != force_bp && !(force_bp == 256 && (small_n || ntaps == 1))) continue;
             const int lg = cand_bp == 256 ? 8 : 7;
-            const TileChoice tc = choose_tile(p.Ho, p.Wo, lg, p.sh, p.sw, p.KH, p.KW);
+            const TileChoice tc = choose_tile(p.Ho, p.Wo, lg, p.sh, p.sw, (p.KH - 1) * dil + 1, (p.KW - 1) * dil + 1);
             long long tiles = cdiv_ll(p.Ho, 1ll << tc.th_log2) * cdiv_ll(p.Wo, 1ll << tc.tw_log2) * p.frames;
             {   // (the dispatcher's rule below: linear tiles when they save >= 10 %)
                 const long long tl = linear_tiles(ctx, d, p, cand_bp);
@@ -1105,7 +1124,7 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
         }
     }
     const bool big = bp == 256;
-    int tag = (small_n ? 64 : 128) * 10000 + bp * 10 + d->dtype;
+    int tag = (small_n ? 64 : 128) * 10000 + bp * 10 + d->dtype + (dil > 1 ? 5 : 0);   // (last digit 5-7: a dilated layer, always this kernel)
     ProfBracket prof(ctx, st);
     int rc;
     // big-tile kernel: one block per CU at a time, so the grid has to fill the chip several times and evenly (FPN P2: 2016 blocks on
@@ -1138,8 +1157,10 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
         // unrolled-tap variants: dense 3x3 (stride 1) and 1x1 (any stride: one tap, one plane); the patch must fit the per-wave
         // piece registers (tile shapes with very long rows fall back to the table-driven loop).  1x1 layers with a large output
         // grid are bandwidth-bound and do better with the leaner table-driven loop (one block more per CU), measured.
-        const TileChoice tc = choose_tile(p.Ho, p.Wo, big ? 8 : 7, p.sh, p.sw, p.KH, p.KW);
-        const long long prow = ((1ll << tc.th_log2) + (p.KH - 1) / p.sh) * ((1ll << tc.tw_log2) + (p.KW - 1) / p.sw);
+        const TileChoice tc = choose_tile(p.Ho, p.Wo, big ? 8 : 7, p.sh, p.sw, (p.KH - 1) * dil + 1, (p.KW - 1) * dil + 1);
+        // (a dilated 3x3 keeps the unrolled variant while its wider patch fits the piece registers -- < 64 KiB, so the packed 16-bit
+        //  addresses hold too; beyond that it takes the table-driven loop)
+        const long long prow = ((1ll << tc.th_log2) + (p.KH - 1) * dil / p.sh) * ((1ll << tc.tw_log2) + (p.KW - 1) * dil / p.sw);
         const bool fits = ((prow * 8 + 63) >> 6) <= 4 * patch_pieces_per_wave(9, big ? 256 : 128);
         const bool pw_small = (long long)p.frames * p.Ho * p.Wo <= 65536;
         // strided 3x3: ONE dense patch of (2*TH+1) x (2*TW+1) cells serves all 9 taps (the table-driven loop stages four stride-parity
@@ -1156,12 +1177,12 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
             const long long t2d = (long long)p.frames * cdiv_ll(p.Ho, 1ll << tc.th_log2) * cdiv_ll(p.Wo, 1ll << tc.tw_log2);
             lin = tlin * 10 <= t2d * 9;
         }
-#define DAT_CONV_LAUNCH(DT_, BN_, WN_, ODT_) (ntapv == 10 ? launch_conv<DT_, BN_, 128, WN_, 10, ODT_>(ctx, st, p, 7, ksplit) : ntapv == 9 ? (big ? launch_conv<DT_, BN_, 256, WN_, 9, ODT_>(ctx, st, p, 8, ksplit, lin) : launch_conv<DT_, BN_, 128, WN_, 9, ODT_>(ctx, st, p, 7, ksplit, lin)) \
+#define DAT_CONV_LAUNCH(DT_, BN_, WN_, ODT_) (lin && dil > 1 ? (big ? launch_conv<DT_, BN_, 256, WN_, 19, ODT_>(ctx, st, p, 8, ksplit, lin, dil) : launch_conv<DT_, BN_, 128, WN_, 19, ODT_>(ctx, st, p, 7, ksplit, lin, dil)) : ntapv == 10 ? launch_conv<DT_, BN_, 128, WN_, 10, ODT_>(ctx, st, p, 7, ksplit) : ntapv == 9 ? (big ? launch_conv<DT_, BN_, 256, WN_, 9, ODT_>(ctx, st, p, 8, ksplit, lin, dil) : launch_conv<DT_, BN_, 128, WN_, 9, ODT_>(ctx, st, p, 7, ksplit, lin, dil)) \
                             : ntapv == 1 ? (big ? launch_conv<DT_, BN_, 256, WN_, 1, ODT_>(ctx, st, p, 8, ksplit) : launch_conv<DT_, BN_, 128, WN_, 1, ODT_>(ctx, st, p, 7, ksplit)) \
-                            : (big ? launch_conv<DT_, BN_, 256, WN_, 0, ODT_>(ctx, st, p, 8, ksplit) : launch_conv<DT_, BN_, 128, WN_, 0, ODT_>(ctx, st, p, 7, ksplit)))
+                            : (big ? launch_conv<DT_, BN_, 256, WN_, 0, ODT_>(ctx, st, p, 8, ksplit, false, dil) : launch_conv<DT_, BN_, 128, WN_, 0, ODT_>(ctx, st, p, 7, ksplit, false, dil)))
         // DAT_CONV_MFMA=1: the bf16 128-channel dense 3x3 variants (2-D tiles, linear strips, split-K) on 16x16x32, like the big-tile kernel
-        if (ctx->dbg_mfma && ntapv == 9 && !x3 && !small_n && d->dtype == DAT_BF16)
-            rc = big ? launch_conv<DAT_BF16, 128, 256, 2, 9, DAT_BF16, 1>(ctx, st, p, 8, ksplit, lin) : launch_conv<DAT_BF16, 128, 128, 2, 9, DAT_BF16, 1>(ctx, st, p, 7, ksplit, lin);
+        if (ctx->dbg_mfma && ntapv == 9 && !x3 && !small_n && d->dtype == DAT_BF16 && !(lin && dil > 1))   // (dilated strips: 32x32x16 only)
+            rc = big ? launch_conv<DAT_BF16, 128, 256, 2, 9, DAT_BF16, 1>(ctx, st, p, 8, ksplit, lin, dil) : launch_conv<DAT_BF16, 128, 128, 2, 9, DAT_BF16, 1>(ctx, st, p, 7, ksplit, lin, dil);
         else if (x3) rc = small_n ? DAT_CONV_LAUNCH(DAT_BF16, 64, 1, DAT_F32) : DAT_CONV_LAUNCH(DAT_BF16, 128, 2, DAT_F32);
         else if (small_n) rc = d->dtype == DAT_BF16 ? DAT_CONV_LAUNCH(DAT_BF16, 64, 1, DAT_BF16) : DAT_CONV_LAUNCH(DAT_F32, 64, 1, DAT_F32);
         else rc = d->dtype == DAT_BF16 ? DAT_CONV_LAUNCH(DAT_BF16, 128, 2, DAT_BF16) : DAT_CONV_LAUNCH(DAT_F32, 128, 2, DAT_F32);

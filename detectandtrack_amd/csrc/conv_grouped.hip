@@ -454,6 +454,7 @@ int grouped_check(dat_ctx* ctx, const dat_conv_desc* d, int groups, const char* 
                         d->pad_t, d->pad_h, d->pad_w);
     DAT_GRP_UNSUPPORTED(ctx, d->stride_h == d->stride_w && (d->stride_h == 1 || d->stride_h == 2), "%s: stride %dx%d (supported: 1, 2)", who,
                         d->stride_h, d->stride_w);
+    DAT_GRP_UNSUPPORTED(ctx, d->dil_h <= 1 && d->dil_w <= 1, "%s: dilation %dx%d (grouped dilated convs are unsupported)", who, d->dil_h, d->dil_w);
     DAT_GRP_UNSUPPORTED(ctx, d->res_mode == 0 || d->res_mode == 1 || (d->res_mode == 3 && max_res_mode >= 3 && d->dtype != DAT_BF16X3),
                         "%s: res_mode %d (supported: 0, 1%s)", who, d->res_mode,
                         max_res_mode >= 3 ? "; 3 = mask for DAT_F32 / DAT_BF16; 4 = sum + mask has no grouped instantiation" : "");

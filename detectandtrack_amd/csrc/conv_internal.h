@@ -137,6 +137,18 @@ inline int cout_pad_of(const dat_conv_desc* d) {
     return (d->Cout + bn - 1) / bn * bn;
 }
 
+// spatial dilation of a descriptor: 0 and 1 both mean "not dilated", and a 1x1 spatial kernel has nothing to dilate.  Every kernel's
+// *_eligible predicate that has spatial taps asks this and declines d > 1; only the generic kernel's host-built patch geometry knows it.
+inline int conv_dilation(const dat_conv_desc* d) { return (d->KH > 1 || d->KW > 1) && d->dil_h > 1 ? d->dil_h : 1; }
+// what every dense entry point that takes a descriptor refuses about the dilation fields (NULL: nothing), for the caller's error text
+inline const char* conv_dilation_refusal(const dat_conv_desc* d) {
+    if (d->KH == 1 && d->KW == 1) return nullptr;
+    if (d->dil_h < 0 || d->dil_w < 0) return "negative dilation";
+    if ((d->dil_h > 1 ? d->dil_h : 1) != (d->dil_w > 1 ? d->dil_w : 1)) return "dil_h != dil_w is unsupported (spatial dilation is equal in H and W)";
+    if (d->dil_h > 1 && (d->stride_h != 1 || d->stride_w != 1)) return "dilation with a spatial stride > 1 is unsupported";
+    return nullptr;
+}
+
 // ---- launch prologue shared by launch_conv and dat_conv3d_grouped_fwd (conv3d_igemm.hip) ----
 struct TileChoice {
     int th_log2, tw_log2;

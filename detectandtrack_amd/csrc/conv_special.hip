@@ -1196,7 +1196,7 @@ namespace dat_conv {
 bool ws64_eligible(const dat_ctx* ctx, const dat_conv_desc* d) {
     return ctx->dbg_ws64 && d->dtype == DAT_BF16 && d->Cin == 64 && d->Cout == 64 && d->KT == 1 && d->KH == 3 && d->KW == 3 &&
            d->stride_h == 1 && d->stride_w == 1 && d->pad_h == 1 && d->pad_w == 1 && d->pad_t == 0 && d->res_mode != 2 &&
-           d->out_tn <= 0 && d->out_cstride % 8 == 0;
+           d->out_tn <= 0 && d->out_cstride % 8 == 0 && conv_dilation(d) == 1;   // (its patch and taps are those of an undilated 3x3)
 }
 
 // CUs a persistent HBM-bound kernel (one block per CU) takes: all of them, or DAT_PERSIST_PCT percent (an experiment: does leaving CUs to the
@@ -1220,7 +1220,7 @@ int ctx_num_cu(dat_ctx* ctx) {
 // big-tile kernel (conv3x3_bt_kernel): what it assumes; the grid must fill the chip about twice (one block per CU at a time)
 bool bt_eligible(const dat_ctx* ctx, const dat_conv_desc* d) {
     return ctx->dbg_bt && d->dtype == DAT_BF16 && d->Cin % 64 == 0 && cout_pad_of(d) % 256 == 0 && d->Cout % 8 == 0 && d->KH == 3 && d->KW == 3 &&
-           d->stride_h == 1 && d->stride_w == 1 && d->pad_h == 1 && d->pad_w == 1 && d->out_cstride % 8 == 0;
+           d->stride_h == 1 && d->stride_w == 1 && d->pad_h == 1 && d->pad_w == 1 && d->out_cstride % 8 == 0 && conv_dilation(d) == 1;
 }
 
 int bt_tile_twl(const ConvParams& p, long long* nblocks) {

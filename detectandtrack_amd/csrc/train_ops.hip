@@ -247,6 +247,7 @@ struct WgradDirectParams {
     int Cout, Cin, g_cs, x_cs;
     int T, H, W, Ho, Wo, stride;
     int KT, KH, KW, pt, ph, pw;
+    int dil;                    // spatial dilation (>= 1): tap (kh, kw) reads input (oy * stride + kh * dil - ph, ox * stride + kw * dil - pw)
     int ntaps, ksplit, n_ci_tiles, n_co_tiles;
     int atomic;                 // add into G with atomics (K split, or a caller-owned accumulator: dat_conv3d_wgrad_acc) instead of storing
     unsigned p_begin, p_end;    // output positions [p_begin, p_end) carry a non-zero gradient (frame window)
@@ -279,7 +280,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad_direct_kernel(const WgradDirectPa
     const int ci_t = bid % p.n_ci_tiles; bid /= p.n_ci_tiles;
     const int co_t = bid % p.n_co_tiles;
     const int split = bid / p.n_co_tiles;
-    const int kw = tap % p.KW, kh = (tap / p.KW) % p.KH, kt = tap / (p.KW * p.KH);
+    const int kw = (tap % p.KW) * p.dil, kh = ((tap / p.KW) % p.KH) * p.dil, kt = tap / (p.KW * p.KH);   // (input offsets of the tap)
     const unsigned nchunks = (p.p_end - p.p_begin + 63u) / 64u;
     const unsigned c_lo = (unsigned)((unsigned long long)nchunks * split / p.ksplit), c_hi = (unsigned)((unsigned long long)nchunks * (split + 1) / p.ksplit);
 
@@ -1222,14 +1223,14 @@ extern "C" {
 static void wgrad_geom(const dat_conv_desc* d, int* Ho, int* Wo, int* Tq, int* Hq, int* Wq, long long* Qtot, long long* Qa,
                        int* ncopies) {
     dat_conv3d_out_shape(d, Ho, Wo);
-    const int s = d->stride_h;
+    const int s = d->stride_h, dl = dat_conv::conv_dilation(d);     // (dl > 1 only at stride 1)
     *Tq = d->T + d->KT - 1;
-    *Hq = *Ho + (d->KH - 1) / s;
-    *Wq = *Wo + (d->KW - 1) / s;
+    *Hq = *Ho + (d->KH - 1) * dl / s;
+    *Wq = *Wo + (d->KW - 1) * dl / s;
     if (*Wq & 1) ++*Wq;
     const int clips = d->frames / d->T;
     *Qtot = (long long)clips * *Tq * *Hq * *Wq;
-    const long long max_off = ((long long)(d->KT - 1) * *Hq + (d->KH - 1) / s) * *Wq + (d->KW - 1) / s;
+    const long long max_off = ((long long)(d->KT - 1) * *Hq + (d->KH - 1) * dl / s) * *Wq + (d->KW - 1) * dl / s;
     const int ck = d->dtype == DAT_BF16 ? 64 : 32;
     long long k = (*Qtot + ck - 1) / ck * ck;
     *Qa = k + (max_off + 63) / 64 * 64 + 64;
@@ -1255,7 +1256,9 @@ static bool wgrad_direct_eligible(const dat_ctx* ctx, const dat_conv_desc* d, in
     // map the same way, as ONE row of Ho columns (column_strip below) -- possible when the layer has no spatial taps, i.e. no bound to check
     // across the relabelled axis; a layer WITH spatial taps on such a map (3 x 3 at stride 2 on a map one or two columns wide) takes the
     // re-pack kernels.  The nine-tap kernel walks 8 x 8 patches and has no such split.
-    const bool nine_tap = d->KH == 3 && d->KW == 3 && d->stride_h == 1 && d->pad_h == 1 && d->pad_w == 1 && (ctx->dbg_wgrad_direct & 2) == 0;
+    // (a dilated 3 x 3 is not a nine-tap layer: that kernel's 10 x 10 patch holds the taps one row / column away)
+    const bool nine_tap = d->KH == 3 && d->KW == 3 && d->stride_h == 1 && d->pad_h == 1 && d->pad_w == 1 && (ctx->dbg_wgrad_direct & 2) == 0 &&
+                          dat_conv::conv_dilation(d) == 1;
     const bool no_spatial_taps = d->KH == 1 && d->KW == 1 && d->pad_h == 0 && d->pad_w == 0;
     if (Wo == 1 && Ho > 1 && !nine_tap && !no_spatial_taps) return false;
     // (the multiply-high is exact while position-in-frame x divisor < 2^32; the relabelled strip divides its positions, < Ho, by Ho)
@@ -1372,6 +1375,8 @@ static int wgrad_impl(dat_ctx* ctx, dat_stream s_, const dat_conv_desc* d, const
     DAT_ENFORCE(ctx, d->frames % d->T == 0 && d->pad_t * 2 + 1 == d->KT, "conv3d_wgrad: needs same-T convs");
     DAT_ENFORCE(ctx, d->KT * d->KH * d->KW <= 32, "conv3d_wgrad: %d taps exceed 32", d->KT * d->KH * d->KW);
     DAT_ENFORCE(ctx, d->Cin % 8 == 0 && g_cstride % 8 == 0, "conv3d_wgrad: channel strides must be multiples of 8");
+    if (const char* why = dat_conv::conv_dilation_refusal(d)) DAT_FAIL(ctx, DAT_ERR_UNSUPPORTED, "conv3d_wgrad: %s (dil %dx%d, stride %dx%d)", why, d->dil_h, d->dil_w, d->stride_h, d->stride_w);
+    const int dl = dat_conv::conv_dilation(d);
     hipStream_t st = (hipStream_t)s_;
     int Ho, Wo, Tq, Hq, Wq, nc;
     long long Qtot, Qa;
@@ -1385,7 +1390,7 @@ static int wgrad_impl(dat_ctx* ctx, dat_stream s_, const dat_conv_desc* d, const
     DAT_ENFORCE(ctx, !acc_mode || wgrad_direct_eligible(ctx, d, g_cstride), "conv3d_wgrad_acc: the layer does not take the direct kernels (ask dat_conv3d_wgrad_acc_supported)");
     if (wgrad_direct_eligible(ctx, d, g_cstride)) {
         float* Gt = (float*)workspace;
-        if (d->KH == 3 && d->KW == 3 && s == 1 && d->pad_h == 1 && d->pad_w == 1 && (ctx->dbg_wgrad_direct & 2) == 0) {
+        if (d->KH == 3 && d->KW == 3 && s == 1 && d->pad_h == 1 && d->pad_w == 1 && (ctx->dbg_wgrad_direct & 2) == 0 && dl == 1) {
             // nine spatial taps from one staged patch (wgrad_dma9_kernel)
             Wgrad9Params q;
             memset(&q, 0, sizeof(q));
@@ -1471,6 +1476,7 @@ static int wgrad_impl(dat_ctx* ctx, dat_stream s_, const dat_conv_desc* d, const
         wp.T = d->T; wp.H = d->H; wp.W = d->W; wp.Ho = Ho; wp.Wo = Wo; wp.stride = s;
         column_strip(&wp.Ho, &wp.Wo, &wp.H, &wp.W, &wp.stride);     // (kT x 1 x 1 on a one-column map, see wgrad_direct_eligible: a one-row strip)
         wp.KT = d->KT; wp.KH = d->KH; wp.KW = d->KW; wp.pt = d->pad_t; wp.ph = d->pad_h; wp.pw = d->pad_w;
+        wp.dil = dl;        // (dilated 3 x 3 layers land here: one block per tap, the tap's input offset scaled)
         wp.ntaps = d->KT * d->KH * d->KW;
         wp.n_co_tiles = (Cout_real + 127) / 128; wp.n_ci_tiles = (Cin_real + 127) / 128;
         wp.how = (unsigned)(Ho * Wo);
@@ -1551,7 +1557,7 @@ static int wgrad_impl(dat_ctx* ctx, dat_stream s_, const dat_conv_desc* d, const
         for (int kh = 0; kh < d->KH; ++kh)
             for (int kw = 0; kw < d->KW; ++kw) {
                 const int tap = (kt * d->KH + kh) * d->KW + kw;
-                long long off = ((long long)kt * Hq + kh / s) * Wq + kw / s;
+                long long off = ((long long)kt * Hq + kh * dl / s) * Wq + kw * dl / s;
                 int copy = 0;
                 if (nc == 2 && (off & 1)) { copy = 1; off -= 1; }
                 wp.tap_off[tap] = off;

@@ -162,12 +162,22 @@ class DetectionModelHelper(object):
         group = int(group)
         assert group >= 1 and dim_in % group == 0 and dim_out % group == 0, \
             'group count %d must divide dim_in %d and dim_out %d' % (group, dim_in, dim_out)
-        if not isinstance(dilations, int):
-            assert all(d == 1 for d in dilations), 'dilated conv unsupported (MODEL.DILATION == 1 in every config)'
-        else:
-            assert dilations == 1
+        # spatial dilation (MODEL.DILATION; ResNet3D.py passes [1, d, d]): equal in H and W, no temporal dilation, never with a stride
+        dil = [1, int(dilations), int(dilations)] if isinstance(dilations, int) else [int(d) for d in dilations]
+        if len(dil) != 3 or min(dil) < 1:
+            raise ValueError('ConvNd %s: dilations %r (expected [1, d, d], d >= 1)' % (blob_out, dilations))
+        if dil[0] != 1:
+            raise ValueError('ConvNd %s: temporal dilation %d is unsupported' % (blob_out, dil[0]))
+        if dil[1] != dil[2]:
+            raise ValueError('ConvNd %s: dilation %dx%d is unsupported (it must be equal in H and W)' % (blob_out, dil[1], dil[2]))
         kernels = [int(k) for k in kernels]
+        dilation = dil[1] if (kernels[1] > 1 or kernels[2] > 1) else 1     # (a 1x1 kernel has nothing to dilate)
         strides = [1, 1, 1] if strides is None else [int(s) for s in strides]
+        if dilation > 1 and (strides[1] != 1 or strides[2] != 1):
+            raise ValueError('ConvNd %s: dilation %d with stride %dx%d is unsupported (add_bottleneck_block forces stride 1 under a '
+                             'dilation)' % (blob_out, dilation, strides[1], strides[2]))
+        if dilation > 1 and group > 1:
+            raise ValueError('ConvNd %s: grouped (ResNeXt) dilated convs are unsupported (dilation %d, group %d)' % (blob_out, dilation, group))
         pads = [0] * 6 if pads is None else [int(p) for p in pads]
         assert pads[:3] == pads[3:], 'symmetric pads expected'
         assert strides[0] == 1, 'temporal stride unsupported (VIDEO.TIME_STRIDE_ON, FPN3D.py:199-203)'
@@ -178,6 +188,8 @@ class DetectionModelHelper(object):
         if not no_bias:
             b = bias or self._param(blob_out + '_b', [dim_out], bias_init or ('ConstantFill', {'value': 0.}), 'b')
         grouped = {'group': group} if group > 1 else {}      # (recorded for grouped convs only: an ungrouped op is what it always was)
+        if dilation > 1:
+            grouped['dilation'] = dilation                   # (likewise: only a dilated op carries the attribute)
         return self.net.add(Op('Conv', [blob_in], [blob_out], w=w, b=b, scale=None, shift=None, dim_in=dim_in,
                                dim_out=dim_out, kernels=kernels, strides=strides[1:], pads=pads[:3], relu=False,
                                residual=None, res_mode=0, **grouped))

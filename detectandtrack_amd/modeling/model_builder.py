@@ -98,6 +98,10 @@ def build_generic_fast_rcnn_model(model, add_conv_body_func, add_roi_frcn_head_f
     """:179-306 (single replica; the reference loops this over NUM_GPUS name scopes for training)."""
     if model.train and not cfg.MODEL.FASTER_RCNN:
         raise NotImplementedError('training graph: end-to-end Faster R-CNN only (pre-computed proposal training needs the dataset layer)')
+    if cfg.MODEL.DILATION != 1 and cfg.FPN.FPN_ON:
+        raise ValueError('MODEL.DILATION %d with FPN.FPN_ON: the FPN level scales (1/32 .. 1/4) and its 2x top-down steps assume res5 at '
+                         '1/32 of the input; a dilated res5 stays at 1/%d. Use a C5 body without FPN' %
+                         (cfg.MODEL.DILATION, 32 // cfg.MODEL.DILATION))
     blob_conv, dim_conv, spatial_scale_conv = add_conv_body_func(model)
     if cfg.MODEL.VIDEO_ON:
         blob_conv = time_pool_blobs(blob_conv, model, cfg.VIDEO.BODY_HEAD_LINK)

@@ -165,8 +165,10 @@ class ConvLayer(object):
     """
 
     def __init__(self, w, scale=None, bias=None, stride=(1, 1), pads=(0, 0, 0), relu=False, dtype=BF16,
-                 cin_stride=None, dgrad_of=None, x3=False, groups=1):
-        """dgrad_of = (w_fwd, scale_fwd): this layer is the DATA-GRADIENT conv of a forward conv with master weights w_fwd
+                 cin_stride=None, dgrad_of=None, x3=False, groups=1, dilation=1):
+        """dilation = d: spatial dilation (MODEL.DILATION), equal in H and W, stride 1 only; tap (kh, kw) reads the input kh * d rows
+        and kw * d columns from the window's corner.  Grouped dilated convs are refused.
+        dgrad_of = (w_fwd, scale_fwd): this layer is the DATA-GRADIENT conv of a forward conv with master weights w_fwd
         [CoutF, CinF, KT, KH, KW]; `w` is then ignored and the packed weights come straight from w_fwd (channels swapped, kernel
         flipped, AffineChannelNd scale folded in: dat_conv3d_pack_weights_dgrad).
         groups > 1: a grouped conv (ResNeXt `branch2b`) on the dat_conv3d_grouped_* entry points, only the shapes that kernel has
@@ -174,6 +176,13 @@ class ConvLayer(object):
         grouped conv, packed by dat_conv3d_grouped_pack_weights_dgrad from w_fwd [C, C / groups, KT, KH, KW]."""
         self.groups = int(groups)
         assert self.groups >= 1
+        self.dilation = int(dilation)
+        if self.dilation < 1:
+            raise ValueError('ConvLayer: dilation %d < 1' % self.dilation)
+        if self.dilation > 1 and tuple(stride) != (1, 1):
+            raise ValueError('ConvLayer: dilation %d with stride %s is unsupported (the reference never combines them)' % (self.dilation, tuple(stride)))
+        if self.dilation > 1 and self.groups > 1:
+            raise ValueError('ConvLayer: grouped (ResNeXt) dilated convs are unsupported (dilation %d, %d groups)' % (self.dilation, self.groups))
         if dgrad_of is not None:
             w_fwd = dgrad_of[0].contiguous().float()
             self.w_src, self.dgrad_scale = w_fwd, (None if dgrad_of[1] is None else dgrad_of[1].contiguous().float())
@@ -269,11 +278,14 @@ class ConvLayer(object):
         d.res_mode = res_mode
         d.out_t0, d.out_tn = out_t if out_t is not None else (0, 0)
         d.in_t0, d.in_tn = in_t if in_t is not None else (0, 0)
+        if self.dilation > 1:
+            d.dil_h = d.dil_w = self.dilation
         return d
 
     def out_hw(self, H, W):
-        return ((H + 2 * self.pads[1] - self.kh) // self.stride[0] + 1,
-                (W + 2 * self.pads[2] - self.kw) // self.stride[1] + 1)
+        dl = self.dilation if (self.kh > 1 or self.kw > 1) else 1
+        return ((H + 2 * self.pads[1] - dl * (self.kh - 1) - 1) // self.stride[0] + 1,
+                (W + 2 * self.pads[2] - dl * (self.kw - 1) - 1) // self.stride[1] + 1)
 
     def flops(self, frames, H, W):
         ho, wo = self.out_hw(H, W)
@@ -366,8 +378,10 @@ class ConvGrad(object):
       weight(x, g) -> G = dL/d(z) / scale-free weight gradient;  dL/dw = scale*G,  dL/dscale[c] = <w[c], G[c]>.
     """
 
-    def __init__(self, w, scale, stride, pads, dtype, x_cstride, g_cstride, groups=1):
-        """groups > 1: a grouped conv (`w` fp32 [C, C / groups, KT, KH, KW]) on dat_conv3d_grouped_wgrad* and the grouped data-gradient
+    def __init__(self, w, scale, stride, pads, dtype, x_cstride, g_cstride, groups=1, dilation=1):
+        """dilation = d > 1: a dilated forward conv (stride 1, dense): its data gradient is the conv with flipped weights, the same
+        dilation and pads d * (K - 1) - p; tap (kh, kw) of the weight gradient pairs g[q] with x[q + (kh * d - p, kw * d - p)].
+        groups > 1: a grouped conv (`w` fp32 [C, C / groups, KT, KH, KW]) on dat_conv3d_grouped_wgrad* and the grouped data-gradient
         layer; `cin` is the full C."""
         self.w = w.contiguous().float()
         self.cout, self.cin, self.kt, self.kh, self.kw = [int(v) for v in self.w.shape]
@@ -377,6 +391,13 @@ class ConvGrad(object):
         self.stride, self.pads, self.dtype = tuple(stride), tuple(pads), dtype
         self.x_cstride, self.g_cstride = x_cstride, g_cstride
         assert self.stride[0] == self.stride[1] and self.stride[0] in (1, 2)
+        self.dilation = int(dilation)
+        if self.dilation < 1:
+            raise ValueError('ConvGrad: dilation %d < 1' % self.dilation)
+        if self.dilation > 1 and self.stride != (1, 1):
+            raise ValueError('ConvGrad: dilation %d with stride %s is unsupported' % (self.dilation, self.stride))
+        if self.dilation > 1 and self.groups > 1:
+            raise ValueError('ConvGrad: grouped (ResNeXt) dilated convs are unsupported (dilation %d, %d groups)' % (self.dilation, self.groups))
         self._data_layer = None
 
     def _fwd_desc(self, frames, T, H, W):
@@ -389,6 +410,8 @@ class ConvGrad(object):
         d.stride_h, d.stride_w = self.stride
         d.pad_t, d.pad_h, d.pad_w = self.pads
         d.relu, d.res_mode, d.out_t0, d.out_tn, d.in_t0, d.in_tn = 0, 0, 0, 0, 0, 0
+        if self.dilation > 1:
+            d.dil_h = d.dil_w = self.dilation
         return d
 
     def weight(self, x, g, T, want_dscale=False, g_frames=None, out=None):
@@ -465,11 +488,12 @@ class ConvGrad(object):
         with the other contribution and the mask in one epilogue (res_mode 4)."""
         if self._data_layer is None:
             # flipped / transposed / scale-folded weights are packed straight from the forward master (no ATen flip, mul, copy)
-            pads = (self.kt - 1 - self.pads[0], self.kh - 1 - self.pads[1], self.kw - 1 - self.pads[2])
+            dl = self.dilation
+            pads = (self.kt - 1 - self.pads[0], dl * (self.kh - 1) - self.pads[1], dl * (self.kw - 1) - self.pads[2])
             self._data_layer = ConvLayer(None, None, None, stride=(1, 1), pads=pads, relu=False, dtype=self.dtype,
-                                         cin_stride=self.g_cstride, dgrad_of=(self.w, self.scale), groups=self.groups)
+                                         cin_stride=self.g_cstride, dgrad_of=(self.w, self.scale), groups=self.groups, dilation=dl)
         frames, Ho, Wo, cs = g.shape
-        Hz, Wz = H - self.kh + 1 + 2 * self.pads[1], W - self.kw + 1 + 2 * self.pads[2]
+        Hz, Wz = H - self.dilation * (self.kh - 1) + 2 * self.pads[1], W - self.dilation * (self.kw - 1) + 2 * self.pads[2]
         if self.stride[0] == 2 or (Hz, Wz) != (Ho, Wo):
             gz = torch.empty((frames, Hz, Wz, cs), dtype=g.dtype, device=g.device)
             if self.stride[0] == 2:

@@ -389,7 +389,8 @@ class TrainExecutor(Executor):
             w5 = self._master(a['w'])
             w5 = w5 if w5.dim() == 5 else w5.unsqueeze(2)
             scale = ws.affine_pair(a)[0]        # (a test-mode SpatialBN: the folded scale)
-            return ops.ConvGrad(w5, scale, a['strides'], a['pads'], y.dt, xin.t.shape[3], g.shape[3], groups=a.get('group', 1))
+            return ops.ConvGrad(w5, scale, a['strides'], a['pads'], y.dt, xin.t.shape[3], g.shape[3], groups=a.get('group', 1),
+                                dilation=a.get('dilation', 1))
         cg = self._conv_grad(i, build)
         if self._trainable(a['w']):
             gfr = (lo - ilo, n) if xin.N == 1 else None

@@ -494,7 +494,7 @@ class Executor(object):
             scale, shift = ws.affine_pair(a)
             bias = shift if a['shift'] else (ws.dev_param(a['b']) if a['b'] else None)
             return ops.ConvLayer(w, scale, bias, stride=a['strides'], pads=a['pads'], relu=a['relu'], dtype=dt,
-                                 cin_stride=xin.t.shape[3], x3=_x3(self.ws), groups=a.get('group', 1))
+                                 cin_stride=xin.t.shape[3], x3=_x3(self.ws), groups=a.get('group', 1), dilation=a.get('dilation', 1))
         layer = self._layer(i, build)
         res = ws.blobs[a['residual']].t if a['residual'] else None
         if xin.tsel is not None:    # lazy SliceKeyFrame: a kT = 1 conv computes output frame k of every clip from input frame k

@@ -59,7 +59,7 @@ int dat_fill_zero(dat_ctx* ctx, dat_stream s, void* ptr, size_t bytes);
 
 /* Per-launch HIP-event timing of the conv kernel (used by bench.py's roofline leg).
  * enable: start recording (capacity launches); read: sync the events and return
- * n records {tag, flops, milliseconds}; tag = BN*10000 + BP*10 + dtype. */
+ * n records {tag, flops, milliseconds}; tag = BN*10000 + BP*10 + dtype (+ 5 on a dilated layer). */
 int dat_prof_enable(dat_ctx* ctx, int capacity);
 int dat_prof_read(dat_ctx* ctx, int max_records, int* tags, double* flops, float* ms);
 /* Average shader clock (MHz) the conv kernel ran at since dat_prof_enable: every block adds its s_memtime (shader
@@ -108,6 +108,10 @@ typedef struct {
                                 indexed like the output */
     int in_t0, in_tn;        /* in_tn > 0: input frames outside [in_t0, in_t0+in_tn) of every clip are known to be ZERO (a key-frame
                                 gradient embedded in its temporal window): the temporal taps that would read them are skipped */
+    int dil_h, dil_w;        /* spatial dilation d (MODEL.DILATION): tap (kh, kw) reads x[oh + kh*d - pad_h, ow + kw*d - pad_w]; 0 and 1 both mean
+                                "not dilated" (zero-initialised descriptors keep their meaning).  d > 1 needs dil_h == dil_w, spatial stride 1
+                                and the dense entry points (the grouped ones refuse it); there is no temporal dilation.  A 1x1 spatial kernel
+                                ignores the fields */
 } dat_conv_desc;
 
 int dat_conv3d_out_shape(const dat_conv_desc* d, int* Ho, int* Wo);
