@@ -7,8 +7,11 @@ modulo MAX_TRACK_IDS (:339-348).  Before that: keep the centre frame of each tub
 / tiny boxes (:731-748).  Detections file: `{'all_boxes': [[], per-image n x (4T+1)], 'all_keyps': [[], per-image
 list of 4 x 17T], ...}`; output adds `all_tracks` (:706).
 
-Not mirrored (unused by the shipped configs / missing upstream): cnn-cosdist and pose-pck costs (weights 0.0),
-LSTM tracker (module absent in the reference), optical-flow smoothing (needs OpenCV), debug upper bounds.
+The other two costs of TRACKING.DISTANCE_METRICS (weight 0.0 in every shipped config, so nothing of them runs by default): `pose-pck`
+(:114-129) on the host, `cnn-cosdist` (:132-155) on the device through core/track_features.py.
+
+Not mirrored (missing upstream / unused): LSTM tracker (module absent in the reference), optical-flow smoothing (needs OpenCV), debug
+upper bounds.
 """
 import logging
 import os.path as osp
@@ -105,8 +108,19 @@ def _compute_pairwise_iou(a, b):
     return box_utils.bbox_overlaps(a, b)
 
 
-def _compute_distance_matrix(prev_boxes, cur_boxes, cost_types, cost_weights):
-    """Weighted sum of the enabled pairwise costs (:158-181)."""
+def _plain_boxes(boxes, kind):
+    """The appearance and pose costs read a detection as ONE box (reference :143 indexes box[0..3]): for an uncentred tube that would be
+    the first frame's box on the centre frame's image."""
+    if len(boxes) and boxes.shape[-1] > 5:
+        raise ValueError('cost type {} needs one box per detection, got rows of {} columns (tubes): set '
+                         'TRACKING.KEEP_CENTER_DETS_ONLY'.format(kind, boxes.shape[-1]))
+
+
+def _compute_distance_matrix(prev_boxes, cur_boxes, cost_types, cost_weights, prev_poses=None, cur_poses=None, prev_entry=None,
+                             cur_entry=None, features=None):
+    """Weighted sum of the enabled pairwise costs, in `cost_types` order, float64 (:158-181).  A term of weight 0 is skipped without
+    touching its inputs.  `features`: the appearance extractor (core/track_features.TrackFeatureExtractor), or a callable that makes it
+    on first use; `*_entry`: the frames' roidb entries (image paths for 'cnn-cosdist', the dataset's keypoint names for 'pose-pck')."""
     assert len(cost_weights) == len(cost_types)
     costs = []
     for kind, wt in zip(cost_types, cost_weights):
@@ -114,8 +128,23 @@ def _compute_distance_matrix(prev_boxes, cur_boxes, cost_types, cost_weights):
             continue
         if kind == 'bbox-overlap':
             costs.append((1 - _compute_pairwise_iou(prev_boxes, cur_boxes)) * wt)
+        elif kind == 'cnn-cosdist':
+            _plain_boxes(prev_boxes, kind)
+            _plain_boxes(cur_boxes, kind)
+            if features is None:
+                raise ValueError('cost type cnn-cosdist needs the appearance extractor (`features`)')
+            if not hasattr(features, 'cost'):
+                features = features()
+            C = features.cost(_image_path(prev_entry), prev_boxes, _image_path(cur_entry), cur_boxes)
+            costs.append(np.asarray(C, dtype=np.float64) * wt)
+        elif kind == 'pose-pck':
+            _plain_boxes(prev_boxes, kind)
+            _plain_boxes(cur_boxes, kind)
+            import detectandtrack_amd.utils.keypoints as kps_utils
+            names = cur_entry['dataset'].person_cat_info['keypoints']
+            costs.append(kps_utils.pck_distance_matrix(prev_poses, cur_poses, names) * wt)
         else:
-            raise NotImplementedError('cost type {} (weight 0.0 in every shipped config)'.format(kind))
+            raise NotImplementedError('Unknown cost type {}'.format(kind))
     return np.sum(np.stack(costs, axis=0), axis=0)
 
 
@@ -133,11 +162,13 @@ def bipartite_matching_greedy(C):
     return prev_ids, cur_ids
 
 
-def _compute_matches(prev_boxes, cur_boxes, cost_types, cost_weights, algo, C=None):
+def _compute_matches(prev_boxes, cur_boxes, cost_types, cost_weights, algo, C=None, prev_poses=None, cur_poses=None, prev_entry=None,
+                     cur_entry=None, features=None):
     """For every current box the index of the previous-frame box it continues, or -1 (:209-246)."""
     if C is None:
         matches = -np.ones((cur_boxes.shape[0],), dtype=np.int32)
-        C = _compute_distance_matrix(prev_boxes, cur_boxes, cost_types, cost_weights)
+        C = _compute_distance_matrix(prev_boxes, cur_boxes, cost_types, cost_weights, prev_poses=prev_poses, cur_poses=cur_poses,
+                                     prev_entry=prev_entry, cur_entry=cur_entry, features=features)
     else:
         matches = -np.ones((C.shape[1],), dtype=np.int32)
     if algo == 'hungarian':
@@ -151,19 +182,39 @@ def _compute_matches(prev_boxes, cur_boxes, cost_types, cost_weights, algo, C=No
     return matches
 
 
-def _compute_tracks_video(video_json_data, dets):
+def _appearance_features():
+    """A callable that makes the appearance extractor on first use and hands out the same one afterwards (one per
+    compute_matches_tracks; never made while the cnn-cosdist weight is 0)."""
+    made = []
+
+    def get():
+        if not made:
+            if not cfg.HIP.TRACK_CNN_WEIGHTS:
+                raise ValueError('TRACKING.DISTANCE_METRIC_WTS gives cnn-cosdist a non-zero weight: set HIP.TRACK_CNN_WEIGHTS to the '
+                                 'ResNet-18 weights (a torchvision resnet18 state_dict)')
+            from detectandtrack_amd.core.track_features import TrackFeatureExtractor
+            made.append(TrackFeatureExtractor())
+        return made[0]
+    return get
+
+
+def _compute_tracks_video(video_json_data, dets, features=None):
     """Track ids for each frame of one video (:272-350)."""
     video_tracks = []
     next_id = FIRST_TRACK_ID
+    poses = lambda i: _get_poses(dets, i) if 'all_keyps' in dets else None      # (read by the pose-pck cost only)
     for frame_id in range(len(video_json_data)):
         _, det_id = video_json_data[frame_id]
         cur_boxes = _get_boxes(dets, det_id)
         if frame_id == 0:
             matches = -np.ones((cur_boxes.shape[0],))
         else:
-            prev_boxes = _get_boxes(dets, video_json_data[frame_id - 1][1])
+            prev_entry, prev_id = video_json_data[frame_id - 1]
+            prev_boxes = _get_boxes(dets, prev_id)
             matches = _compute_matches(prev_boxes, cur_boxes, cfg.TRACKING.DISTANCE_METRICS,
-                                       cfg.TRACKING.DISTANCE_METRIC_WTS, cfg.TRACKING.BIPARTITE_MATCHING_ALGO)
+                                       cfg.TRACKING.DISTANCE_METRIC_WTS, cfg.TRACKING.BIPARTITE_MATCHING_ALGO,
+                                       prev_poses=poses(prev_id), cur_poses=poses(det_id),
+                                       prev_entry=prev_entry, cur_entry=video_json_data[frame_id][0], features=features)
         prev_tracks = video_tracks[frame_id - 1] if frame_id > 0 else None
         frame_tracks = []
         for m in matches:
@@ -199,8 +250,9 @@ def compute_matches_tracks(json_data, dets, lstm_model=None):
     all_tracks = [[]] * len(json_data)
     videos = split_into_videos(json_data)
     assert len(json_data) == sum(len(v) for v in videos)
+    features = _appearance_features()
     for video in videos:
-        tracks = _compute_tracks_video(video, dets)
+        tracks = _compute_tracks_video(video, dets, features)
         for i, (_, det_id) in enumerate(video):
             all_tracks[det_id] = tracks[i]
     dets['all_tracks'] = [[], all_tracks]

@@ -192,6 +192,9 @@ _PROTOS = {
     'dat_scatter_words': (_i, [_p, _p, _p, C.c_longlong, _p, _p, _i]),
     'dat_sample_rois': (_i, [_p, _p, C.POINTER(RoiSampleDesc), _p, _p, _i, _p, _p, _p, _i] + [_p] * 10),
     'dat_softmax_ce_rows': (_i, [_p, _p, _i, _p, _i, _p, _p, _i, _i, _f, _i, _p, _i, _p, _p]),
+    'dat_crop_resize_patches': (_i, [_p, _p, _p, _i, _i, C.POINTER(_i), _i, _i, C.POINTER(_d), C.POINTER(_d), _p]),
+    'dat_cosine_cost_workspace_bytes': (C.c_size_t, [_i, _i, _ll]),
+    'dat_cosine_cost': (_i, [_p, _p, _i, _p, _i, _p, _i, _ll, _ll, _p, _p, C.c_size_t]),
 }
 EXPORTS = sorted(_PROTOS)
 for _name, (_res, _args) in _PROTOS.items():

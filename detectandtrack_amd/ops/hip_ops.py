@@ -1339,6 +1339,39 @@ def preprocess_frames(frames, T, scale, pixel_means, pad_stride=0, out=None):
     return out, (oh, ow)
 
 
+def crop_resize_patches(frame, ranges, out_size, mean, std, out=None):
+    """frame: CUDA uint8 [h, w, 3] (BGR); ranges: HOST int32 [n, 4] = x0, x1, y0, y1 (utils.image.crop_ranges) -> the `data` blob fp32
+    [n, 3, 1, out, out] of the tracker's appearance trunk (dat_crop_resize_patches: 8-bit bilinear resize, RGB planes, (v / 255 - mean) /
+    std), bit-identical to utils.image.crop_resize_patches."""
+    assert frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    ranges = np.ascontiguousarray(np.asarray(ranges, dtype=np.int32).reshape(-1, 4))
+    n, size = int(ranges.shape[0]), int(out_size)
+    if out is None:
+        out = torch.empty((n, 3, 1, max(size, 0), max(size, 0)), dtype=torch.float32, device=frame.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * 3 * max(size, 0) ** 2
+    m3 = (C.c_double * 3)(*[float(v) for v in mean])
+    s3 = (C.c_double * 3)(*[float(v) for v in std])
+    ctx().call('dat_crop_resize_patches', _stream(), _ptr(frame), int(frame.shape[0]), int(frame.shape[1]),
+               ranges.ctypes.data_as(C.POINTER(C.c_int)), n, size, m3, s3, _ptr(out))
+    return out
+
+
+def cosine_cost(fa, fb, D, dtype, out=None):
+    """fa [n, ld], fb [m, ld] CUDA tensors of `dtype` (F32 | BF16 = the build's 16-bit format) -> fp32 CUDA [n, m] cosine distances over
+    the first D elements of every row (dat_cosine_cost; bit-reproducible, a zero row is at distance 1)."""
+    assert fa.dim() == 2 and fb.dim() == 2 and fa.is_contiguous() and fb.is_contiguous() and fa.shape[1] == fb.shape[1]
+    assert fa.dtype == fb.dtype == tdtype(dtype), (fa.dtype, fb.dtype, dtype)
+    n, m, ld = int(fa.shape[0]), int(fb.shape[0]), int(fa.shape[1])
+    if out is None:
+        out = torch.empty((n, m), dtype=torch.float32, device=fa.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * m
+    nbytes = int(L.lib().dat_cosine_cost_workspace_bytes(n, m, C.c_longlong(int(D))))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=fa.device)
+    ctx().call('dat_cosine_cost', _stream(), dtype, _ptr(fa), n, _ptr(fb), m, C.c_longlong(int(D)), C.c_longlong(ld), _ptr(out), _ptr(ws),
+               C.c_size_t(nbytes))
+    return out
+
+
 def heatmaps_to_keypoints(maps, boxes, T, K, min_size=0):
     """maps fp32 CUDA [R, T*K, M, M], boxes fp32 CUDA [R, 4T] -> fp32 CUDA [R, 4, T*K] rows (x, y, logit, prob)."""
     R, TK, M, M2 = maps.shape

@@ -54,3 +54,38 @@ def heatmaps_to_keypoints(maps, rois):
             xy[i, 2, k] = roi_map[k, y_int, x_int]
             xy[i, 3, k] = probs[k, y_int, x_int]
     return xy
+
+
+# ---- pose distance of the tracker, TRACKING.DISTANCE_METRICS 'pose-pck' (reference :266-291) ------------------------------------
+def compute_head_size(kps, kpt_names):
+    """|head_top - head_bottom| + 1 of a 3 x K / 4 x K pose (:266-274; the + 1 keeps a degenerate head from dividing by zero)."""
+    kps = np.asarray(kps, dtype=np.float64)
+    top = kps[:2, kpt_names.index('head_top')]
+    bottom = kps[:2, kpt_names.index('head_bottom')]
+    return np.linalg.norm(top - bottom) + 1
+
+
+def pck_distance(kps_a, kps_b, kpt_names, dist_thresh=0.5):
+    """1 - PCK of two poses (:277-291): a keypoint matches when its distance, divided by the head size of `kps_a`, is strictly below
+    `dist_thresh`; every keypoint counts, labelled or not.  float64."""
+    a, b = np.asarray(kps_a, dtype=np.float64), np.asarray(kps_b, dtype=np.float64)
+    normed = np.linalg.norm(a[:2] - b[:2], axis=0) / compute_head_size(a, kpt_names)
+    match = normed < dist_thresh
+    return 1.0 - np.sum(match) / match.size
+
+
+def pck_distance_matrix(poses_a, poses_b, kpt_names, dist_thresh=0.5):
+    """C[i, j] = pck_distance(poses_a[i], poses_b[j]) for two lists of poses, vectorised (tracking_engine.py:114-129): the head size is
+    that of the ROW pose (the previous frame's).  float64 [len(a), len(b)]; zeros((n, m)) when either list is empty."""
+    n, m = len(poses_a), len(poses_b)
+    if n == 0 or m == 0:
+        return np.zeros((n, m))
+    a = np.stack([np.asarray(p, dtype=np.float64)[:2] for p in poses_a])          # (n, 2, K)
+    b = np.stack([np.asarray(p, dtype=np.float64)[:2] for p in poses_b])          # (m, 2, K)
+    d = a[:, None] - b[None]                                                      # (n, m, 2, K)
+    # np.linalg.norm over an axis is sqrt(sum(|x|^2)): the same two squares, one sum and one root per keypoint as the scalar function
+    dist = np.sqrt(np.sum(d * d, axis=2))
+    head = a[:, :, kpt_names.index('head_top')] - a[:, :, kpt_names.index('head_bottom')]
+    head = np.sqrt(np.sum(head * head, axis=1)) + 1
+    match = dist / head[:, None, None] < dist_thresh
+    return 1.0 - np.sum(match, axis=2) / float(match.shape[2])

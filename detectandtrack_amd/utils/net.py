@@ -226,3 +226,73 @@ def _plain(d):
     if isinstance(d, (np.floating, np.integer)):
         return d.item()
     return d
+
+
+# ---- torchvision ResNet-18 -> body blobs (the tracker's appearance trunk, core/track_features.py) -----------------------------------
+_R18_BLOCKS = 2
+_BN_FIELDS = ('weight', 'bias', 'running_mean', 'running_var')
+
+
+def _resnet18_layout(stages):
+    """[(conv key, bn prefix, blob prefix of the conv, blob prefix of its affine)] of torchvision's resnet18 through `layer<stages>`."""
+    out = [('conv1', 'bn1', 'conv1', 'res_conv1_bn')]
+    for L in range(1, stages + 1):
+        for B in range(_R18_BLOCKS):
+            tv, blob = 'layer%d.%d' % (L, B), 'res%d_%d' % (L + 1, B)
+            out.append((tv + '.conv1', tv + '.bn1', blob + '_branch2a', blob + '_branch2a_bn'))
+            out.append((tv + '.conv2', tv + '.bn2', blob + '_branch2b', blob + '_branch2b_bn'))
+            if L > 1 and B == 0:
+                out.append((tv + '.downsample.0', tv + '.downsample.1', blob + '_branch1', blob + '_branch1_bn'))
+    return out
+
+
+def resnet18_state_to_blobs(state, stages=4, eps=1e-5):
+    """A torchvision `resnet18` state_dict (name -> tensor / ndarray) -> the parameters of `ResNet3D.add_ResNet18_conv4_body` (stages 3)
+    or `..._conv5_body` (stages 4): `conv1` -> `conv1_w`, `layerL.B.conv1 / conv2 / downsample.0` -> `res{L+1}_{B}_branch2a / branch2b /
+    branch1` (+ `_w`, with a unit time axis), and every BatchNorm folded in float64 into the AffineChannel pair behind its conv:
+    s = gamma / sqrt(var + eps), b = beta - mean * s.  Tensors of a full resnet18 that the trunk does not use (later layers, `fc`,
+    `num_batches_tracked`) are accepted and dropped; a missing or an unknown tensor is a KeyError that lists the names."""
+    assert stages in (1, 2, 3, 4), stages
+    arr = {}
+    for k, v in state.items():
+        arr[str(k)] = v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)
+    known = {'fc.weight', 'fc.bias'}
+    for conv, bn, _, _ in _resnet18_layout(4):
+        known.add(conv + '.weight')
+        known.update(bn + '.' + f for f in _BN_FIELDS + ('num_batches_tracked',))
+    unknown = sorted(k for k in arr if k not in known)
+    if unknown:
+        raise KeyError('not tensors of a torchvision resnet18: %s' % ', '.join(unknown))
+    need = []
+    for conv, bn, _, _ in _resnet18_layout(stages):
+        need += [conv + '.weight'] + [bn + '.' + f for f in _BN_FIELDS]
+    missing = [k for k in need if k not in arr]
+    if missing:
+        raise KeyError('resnet18 state_dict lacks: %s' % ', '.join(missing))
+    blobs = {}
+    for conv, bn, wname, aname in _resnet18_layout(stages):
+        w = np.asarray(arr[conv + '.weight'], dtype=np.float32)
+        assert w.ndim == 4, (conv, w.shape)
+        blobs[wname + '_w'] = np.ascontiguousarray(w[:, :, None])
+        gamma, beta, mean, var = (np.asarray(arr[bn + '.' + f], dtype=np.float64) for f in _BN_FIELDS)
+        s = gamma / np.sqrt(var + eps)
+        blobs[aname + '_s'] = s.astype(np.float32)
+        blobs[aname + '_b'] = (beta - mean * s).astype(np.float32)
+    return blobs
+
+
+def load_resnet18_state(path):
+    """A `torch.save`d state_dict (a zip archive; loaded with weights_only=True) or a pickle of name -> ndarray."""
+    import zipfile
+    if zipfile.is_zipfile(path):
+        import torch
+        return dict(torch.load(path, map_location='cpu', weights_only=True))
+    with open(path, 'rb') as f:
+        try:
+            state = pickle.load(f)
+        except UnicodeDecodeError:
+            f.seek(0)
+            state = pickle.load(f, encoding='latin1')
+    if not isinstance(state, dict):
+        raise ValueError('%s: expected a pickle of name -> ndarray, got %s' % (path, type(state).__name__))
+    return state

@@ -704,6 +704,24 @@ int dat_sample_rois(dat_ctx* ctx, dat_stream s, const dat_roi_sample_desc* d, co
                     const float* gt_boxes, const int* gt_classes, const int* gt_kps, int G, float* rois, int* labels, float* targets,
                     float* w_in, float* w_out, float* kp_rois, int* kp_loc, float* kp_w, int* counts, int* picked);
 
+/* ---- tracker appearance cost, TRACKING.DISTANCE_METRICS 'cnn-cosdist'  ------------------------------------
+ * Every box of one frame cut out of the uploaded uint8 BGR frame [h][w][3], resized to out x out with the 8-bit bilinear rule of
+ * utils/image.resize_bilinear_u8, turned RGB / CHW and normalised (v / 255 - mean[c]) / std[c] in double, rounded once to fp32:
+ * data fp32 [n][3][1][out][out], every element written, bit-identical to the host restatement.  `ranges` is a HOST array int32 [n][4]
+ * = x0, x1, y0, y1, the slices `I[y0:y1, x0:x1]` already resolved against the frame (slice.indices); x1 <= x0 or y1 <= y0 is an empty
+ * crop (an all-zero image, normalised like any other).  mean / std: 3 host doubles in R, G, B order.  out < 1, n < 0 or a range
+ * outside the frame is DAT_ERR_ARG and launches nothing; n == 0 is a no-op.  One launch per 128 boxes. */
+int dat_crop_resize_patches(dat_ctx* ctx, dat_stream s, const unsigned char* frame, int h, int w, const int* ranges, int n, int out,
+                            const double* mean, const double* stdv, float* data);
+/* cost[i][j] = 1 - fa_i . fb_j / sqrt(|fa_i|^2 |fb_j|^2), fp32 [n][m], for fa [n][ld] and fb [m][ld] of `dtype` (DAT_F32 | DAT_BF16 =
+ * the 16-bit format of the build), the first D <= ld elements of every row (the rest is never read).  fp32 accumulation over chunks
+ * of the feature axis whose partial sums are added in a fixed order: no float atomics, the same bits run after run.  A row of
+ * squared norm zero is at distance exactly 1 from everything.  n, m <= 1024 (more: DAT_ERR_ARG); n == 0 or m == 0 is a no-op.
+ * ws: caller-owned scratch of dat_cosine_cost_workspace_bytes(n, m, D) bytes (0: bad shape). */
+size_t dat_cosine_cost_workspace_bytes(int n, int m, long long D);
+int dat_cosine_cost(dat_ctx* ctx, dat_stream s, int dtype, const void* fa, int n, const void* fb, int m, long long D, long long ld,
+                    float* cost, void* ws, size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif
