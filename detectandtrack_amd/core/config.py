@@ -300,13 +300,18 @@ def _build_defaults():
     # TRACK_CNN_WEIGHTS: the ImageNet ResNet-18 of the tracker's appearance cost (TRACKING.DISTANCE_METRICS 'cnn-cosdist' with a non-zero weight,
     # core/track_features.py): a torch.save'd torchvision resnet18 state_dict or a pickle of name -> ndarray.  Read only
     # when that cost is on; empty then is a ValueError (the reference downloads the weights through torchvision, which is not possible offline)
+    # TUBE_NMS_OKS / NMS_OKS_THRESH: KRCNN.NMS_OKS is greedy NMS of the poses on their object keypoint similarity
+    # (lib/utils/keypoints.py:221-263); the reference's wiring sits behind a raise and hard-codes the threshold 0.3, here it is a key.
+    # For tubes the reference defines nothing: without TUBE_NMS_OKS they raise its NotImplementedError('Handle tubes'), with it the
+    # overlap of two tubes is the float64 mean of their T per-frame OKS values, each with the kept tube's box of that frame as the area
     c.HIP = AttrDict({'DTYPE': 'bf16', 'KEYFRAME_DCE': False, 'DEVICE_KPS_DECODE': True, 'FRAME_TRUNK_CACHE': 0,
                       'DEVICE_BOX_RESULTS': True, 'FUSE_STEM_POOL': True, 'RCCL_DIRECT': False,
                       'PIPELINE_DEPTH': 4, 'CLIP_GRAPH': True, 'IMS_PER_FORWARD': 1, 'FUSE_RELU_BWD': True, 'FUSE_RELU_SUM_BWD': True, 'PERSISTENT_CU_SHARE': 50, 'DET_SPARE_ROWS': 4,
                       'DEFER_WGRAD_FINISH': True, 'MAX_GRAPHS_PER_SLOT': 6, 'PAD_TAIL_FORWARD': True,
                       'OVERLAP_ALLREDUCE': True, 'WGRAD_PW_BATCH': 16, 'DEVICE_ROI_SAMPLING': True, 'DECONV_GROUP_IGNORED': False, 'STEM_FROM_UINT8': True,
                       'TRAIN_GROUPED_CONV': False, 'USE_GN': False, 'GN_NUM_GROUPS': 32, 'GN_EPSILON': 1e-5, 'GN_KPS_HEAD': False,
-                      'TUBE_SOFT_NMS': False, 'TRACK_CNN_WEIGHTS': ''})
+                      'TUBE_SOFT_NMS': False, 'TRACK_CNN_WEIGHTS': '',
+                      'TUBE_NMS_OKS': False, 'NMS_OKS_THRESH': 0.3})
     return c
 
 

@@ -451,7 +451,7 @@ class ClipPipeline(object):
         info = np.asarray(im_info, np.float64).reshape(-1, 3)
         out = list(res)
         for i, r in enumerate(res):
-            if r is not None:
+            if r is not None or not engine.rerun_rows_supported(n[i, 1]):      # (KRCNN.NMS_OKS beyond the kernel's rows: _host_path)
                 continue
             again = engine.enqueue_results_on_device(self.model, tuple(shapes[i]), float(info[i, 2]), out_cap=int(n[i, 1]),
                                                      image=i if len(res) > 1 else None)

@@ -13,6 +13,7 @@ import numpy as np
 from detectandtrack_amd.core.config import cfg
 from detectandtrack_amd.core.nms_wrapper import nms, soft_nms
 from detectandtrack_amd.ops.hip_ops import SOFT_NMS_MAX_BOXES      # the device Soft-NMS keeps a class's rows in LDS
+from detectandtrack_amd.ops.hip_ops import OKS_NMS_MAX_ROWS        # the device OKS-NMS keeps an image's keys, order and flags in LDS
 from detectandtrack_amd.utils.timer import Timer
 from detectandtrack_amd import workspace
 import detectandtrack_amd.utils.blob as blob_utils
@@ -176,8 +177,6 @@ def keypoint_results_on_device(model, cls_boxes, ref_boxes, im_scales, image=0):
     person = keypoint_utils.get_person_class_index()
     assert len(im_scales) == 1, 'Only single-image / single-scale batch implemented'
     time_dim = ref_boxes.shape[-1] // 4
-    if cfg.KRCNN.NMS_OKS:
-        raise NotImplementedError('Handle tubes')
     kp_rois = _get_rois_blob(ref_boxes, im_scales)
     kp_rois[:, 0] = image                               # (column 0 = the image's index in the batch: what RoIAlign reads)
     workspace.FeedBlob('keypoint_rois', kp_rois)
@@ -187,8 +186,22 @@ def keypoint_results_on_device(model, cls_boxes, ref_boxes, im_scales, image=0):
     assert heat.shape[1] == K * time_dim, 'Heatmaps must be 17xT'
     boxes = torch.from_numpy(np.ascontiguousarray(ref_boxes, dtype=np.float32)).to(heat.device)
     xy = ops.heatmaps_to_keypoints(heat.contiguous(), boxes, time_dim, K, cfg.KRCNN.INFERENCE_MIN_SIZE).cpu().numpy()
+    if cfg.KRCNN.NMS_OKS:
+        xy = _nms_oks_on_host(xy, ref_boxes, cls_boxes, person)
     cls_keyps[person] = [xy[i] for i in range(xy.shape[0])]
     return cls_keyps
+
+
+def _nms_oks_on_host(xy, ref_boxes, cls_boxes, person):
+    """KRCNN.NMS_OKS (:883-890, the statements behind the reference's unconditional raise): greedy NMS of the poses on their OKS; the
+    keypoint rows are returned re-indexed by the keep list and cls_boxes[person] is re-indexed in place, as the reference does.  Tubes:
+    the reference's NotImplementedError unless cfg.HIP.TUBE_NMS_OKS defines the overlap (utils/keypoints.compute_oks_tubes)."""
+    if ref_boxes.shape[-1] // 4 > 1 and not cfg.HIP.TUBE_NMS_OKS:
+        raise NotImplementedError('Handle tubes')
+    keypoint_utils.check_nms_oks_config()
+    keep = np.asarray(keypoint_utils.nms_oks(xy, ref_boxes, cfg.HIP.NMS_OKS_THRESH), dtype=np.int64)
+    cls_boxes[person] = cls_boxes[person][keep, :]
+    return xy[keep, :, :]
 
 
 def _tube_detections():
@@ -207,17 +220,37 @@ def _soft_nms_capacity():
     return soft_nms_tubes_max_boxes(cfg.VIDEO.NUM_FRAMES_MID)
 
 
+def _device_out_cap():
+    """Rows per image of the device detection buffers (enqueue_results_on_device without out_cap)."""
+    D = int(cfg.TEST.DETECTIONS_PER_IM)
+    return D + max(0, int(cfg.HIP.get('DET_SPARE_ROWS', 4))) if D > 0 else int(cfg.TEST.RPN_POST_NMS_TOP_N) * (cfg.MODEL.NUM_CLASSES - 1)
+
+
+def _nms_oks_on_device():
+    """KRCNN.NMS_OKS runs in the device post-processing (dat_oks_nms) for box detections, and for tubes with HIP.TUBE_NMS_OKS, when person
+    is the only foreground class, the poses have the 17 COCO keypoints and an image's rows fit the kernel.  Anything else takes the host
+    path, which raises what the config deserves (_nms_oks_on_host) or runs the host loop."""
+    return bool((not _tube_detections() or cfg.HIP.TUBE_NMS_OKS) and cfg.MODEL.NUM_CLASSES == 2 and cfg.KRCNN.NUM_KEYPOINTS == 17 and
+                _device_out_cap() <= OKS_NMS_MAX_ROWS)
+
+
 def device_results_supported():
     """The device post-processing covers FASTER_RCNN with hard NMS, and TEST.SOFT_NMS / TEST.BBOX_VOTE (:766-779) for box detections
-    and, with HIP.TUBE_SOFT_NMS, for tube detections.  Without that switch tubes with either one stay on the host path, where Soft-NMS
+    and, with HIP.TUBE_SOFT_NMS, for tube detections, and KRCNN.NMS_OKS under the conditions of _nms_oks_on_device.  Without that switch tubes with either one stay on the host path, where Soft-NMS
     is the loud error the reference raises (nms_wrapper.py:34-35); so does Soft-NMS over more rois per image
     (TEST.RPN_POST_NMS_TOP_N, the capacity of the `rois` blob) than the device kernel holds for the clip's T: the host loop has no
     capacity."""
     return bool(cfg.HIP.DEVICE_BOX_RESULTS and cfg.MODEL.FASTER_RCNN and cfg.TEST.BBOX_REG and
                 not ((cfg.TEST.SOFT_NMS.ENABLED or cfg.TEST.BBOX_VOTE.ENABLED) and _tube_detections() and not cfg.HIP.TUBE_SOFT_NMS) and
                 not (cfg.TEST.SOFT_NMS.ENABLED and cfg.TEST.RPN_POST_NMS_TOP_N > _soft_nms_capacity()) and
-                not cfg.TEST.SVM and not cfg.KRCNN.NMS_OKS and
+                not cfg.TEST.SVM and not (cfg.KRCNN.NMS_OKS and cfg.MODEL.KEYPOINTS_ON and not _nms_oks_on_device()) and
                 (cfg.HIP.DEVICE_KPS_DECODE or not cfg.MODEL.KEYPOINTS_ON))
+
+
+def rerun_rows_supported(need):
+    """The tie-overflow re-run of the device glue with `need` rows per image: dat_oks_nms holds at most OKS_NMS_MAX_ROWS (more: the host
+    path for that image)."""
+    return not (cfg.KRCNN.NMS_OKS and cfg.MODEL.KEYPOINTS_ON) or int(need) <= OKS_NMS_MAX_ROWS
 
 
 def enqueue_results_on_device(model, im_shape, im_scale, out_cap=None, image=None):
@@ -225,6 +258,9 @@ def enqueue_results_on_device(model, im_shape, im_scale, out_cap=None, image=Non
     dat_box_results (test.py:215-252 decode + clip, :750-806 score threshold / per-class NMS or Soft-NMS / voting / DETECTIONS_PER_IM, :78-123 keypoint
     rois), then -- with MODEL.KEYPOINTS_ON -- `model.keypoint_net` on the device-resident rois and the heatmap decode
     (:584-627, :865-894).  Returns device tensors (dets [cap, 4T+2], n_out int32[2], keypoint rows [cap, 4, 17T] | None).
+    With KRCNN.NMS_OKS (and keypoints) dat_oks_nms follows the decode: dets and keypoint rows are then the rows it keeps, in its
+    visiting order with zero rows behind them, and a fourth value is returned, n_keep int32[n_images] -- n_out stays what
+    dat_box_results wrote, since n_out[1] > n_out[0] is the tie-overflow signal of the read-back.
 
     Several images per forward (the `rois` blob carries one count per image): `im_shape` / `im_scale` may be per-image sequences;
     dets / keypoint rows then hold `cap` rows per image and n_out is int32[n_images, 2] (read_batch_results_from_device)."""
@@ -253,7 +289,7 @@ def enqueue_results_on_device(model, im_shape, im_scale, out_cap=None, image=Non
     # out_cap (optional): rows per image the caller wants -- the pipelined engine re-runs the glue with exactly as many rows as the
     # limit rule keeps when an image overflowed the default (core/pipeline.py)
     if out_cap is None:
-        out_cap = D + max(0, int(cfg.HIP.get('DET_SPARE_ROWS', 4))) if D > 0 else (int(rois_t.shape[0]) // ni) * (cfg.MODEL.NUM_CLASSES - 1)
+        out_cap = _device_out_cap() if D > 0 else (int(rois_t.shape[0]) // ni) * (cfg.MODEL.NUM_CLASSES - 1)
     dets, kp_rois, n_out = ops.box_results(
         rois_t, rois_n, prob, pred, cfg.MODEL.NUM_CLASSES, T, im_scale, im_shape, cfg.MODEL.BBOX_REG_WEIGHTS,
         float(np.float32(cfg.BBOX_XFORM_CLIP)), cfg.TEST.SCORE_THRESH, cfg.TEST.NMS, D, out_cap,
@@ -275,6 +311,10 @@ def enqueue_results_on_device(model, im_shape, im_scale, out_cap=None, image=Non
         assert heat.shape[1] == cfg.KRCNN.NUM_KEYPOINTS * T, 'Heatmaps must be 17xT'
         xy = ops.heatmaps_to_keypoints(heat.contiguous(), dets, T, cfg.KRCNN.NUM_KEYPOINTS,     # (box columns of the detection rows, in place)
                                        cfg.KRCNN.INFERENCE_MIN_SIZE)
+        if cfg.KRCNN.NMS_OKS:
+            keypoint_utils.check_nms_oks_config()
+            dets, xy, _, n_keep = ops.oks_nms(xy, dets, b.count, ni, T, cfg.KRCNN.NUM_KEYPOINTS, cfg.HIP.NMS_OKS_THRESH)
+            return dets, n_out, xy, n_keep
     return dets, n_out, xy
 
 
@@ -289,20 +329,21 @@ def _split_results(d, keyps, num_classes):
     return cls_boxes, cls_keyps
 
 
-def read_results_from_device(dets, n_out, xy):
+def read_results_from_device(dets, n_out, xy, n_keep=None):
     """The ONE device -> host transfer of a clip: (cls_boxes, cls_keyps) in the reference's layout, or None when exact score ties
-    at the DETECTIONS_PER_IM cut keep more rows than the device buffers hold (the caller then takes the host path)."""
+    at the DETECTIONS_PER_IM cut keep more rows than the device buffers hold (the caller then takes the host path).  n_keep (KRCNN.NMS_OKS):
+    the rows dat_oks_nms kept, the result's row count in place of n_out[0]."""
     n = n_out.cpu().numpy()
     assert n.ndim == 1, 'several images per forward: read_batch_results_from_device'
     if int(n[1]) > int(n[0]):
         return None
-    k = int(n[0])
+    k = int(n[0]) if n_keep is None else int(n_keep.cpu().numpy().reshape(-1)[0])
     d = dets[:k].cpu().numpy()
     keyps = xy[:k].cpu().numpy() if xy is not None else None
     return _split_results(d, keyps, cfg.MODEL.NUM_CLASSES)
 
 
-def read_batch_results_from_device(dets, n_out, xy):
+def read_batch_results_from_device(dets, n_out, xy, n_keep=None):
     """Several images per forward: the list of per-image (cls_boxes, cls_keyps) -- or None for an image with the exact-tie
     overflow -- from ONE read-back of the batch (dets / keypoint rows hold `cap` rows per image)."""
     n = n_out.cpu().numpy().reshape(-1, 2)
@@ -310,12 +351,13 @@ def read_batch_results_from_device(dets, n_out, xy):
     cap = int(dets.shape[0]) // ni
     d_all = dets.cpu().numpy()
     k_all = xy.cpu().numpy() if xy is not None else None
+    kept = n_keep.cpu().numpy().reshape(-1) if n_keep is not None else n[:, 0]     # (KRCNN.NMS_OKS: the rows dat_oks_nms kept)
     out = []
     for i in range(ni):
         if int(n[i, 1]) > int(n[i, 0]):
             out.append(None)
             continue
-        k = int(n[i, 0])
+        k = int(kept[i])
         d = d_all[i * cap:i * cap + k]
         keyps = k_all[i * cap:i * cap + k] if k_all is not None else None
         out.append(_split_results(d, keyps, cfg.MODEL.NUM_CLASSES))
@@ -374,7 +416,7 @@ def keypoint_results(cls_boxes, pred_heatmaps, ref_boxes):
              for t in range(time_dim)]
     xy = np.concatenate(per_t, axis=-1)
     if cfg.KRCNN.NMS_OKS:
-        raise NotImplementedError('Handle tubes')
+        xy = _nms_oks_on_host(xy, ref_boxes, cls_boxes, person)
     cls_keyps[person] = [xy[i] for i in range(xy.shape[0])]
     return cls_keyps
 
@@ -396,7 +438,8 @@ def im_detect_all(model, im, box_proposals, timers=None, frame_ids=None):
             # exact score ties at the DETECTIONS_PER_IM cut beyond the spare rows: the device glue again with as many rows as the limit rule
             # keeps (n_out[1]) -- the same kernels, every tied row, no host post-processing (the pipelined engine does the same)
             need = int(dev[1].cpu().numpy().reshape(-1)[1])
-            res = read_results_from_device(*enqueue_results_on_device(model, im[0].shape, im_scales[0], out_cap=need))
+            if rerun_rows_supported(need):
+                res = read_results_from_device(*enqueue_results_on_device(model, im[0].shape, im_scales[0], out_cap=need))
         timers['im_detect_bbox'].toc()
         if res is not None:
             cls_boxes, cls_keyps = res

@@ -195,6 +195,8 @@ _PROTOS = {
     'dat_crop_resize_patches': (_i, [_p, _p, _p, _i, _i, C.POINTER(_i), _i, _i, C.POINTER(_d), C.POINTER(_d), _p]),
     'dat_cosine_cost_workspace_bytes': (C.c_size_t, [_i, _i, _ll]),
     'dat_cosine_cost': (_i, [_p, _p, _i, _p, _i, _p, _i, _ll, _ll, _p, _p, C.c_size_t]),
+    'dat_oks_nms_host': (_i, [C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _d, C.POINTER(_i), C.POINTER(_i), C.POINTER(_d), C.POINTER(_d)]),
+    'dat_oks_nms': (_i, [_p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p]),
 }
 EXPORTS = sorted(_PROTOS)
 for _name, (_res, _args) in _PROTOS.items():

@@ -19,6 +19,11 @@ add_fpn = FPN3D.add_fpn
 add_topdown_lateral_module = FPN3D.add_topdown_lateral_module
 
 
+def add_fpn_ResNet18_conv5_body(model):
+    """(not in the reference's 2D FPN.py: the 2D form of FPN3D.add_fpn_ResNet18_conv5_body, the small body of the model tests)"""
+    return FPN3D._onto(model, ResNet.add_ResNet18_conv5_body, ResNet.stage_info_ResNet18_conv5)
+
+
 def add_fpn_ResNet50_conv5_body(model):
     return FPN3D._onto(model, ResNet.add_ResNet50_conv5_body, ResNet.stage_info_ResNet50_conv5)
 

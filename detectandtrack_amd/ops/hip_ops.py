@@ -1372,6 +1372,51 @@ def cosine_cost(fa, fb, D, dtype, out=None):
     return out
 
 
+OKS_NMS_MAX_ROWS = 1024      # DAT_OKS_NMS_MAX_ROWS: an image's score keys, visiting order and alive flags stay in LDS
+
+
+def oks_nms(kps, dets, n_rows, n_images, T, K, thresh):
+    """dat_oks_nms (greedy NMS of poses on OKS, lib/utils/keypoints.py:221-263 on the device).  kps CUDA fp32
+    [n_images * cap, 4, K*T], dets CUDA fp32 [n_images * cap, >= 4T] (the boxes are read in place), n_rows: DEVICE int32, one live-row
+    count per image (a strided view is fine).  Returns (dets and kps gathered by the keep list with zero rows behind, keep int32
+    [n_images, cap] in visiting order with -1 behind, n_keep int32 [n_images]) on the device -- no host synchronisation; the inputs
+    stay as they are."""
+    ni, T, K = int(n_images), int(T), int(K)
+    assert kps.dtype == dets.dtype == torch.float32 and kps.is_contiguous() and dets.is_contiguous() and dets.dim() == 2
+    assert n_rows.dtype == torch.int32 and n_rows.numel() == ni
+    cap = int(dets.shape[0]) // max(ni, 1)
+    assert cap * ni == int(dets.shape[0]) and kps.numel() == int(dets.shape[0]) * 4 * K * T, (tuple(kps.shape), tuple(dets.shape), ni, T, K)
+    stride = int(n_rows.stride(-1)) if n_rows.dim() >= 1 and ni > 1 else 1
+    dets_out, kps_out = torch.empty_like(dets), torch.empty_like(kps)
+    keep = torch.empty((ni, cap), dtype=torch.int32, device=dets.device)
+    n_keep = torch.empty((ni,), dtype=torch.int32, device=dets.device)
+    ctx().call('dat_oks_nms', _stream(), _ptr(kps), _ptr(dets), int(dets.shape[1]), _ptr(n_rows), stride, cap, ni, T, K, C.c_double(thresh),
+               _ptr(keep), _ptr(n_keep), _ptr(dets_out), _ptr(kps_out))
+    return dets_out, kps_out, keep, n_keep
+
+
+def oks_nms_host(kps, boxes, T, thresh, want_oks=False):
+    """dat_oks_nms_host, the kernel's host twin in C double arithmetic: kps fp32 [n, 4, 17T], boxes fp32 [n, >= 4T] (NumPy) -> (keep
+    int32 [n_keep] in visiting order, scores float64 [n], and with want_oks the float64 [n, n] similarities the loop evaluated, NaN
+    elsewhere)."""
+    kps = np.ascontiguousarray(kps, dtype=np.float32)
+    boxes = np.ascontiguousarray(boxes, dtype=np.float32)
+    n, T = int(boxes.shape[0]), int(T)
+    assert boxes.ndim == 2 and kps.size == n * 4 * 17 * T
+    keep = np.full(max(n, 1), -1, dtype=np.int32)
+    nk = C.c_int(0)
+    scores = np.zeros(max(n, 1), dtype=np.float64)
+    oks = np.full((max(n, 1), max(n, 1)), np.nan, dtype=np.float64) if want_oks else None
+    pf, pd, pi = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int)
+    rc = L.lib().dat_oks_nms_host(kps.ctypes.data_as(pf), boxes.ctypes.data_as(pf), int(boxes.shape[1]) if boxes.shape[1] else 4 * T, n, T, 17,
+                                  C.c_double(thresh), keep.ctypes.data_as(pi), C.byref(nk), scores.ctypes.data_as(pd),
+                                  oks.ctypes.data_as(pd) if want_oks else None)
+    if rc != L.DAT_OK:
+        raise L.DatError('dat_oks_nms_host: bad arguments (%d)' % rc)
+    keep = keep[:nk.value]
+    return (keep, scores[:n], oks[:n, :n]) if want_oks else (keep, scores[:n])
+
+
 def heatmaps_to_keypoints(maps, boxes, T, K, min_size=0):
     """maps fp32 CUDA [R, T*K, M, M], boxes fp32 CUDA [R, 4T] -> fp32 CUDA [R, 4, T*K] rows (x, y, logit, prob)."""
     R, TK, M, M2 = maps.shape

@@ -56,7 +56,68 @@ def heatmaps_to_keypoints(maps, rois):
     return xy
 
 
-# ---- pose distance of the tracker, TRACKING.DISTANCE_METRICS 'pose-pck' (reference :266-291) ------------------------------------
+# ---- greedy NMS of poses on object keypoint similarity, KRCNN.NMS_OKS (reference :221-263) ----------------------
+OKS_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
+
+
+def compute_oks(src_keypoints, src_roi, dst_keypoints, dst_roi):
+    """OKS of N poses against one (:240-263).  src_keypoints 4 x K, src_roi (4,), dst_keypoints N x 4 x K, dst_roi N x 4 (never read, as in
+    the reference: the area is the SOURCE box's, with the + 1 convention).  float32 inputs: differences, squares and the area in float32,
+    the division chain and the exponentials in float64, as NumPy evaluates the reference's statements.  float64 [N]."""
+    src_keypoints, dst_keypoints = np.asarray(src_keypoints, dtype=np.float32), np.asarray(dst_keypoints, dtype=np.float32)
+    src_roi = np.asarray(src_roi, dtype=np.float32)
+    vars = (OKS_SIGMAS * 2) ** 2
+    src_area = (src_roi[2] - src_roi[0] + np.float32(1)) * (src_roi[3] - src_roi[1] + np.float32(1))
+    dx = dst_keypoints[:, 0, :] - src_keypoints[0, :]
+    dy = dst_keypoints[:, 1, :] - src_keypoints[1, :]
+    e = (dx * dx + dy * dy).astype(np.float64) / vars / (np.float64(src_area) + np.spacing(1)) / 2
+    return np.sum(np.exp(-e), axis=1) / e.shape[1]
+
+
+def compute_oks_tubes(src_keypoints, src_roi, dst_keypoints, dst_roi):
+    """The tube form (cfg.HIP.TUBE_NMS_OKS; the reference defines none): src_keypoints 4 x (K T), src_roi (4 T,), dst_keypoints
+    N x 4 x (K T), dst_roi N x 4T -> the T per-frame compute_oks values, each with frame t's box of the source as the area, summed in
+    float64 in frame order from 0 and divided by T.  At T = 1 it is compute_oks bit for bit (0 + x and x / 1 are exact)."""
+    src_keypoints, dst_keypoints = np.asarray(src_keypoints), np.asarray(dst_keypoints)
+    src_roi, dst_roi = np.asarray(src_roi), np.asarray(dst_roi)
+    T = src_roi.shape[-1] // 4
+    K = src_keypoints.shape[-1] // T
+    total = np.zeros(dst_keypoints.shape[0], dtype=np.float64)
+    for t in range(T):
+        total = total + compute_oks(src_keypoints[:, t * K:(t + 1) * K], src_roi[4 * t:4 * t + 4],
+                                    dst_keypoints[:, :, t * K:(t + 1) * K], dst_roi[:, 4 * t:4 * t + 4])
+    return total / T
+
+
+def nms_oks(kp_predictions, rois, thresh):
+    """Greedy NMS on OKS (:221-237): kp_predictions N x 4 x (K T), rois N x 4T -> the kept rows in visiting order.  The score is the mean
+    logit; rows are visited in descending score order and a visited row removes every later row whose OKS with it is not <= thresh.
+    Score ties: the reference's argsort()[::-1] leaves them undefined; here the sort is stable, so among equal scores the LATER row
+    comes first (a definition).  Rows of more than 4 box columns are tubes (compute_oks_tubes; the callers gate them)."""
+    kp_predictions, rois = np.asarray(kp_predictions), np.asarray(rois)
+    oks = compute_oks if rois.shape[-1] == 4 else compute_oks_tubes
+    scores = np.mean(kp_predictions[:, 2, :], axis=1)
+    order = np.argsort(scores, kind='stable')[::-1]
+    keep = []
+    while order.size > 0:
+        i = order[0]
+        keep.append(i)
+        ovr = oks(kp_predictions[i], rois[i], kp_predictions[order[1:]], rois[order[1:]])
+        inds = np.where(ovr <= thresh)[0]
+        order = order[inds + 1]
+    return keep
+
+
+def check_nms_oks_config():
+    """What KRCNN.NMS_OKS needs of a config, host and device path alike: re-indexing cls_boxes[person] by the poses' keep list
+    (lib/core/test.py:886-890) is only right when person is the one foreground class, and the sigma table has 17 entries."""
+    if cfg.MODEL.NUM_CLASSES != 2:
+        raise ValueError('KRCNN.NMS_OKS re-indexes the person boxes by the kept poses: MODEL.NUM_CLASSES must be 2, not %d' % cfg.MODEL.NUM_CLASSES)
+    if cfg.KRCNN.NUM_KEYPOINTS != 17:
+        raise ValueError('KRCNN.NMS_OKS uses the 17 COCO keypoint sigmas: KRCNN.NUM_KEYPOINTS must be 17, not %d' % cfg.KRCNN.NUM_KEYPOINTS)
+
+
+# ---- pose distance of the tracker,TRACKING.DISTANCE_METRICS 'pose-pck' (reference :266-291) ------------------------------------
 def compute_head_size(kps, kpt_names):
     """|head_top - head_bottom| + 1 of a 3 x K / 4 x K pose (:266-274; the + 1 keeps a degenerate head from dividing by zero)."""
     kps = np.asarray(kps, dtype=np.float64)

@@ -722,6 +722,34 @@ size_t dat_cosine_cost_workspace_bytes(int n, int m, long long D);
 int dat_cosine_cost(dat_ctx* ctx, dat_stream s, int dtype, const void* fa, int n, const void* fb, int m, long long D, long long ld,
                     float* cost, void* ws, size_t ws_bytes);
 
+/* ---- greedy NMS of poses on object keypoint similarity, KRCNN.NMS_OKS (lib/utils/keypoints.py:221-263) -----
+ * Rows: kps fp32 [.][4][K*T] (x, y, logit, prob; frame-major columns t*K + k) with their boxes, 4T coordinates at the start of rows of
+ * box_ld / det_ld floats.  score = the mean of a row's K*T logits (double, storage order); rows are visited in descending score
+ * order, among equal scores the later row first.  A visited row i is kept and removes every row j still alive behind it unless
+ * OKS(i, j) <= thresh;  OKS(i, j) = (sum_t mean_k exp(-e)) / T,  e = (dx^2 + dy^2) / vars[k] / (area_i,t + 2^-52) / 2,  vars =
+ * (2 sigma_k)^2 of the 17 COCO sigmas, area_i,t = (x2 - x1 + 1)(y2 - y1 + 1) of frame t's box of the KEPT row: differences, squares
+ * and the area in float32, the division chain, exp and the sums in double, keypoints in order within frames in order from 0.  At
+ * T = 1 this is the reference's nms_oks statement for statement (its argsort leaves ties undefined).  The probability row of a
+ * pose and the columns of a box row behind the 4T coordinates are never read.  K != 17 or T outside 1..16 is DAT_ERR_ARG.
+ *
+ * dat_oks_nms_host: HOST pointers, plain C double arithmetic; keep [n] = the kept rows in visiting order, *n_keep their number.
+ * scores_out (double [n]) and oks_out (double [n][n]: entry [i][j] written for every pair the loop evaluates, the rest untouched)
+ * may be NULL.  The comparison path of dat_oks_nms. */
+int dat_oks_nms_host(const float* kps, const float* boxes, int box_ld, int n, int T, int K, double thresh, int* keep, int* n_keep,
+                     double* scores_out, double* oks_out);
+/* dat_oks_nms: all DEVICE pointers, one block per image, no host synchronisation, no scratch, a launch shape that depends on n_images
+ * only (capturable).  Image i owns rows [i*cap, (i+1)*cap) of kps and of dets ([4T | score | class] rows of det_ld floats, the boxes
+ * read in place); its first min(max(n_rows[i * n_rows_stride], 0), cap) rows are live, the others are never read.  Outputs: keep
+ * int32 [n_images][cap] in visiting order, -1 past the end; n_keep int32 [n_images]; dets_out / kps_out (shaped like dets / kps, and
+ * not the same buffers): the live rows gathered by keep, zero rows past n_keep.  n_rows, dets and kps are left as they are.  Two runs
+ * write identical bytes; against dat_oks_nms_host the similarities differ by a few ulp (one reciprocal per kept row and
+ * keypoint in place of the division chain, the device exp()).
+ * cap > DAT_OKS_NMS_MAX_ROWS (the rows' keys, order and flags stay in LDS) is DAT_ERR_ARG and launches nothing; n_images == 0 is a
+ * no-op. */
+#define DAT_OKS_NMS_MAX_ROWS 1024
+int dat_oks_nms(dat_ctx* ctx, dat_stream s, const float* kps, const float* dets, int det_ld, const int* n_rows, int n_rows_stride, int cap,
+                int n_images, int T, int K, double thresh, int* keep, int* n_keep, float* dets_out, float* kps_out);
+
 #ifdef __cplusplus
 }
 #endif
