@@ -1088,7 +1088,18 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
     const int ntaps = d->KH * d->KW;
     const long long nbn = p.Cout_pad / (small_n ? 64 : 128);
     int bp = 128, ksplit = 1;
-    {
+    // The split-K factor decides the order in which a result's fp32 partial sums are added, so it must not depend on how many images
+    // share a per-RoI blob: with d->plan_frames (the rows of ONE image) the factor is the one the model picks for that many frames, and
+    // only the tile size follows the real grid -- an image's head results are then bit-equal to those it gets in a forward of its own.
+    const int plan_passes = (d->plan_frames > 0 && d->plan_frames < d->frames && !force_ks) ? 2 : 1;
+    int ks_fixed = force_ks;
+    for (int pass = 0; pass < plan_passes; ++pass) {
+        const bool model_pass = plan_passes == 2 && pass == 0;
+        ConvParams pm = p;
+        if (model_pass) pm.frames = d->plan_frames;
+        const ConvParams& p = pm;       // (shadows the launch parameters inside the model)
+        const int force_ks = ks_fixed;
+        bp = 128; ksplit = 1;
         double best = 1e30;
         const bool deep_1x1 = (ntaps == 1 && ncc >= 16);
         for (int cand_bp = 128; cand_bp <= 256; cand_bp += 128) {
@@ -1122,6 +1133,7 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
                 if (t < best) { best = t; bp = cand_bp; ksplit = ks; }
             }
         }
+        if (model_pass) ks_fixed = ksplit;
     }
     const bool big = bp == 256;
     int tag = (small_n ? 64 : 128) * 10000 + bp * 10 + d->dtype + (dil > 1 ? 5 : 0);   // (last digit 5-7: a dilated layer, always this kernel)

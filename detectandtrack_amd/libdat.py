@@ -28,7 +28,7 @@ class DatError(RuntimeError):
 class ConvDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in (
         'dtype', 'frames', 'T', 'H', 'W', 'Cin', 'Cout', 'out_cstride', 'KT', 'KH', 'KW',
-        'stride_h', 'stride_w', 'pad_t', 'pad_h', 'pad_w', 'relu', 'res_mode', 'out_t0', 'out_tn', 'in_t0', 'in_tn', 'dil_h', 'dil_w')]
+        'stride_h', 'stride_w', 'pad_t', 'pad_h', 'pad_w', 'relu', 'res_mode', 'out_t0', 'out_tn', 'in_t0', 'in_tn', 'plan_frames', 'dil_h', 'dil_w')]
 
 
 class PackItem(C.Structure):
@@ -72,6 +72,11 @@ class RpnLevel(C.Structure):
     _fields_ = [('H', C.c_int), ('W', C.c_int), ('A', C.c_int), ('T', C.c_int), ('feat_stride', C.c_float),
                 ('cstride', C.c_int), ('logit_off', C.c_int), ('delta_off', C.c_int), ('frame', C.c_int),
                 ('apply_sigmoid', C.c_int), ('per_frame', C.c_int)]
+
+
+class NonLocalDesc(C.Structure):
+    _fields_ = [('dtype', C.c_int), ('clips', C.c_int), ('Lq', C.c_longlong), ('Lk', C.c_longlong), ('D', C.c_int), ('ldq', C.c_int),
+                ('ldk', C.c_int), ('ldv', C.c_int), ('ldy', C.c_int), ('scale', C.c_float)]
 
 
 if not os.path.exists(LIB_PATH):
@@ -197,6 +202,7 @@ _PROTOS = {
     'dat_cosine_cost': (_i, [_p, _p, _i, _p, _i, _p, _i, _ll, _ll, _p, _p, C.c_size_t]),
     'dat_oks_nms_host': (_i, [C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _d, C.POINTER(_i), C.POINTER(_i), C.POINTER(_d), C.POINTER(_d)]),
     'dat_oks_nms': (_i, [_p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p]),
+    'dat_nonlocal_attention': (_i, [_p, _p, C.POINTER(NonLocalDesc), _p, _p, _p, _p]),
 }
 EXPORTS = sorted(_PROTOS)
 for _name, (_res, _args) in _PROTOS.items():

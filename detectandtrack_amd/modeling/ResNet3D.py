@@ -6,6 +6,8 @@ arithmetic.  "3D" here means full kT x 3 x 3 kernels with kT = VIDEO.TIME_KERNEL
 kT = 1 in conv1/res2, never a temporal stride (reference ResNet3D.py:258-284).  The `*_2plus1d_*` bodies
 (ResNet-(2+1)D, Tran et al., CVPR 2018; no reference code) factorise every kT x 3 x 3 conv of res3..res5 into a 1 x 3 x 3 conv,
 affine, ReLU and a kT x 1 x 1 conv, affine; blob names of block outputs, stage outputs and FPN taps stay those of the I3D body.
+Blocks of res3 / res4 named in HIP.NONLOCAL are followed by a spacetime non-local block (add_nonlocal_block; Wang et al., CVPR 2018; no
+reference code; inference only); stage output names stay what FPN and the heads look up.
 """
 from detectandtrack_amd.core.config import cfg
 from detectandtrack_amd.modeling.common import ConvStageInfo
@@ -110,26 +112,82 @@ def add_shortcut(model, prefix, blob_in, dim_in, dim_out, stride, time_stride_on
 
 
 def add_bottleneck_block(stage_id, model, prefix, blob_in, dim_in, dim_out, dim_inner, dilation, stride_init=2,
-                         inplace_sum=False, time_kernel_dim=1, time_stride_on=False):
+                         inplace_sum=False, time_kernel_dim=1, time_stride_on=False, sum_name=None):
     """transformation + shortcut -> Sum -> Relu (reference :120-154).  The explicit stage_id keeps stride 1 in
-    the first stage even for R-18/34 where dim_in == dim_out == 64 (:133-135)."""
+    the first stage even for R-18/34 where dim_in == dim_out == 64 (:133-135).  sum_name: another name for the block's `<prefix>_sum`
+    (a non-local block behind the last block of a stage takes that name, add_stage)."""
     stride = stride_init if (dim_in != dim_out and stage_id != 1 and dilation == 1) else 1
     tr = _TRANS[cfg.RESNETS.TRANS_FUNC](model, blob_in, dim_in, dim_out, stride, prefix, dim_inner,
                                         group=cfg.RESNETS.NUM_GROUPS, dilation=dilation,
                                         time_kernel_dim=time_kernel_dim, time_stride_on=time_stride_on)
     sc = add_shortcut(model, prefix, blob_in, dim_in, dim_out, stride, time_stride_on=time_stride_on)
-    s = model.net.Sum([tr, sc], tr if inplace_sum else prefix + '_sum')
+    s = model.net.Sum([tr, sc], tr if inplace_sum else (sum_name or prefix + '_sum'))
     return model.Relu(s, s)
+
+
+NONLOCAL_STAGES = ('res3', 'res4')
+
+
+def parse_nonlocal_spec(spec):
+    """HIP.NONLOCAL 'res3_1,res4_0' -> [('res3', 1), ('res4', 0)]: the body blocks that get a spacetime non-local block behind them.  Only
+    res3 and res4 take one (res2 is too large to attend over, res5 of the C4 models is a per-RoI head); a name twice is an error."""
+    out = []
+    for name in [s.strip() for s in str(spec).split(',') if s.strip()]:
+        stage, _, idx = name.rpartition('_')
+        if stage not in NONLOCAL_STAGES or not idx.isdigit():
+            raise ValueError('HIP.NONLOCAL: %r is not a block of %s (expected names like res3_1, res4_0)' % (name, ' / '.join(NONLOCAL_STAGES)))
+        if (stage, int(idx)) in out:
+            raise ValueError('HIP.NONLOCAL: block %r is listed twice' % (name,))
+        out.append((stage, int(idx)))
+    return out
+
+
+def nonlocal_blocks_of_stage(prefix, n, dim):
+    """Indices of the blocks of stage `prefix` (n blocks of `dim` channels) named in HIP.NONLOCAL."""
+    idx = [i for stage, i in parse_nonlocal_spec(cfg.HIP.NONLOCAL) if stage == prefix]
+    for i in idx:
+        if i >= n:
+            raise ValueError('HIP.NONLOCAL: %s_%d is outside its stage, which has blocks %s_0 .. %s_%d' % (prefix, i, prefix, prefix, n - 1))
+    if idx and dim % 2:
+        raise ValueError('HIP.NONLOCAL: stage %s has %d channels, an odd number: the block works on C / 2' % (prefix, dim))
+    return idx
+
+
+def add_nonlocal_block(model, blob_in, dim, nl, blob_out):
+    """Spacetime non-local block, embedded-Gaussian form (Wang et al., CVPR 2018; inference only): theta / phi / g
+    1x1x1 convs to D = dim / 2 channels, phi and g max-pooled 2 x 2 in space (HIP.NONLOCAL_MAXPOOL), y = softmax(scale theta phi^T) g over
+    every position of the CLIP in one fused launch, then `<nl>_out` (D -> dim, no bias) + `<nl>_out_bn` + blob_in with no ReLU -- one conv
+    launch with the residual in its epilogue.  `_out_bn_s` starts at zero: a checkpoint without the block's blobs gives the base network."""
+    D = dim // 2
+    one, zero = [1, 1, 1], 2 * [0, 0, 0]
+    theta = model.ConvNd(blob_in, nl + '_theta', dim, D, one, strides=one, pads=zero)
+    phi = model.ConvNd(blob_in, nl + '_phi', dim, D, one, strides=one, pads=zero)
+    g = model.ConvNd(blob_in, nl + '_g', dim, D, one, strides=one, pads=zero)
+    if cfg.HIP.NONLOCAL_MAXPOOL:
+        phi = model.MaxPool(phi, nl + '_phi_pool', kernels=[1, 2, 2], pads=zero, strides=[1, 2, 2])
+        g = model.MaxPool(g, nl + '_g_pool', kernels=[1, 2, 2], pads=zero, strides=[1, 2, 2])
+    y = model.NonLocalAttention([theta, phi, g], nl + '_y', dim=D, scale=D ** -0.5 if cfg.HIP.NONLOCAL_SCALE else 1.)
+    z = model.ConvNd(y, nl + '_out', D, dim, one, strides=one, pads=zero, no_bias=1)
+    z = model.AffineChannelNd(z, nl + '_out_bn', dim_out=dim, scale_init=('ConstantFill', {'value': 0.}))
+    return model.net.Sum([z, blob_in], blob_out)
 
 
 def add_stage(stage_id, model, prefix, blob_in, n, dim_in, dim_out, dim_inner, dilation, stride_init=2,
               time_kernel_dim=1, time_stride_on=False):
-    """n blocks; the last block's sum is a named blob (`<prefix>_<n-1>_sum`) because FPN taps it (:210-227)."""
+    """n blocks; the last block's sum is a named blob (`<prefix>_<n-1>_sum`) because FPN taps it (:210-227).  A block named in
+    HIP.NONLOCAL is followed by a non-local block `nonlocal_<prefix>_<i>`: behind the last block it takes the stage's output name (the
+    body block's own sum becomes `<prefix>_<n-1>_sum_nl_in`), anywhere else it writes `nonlocal_<prefix>_<i>_sum`."""
+    nonlocal_at = nonlocal_blocks_of_stage(prefix, n, dim_out) if cfg.HIP.NONLOCAL else ()
     for i in range(n):
-        blob_in = add_bottleneck_block(stage_id, model, '{}_{}'.format(prefix, i), blob_in, dim_in, dim_out, dim_inner,
+        name = '{}_{}'.format(prefix, i)
+        taken = i in nonlocal_at and i == n - 1
+        blob_in = add_bottleneck_block(stage_id, model, name, blob_in, dim_in, dim_out, dim_inner,
                                        dilation, stride_init, inplace_sum=i < n - 1,
-                                       time_kernel_dim=time_kernel_dim, time_stride_on=time_stride_on)
+                                       time_kernel_dim=time_kernel_dim, time_stride_on=time_stride_on,
+                                       **({'sum_name': name + '_sum_nl_in'} if taken else {}))
         dim_in = dim_out
+        if i in nonlocal_at:
+            blob_in = add_nonlocal_block(model, blob_in, dim_out, 'nonlocal_' + name, name + '_sum' if taken else 'nonlocal_' + name + '_sum')
     return blob_in, dim_in
 
 

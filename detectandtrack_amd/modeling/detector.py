@@ -210,17 +210,18 @@ class DetectionModelHelper(object):
             return self.ConvNd(blob_in, blob_out, dim_in, dim_out, kernel, weight=weight, bias=bias, **kwargs)
         return self.Conv(blob_in, blob_out, dim_in, dim_out, kernel, weight=weight, bias=bias, **kwargs)
 
-    def AffineChannelNd(self, blob_in, blob_out, dim_out, share_with=None, inplace=False):
-        """detector.py:89-108.  Folded into the producing conv's epilogue when possible."""
+    def AffineChannelNd(self, blob_in, blob_out, dim_out, share_with=None, inplace=False, scale_init=None):
+        """detector.py:89-108.  Folded into the producing conv's epilogue when possible.  scale_init: init spec of `_s` in place of the
+        constant 1 (the zero-initialised last scale of a non-local block)."""
         if cfg.HIP.USE_GN and cfg.MODEL.USE_BN:
             raise ValueError('HIP.USE_GN and MODEL.USE_BN both replace every AffineChannel[Nd]: set one of them')
         if cfg.MODEL.USE_BN:
-            return self.SpatialBNLayer(blob_in, blob_out, dim_out, share_with, inplace)
+            return self.SpatialBNLayer(blob_in, blob_out, dim_out, share_with, inplace, scale_init=scale_init)
         if cfg.HIP.USE_GN:
-            return self.GroupNormLayer(blob_in, blob_out, dim_out, share_with, inplace)
+            return self.GroupNormLayer(blob_in, blob_out, dim_out, share_with, inplace, scale_init=scale_init)
         blob_in = str(blob_in)
         prefix = str(blob_out) if share_with is None else share_with
-        s = self._param(prefix + '_s', [dim_out], ('ConstantFill', {'value': 1.}), 'w')
+        s = self._param(prefix + '_s', [dim_out], scale_init or ('ConstantFill', {'value': 1.}), 'w')
         b = self._param(prefix + '_b', [dim_out], ('ConstantFill', {'value': 0.}), 'b')
         self.param_specs[s]['affine'] = self.param_specs[b]['affine'] = True
         return self._record_affine(blob_in, blob_in if inplace else str(blob_out), s, b)
@@ -237,7 +238,7 @@ class DetectionModelHelper(object):
             return out
         return self.net.add(Op('AffineChannel', [blob_in], [out], scale=s, shift=b, **bn))
 
-    def SpatialBNLayer(self, blob_in, blob_out, dim_out, share_with=None, inplace=False):
+    def SpatialBNLayer(self, blob_in, blob_out, dim_out, share_with=None, inplace=False, scale_init=None):
         """detector.py:111-124: Caffe2 SpatialBN in place of every AffineChannel[Nd] (MODEL.USE_BN).  Parameters `<blob>_s` (a weight),
         `<blob>_b` (a bias), and the computed `<blob>_rm` / `<blob>_riv` (running mean / running VARIANCE, utils/net.py:225-233).
         Test mode is the affine graph with the folded pair; training mode records a `SpatialBN` op behind the unfused conv."""
@@ -245,7 +246,7 @@ class DetectionModelHelper(object):
             raise NotImplementedError('Handle that')
         blob_in, prefix = str(blob_in), str(blob_out)
         is_test = True if cfg.MODEL.USE_BN_TESTMODE_ONLY else not self.train
-        s = self._param(prefix + '_s', [dim_out], ('ConstantFill', {'value': 1.}), 'w')
+        s = self._param(prefix + '_s', [dim_out], scale_init or ('ConstantFill', {'value': 1.}), 'w')
         b = self._param(prefix + '_b', [dim_out], ('ConstantFill', {'value': 0.}), 'b')
         rm = self._param(prefix + '_rm', [dim_out], ('ConstantFill', {'value': 0.}), 'c')
         riv = self._param(prefix + '_riv', [dim_out], ('ConstantFill', {'value': 1.}), 'c')
@@ -259,14 +260,14 @@ class DetectionModelHelper(object):
         return self.net.add(Op('SpatialBN', [blob_in], [prefix], scale=s, bias=b, rm=rm, riv=riv, eps=eps,
                                momentum=float(cfg.MODEL.BN_MOMENTUM), relu=False, residual=None))
 
-    def GroupNormLayer(self, blob_in, blob_out, dim_out, share_with=None, inplace=False):
+    def GroupNormLayer(self, blob_in, blob_out, dim_out, share_with=None, inplace=False, scale_init=None):
         """GroupNorm in place of every AffineChannel[Nd] (HIP.USE_GN; not in the reference): statistics per clip and group, so the op is
         the same in training and test graphs and has no computed parameters.  `<blob>_s` (a weight, init 1) and `<blob>_b` (a bias,
         init 0) train.  Recorded behind the unfused conv; `Sum` and `Relu` fold into it as they fold into a SpatialBN."""
         if share_with is not None:
             raise NotImplementedError('Handle that')
         blob_in, prefix = str(blob_in), str(blob_out)
-        s = self._param(prefix + '_s', [dim_out], ('ConstantFill', {'value': 1.}), 'w')
+        s = self._param(prefix + '_s', [dim_out], scale_init or ('ConstantFill', {'value': 1.}), 'w')
         b = self._param(prefix + '_b', [dim_out], ('ConstantFill', {'value': 0.}), 'b')
         self.param_specs[s]['gn'] = self.param_specs[b]['gn'] = True
         # (keeps its input for the backward, and the statistics pass reads it before the apply pass writes: never in place)
@@ -310,6 +311,12 @@ class DetectionModelHelper(object):
         assert kernels[0] == 1 and strides[0] == 1 and kernels[1] == kernels[2] and strides[1] == strides[2]
         return self.net.add(Op('MaxPool', [str(blob_in)], [str(blob_out)], k=int(kernels[1]), stride=int(strides[1]),
                                pad=int(pads[1])))
+
+    def NonLocalAttention(self, blobs_in, blob_out, dim, scale):
+        """y = softmax(scale * theta phi^T) g over all positions of a clip (blobs_in = [theta, phi, g], `dim` channels each): one fused
+        launch that never writes the scores (csrc/nonlocal.hip).  Inference only."""
+        assert len(blobs_in) == 3, blobs_in
+        return self.net.add(Op('NonLocalAttention', [str(b) for b in blobs_in], [str(blob_out)], dim=int(dim), scale=float(scale)))
 
     def FC(self, blob_in, blob_out, dim_in, dim_out, weight_init=None, bias_init=None):
         blob_out = str(blob_out)

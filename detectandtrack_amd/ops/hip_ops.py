@@ -265,8 +265,9 @@ class ConvLayer(object):
         if not weights_only and self.bias_src is not None:
             self.bias[:self.cout_real] = self.bias_src.float()
 
-    def desc(self, frames, T, H, W, res_mode=0, relu=None, cstride=None, out_t=None, in_t=None):
+    def desc(self, frames, T, H, W, res_mode=0, relu=None, cstride=None, out_t=None, in_t=None, plan_frames=0):
         d = L.ConvDesc()
+        d.plan_frames = int(plan_frames)
         d.dtype = L.DAT_BF16X3 if self.x3 else self.dtype
         d.frames, d.T, d.H, d.W, d.Cin = frames, T, H, W, self.cin
         d.Cout = self.cout
@@ -309,15 +310,16 @@ class ConvLayer(object):
         return float(b)
 
     def __call__(self, x, T=1, residual=None, res_mode=None, out=None, out_t=None, in_t=None, x_split=None, zero_pad=True,
-                 want_split=False, addend=None):
+                 want_split=False, addend=None, plan_frames=0):
         """out_t = (t0, n): only output frames t0..t0+n-1 of every clip are computed and stored.
+        plan_frames: the rows one image contributes to a per-RoI blob of several images (dat_conv_desc.plan_frames).
         x_split (bf16x3 layers): the hi / lo split of `x` when the caller already has it (a blob read by several convs is split once)."""
         frames, H, W, cin = x.shape
         assert cin == self.cin, 'channel stride %d != layer Cin %d' % (cin, self.cin)
         assert x.dtype == tdtype(self.dtype) and x.is_contiguous()
         if res_mode is None:
             res_mode = 1 if residual is not None else 0
-        d = self.desc(frames, T, H, W, res_mode, out_t=out_t, in_t=in_t)
+        d = self.desc(frames, T, H, W, res_mode, out_t=out_t, in_t=in_t, plan_frames=plan_frames)
         ho, wo = self.out_hw(H, W)
         oframes = frames if out_t is None else frames // T * out_t[1]
         if out is None:
@@ -1369,6 +1371,26 @@ def cosine_cost(fa, fb, D, dtype, out=None):
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=fa.device)
     ctx().call('dat_cosine_cost', _stream(), dtype, _ptr(fa), n, _ptr(fb), m, C.c_longlong(int(D)), C.c_longlong(ld), _ptr(out), _ptr(ws),
                C.c_size_t(nbytes))
+    return out
+
+
+def nonlocal_attention(q, k, v, dtype, clips, D, scale, out=None):
+    """dat_nonlocal_attention (fused q k^T -> softmax -> p v of the spacetime non-local block).  q [clips * Lq, ldq],
+    k / v [clips * Lk, ld] CUDA tensors of `dtype` (F32 | BF16 = the build's 16-bit format) whose first D channels are the operands; they
+    may be channel-range views of wider blobs (unit channel stride, any row stride).  Returns y [clips * Lq, D] (or fills the first D
+    channels of `out`'s rows and leaves the rest alone); the scores are never materialised and nothing is allocated besides y."""
+    clips, D = int(clips), int(D)
+    for t in (q, k, v):
+        assert t.dim() == 2 and t.stride(1) == 1 and t.shape[1] >= D and t.dtype == tdtype(dtype), (tuple(t.shape), t.stride(), t.dtype, D)
+    assert clips >= 1 and q.shape[0] % clips == 0 and k.shape[0] % clips == 0 and k.shape[0] == v.shape[0], (q.shape, k.shape, v.shape, clips)
+    if out is None:
+        out = torch.empty((q.shape[0], D), dtype=q.dtype, device=q.device)
+    assert out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == q.shape[0] and out.shape[1] >= D and out.dtype == q.dtype
+    d = L.NonLocalDesc()
+    d.dtype, d.clips, d.D, d.scale = dtype, clips, D, float(scale)
+    d.Lq, d.Lk = int(q.shape[0]) // clips, int(k.shape[0]) // clips
+    d.ldq, d.ldk, d.ldv, d.ldy = int(q.stride(0)), int(k.stride(0)), int(v.stride(0)), int(out.stride(0))
+    ctx().call('dat_nonlocal_attention', _stream(), C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(out))
     return out
 
 

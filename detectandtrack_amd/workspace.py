@@ -243,6 +243,9 @@ def check_bn_sees_every_frame(net):
     if any(op.type == 'GroupNorm' for op in net.ops):
         raise ValueError('net %r holds GroupNorm ops (HIP.USE_GN), whose statistics need every frame of the clip: not combinable with '
                          'HIP.KEYFRAME_DCE / HIP.FRAME_TRUNK_CACHE, which compute a subset of the frames' % (net.name,))
+    if any(op.type == 'NonLocalAttention' for op in net.ops):
+        raise ValueError('net %r holds NonLocalAttention ops (HIP.NONLOCAL), where every position attends to every frame of the clip: not '
+                         'combinable with HIP.KEYFRAME_DCE / HIP.FRAME_TRUNK_CACHE, which compute a subset of the frames' % (net.name,))
 
 
 def _mode(ws=None):
@@ -517,8 +520,12 @@ class Executor(object):
         assert xin.keyframe is None or a['kernels'][0] == 1, 'temporal conv on a key-frame-only blob'
         self._log_conv(op.outputs[0], layer, xin.t.shape[0], xin.t.shape[1], xin.t.shape[2],
                        res_mode=(a['res_mode'] or 1) if res is not None else 0)
+        # a per-RoI blob of several images (one count per image): the layer is planned for one image's rows, so that an image's head
+        # results do not depend on how many images share the forward
+        n_img = xin.count.numel() if (xin.roi and isinstance(xin.count, torch.Tensor)) else 1
+        per_image = xin.t.shape[0] // n_img if (n_img > 1 and xin.t.shape[0] % n_img == 0) else 0
         y = layer(xin.t, T=xin.T, residual=res, res_mode=a['res_mode'], x_split=self._split_of(xin, layer),
-                  want_split=layer.x3 and self._read_by_a_conv(op.outputs[0]))
+                  want_split=layer.x3 and self._read_by_a_conv(op.outputs[0]), plan_frames=per_image)
         b = Blob(y, 'fmap', xin.N, xin.T, a['dim_out'], dt, xin.five_d)
         b.split = getattr(y, '_split', None)      # (bf16x3: written by this conv's epilogue for the convs that read the blob)
         b.keyframe = xin.keyframe
@@ -717,6 +724,20 @@ class Executor(object):
         b = Blob(y, 'fmap', x.N, x.T, x.C, x.dt, x.five_d)
         b.bn = (x.t, st)
         ws.blobs[op.outputs[0]] = b
+
+    def op_NonLocalAttention(self, i, op):
+        """softmax(scale theta phi^T) g per clip in one fused launch (ops.nonlocal_attention): the rows of a clip are its T x H x W
+        positions in storage order, the keys the (pooled) positions of the same clip.  Nothing synchronises or allocates besides y, so the
+        op is captured into a clip graph like a conv."""
+        ws, a = self.ws, op.args
+        q, k, v = (ws.blobs[n] for n in op.inputs)
+        for x in (q, k, v):
+            assert x.kind == 'fmap' and x.keyframe is None and x.tsel is None and not x.t2c and x.count is None, (op, x.kind)
+            assert x.C == a['dim'] and x.N == q.N and x.T == q.T and x.dt == q.dt and x.t.shape[0] == x.N * x.T, (op, x.C, x.N, x.T)
+        assert k.t.shape[:3] == v.t.shape[:3], (op, tuple(k.t.shape), tuple(v.t.shape))
+        rows = lambda x: x.t.view(-1, x.t.shape[3])
+        y = ops.nonlocal_attention(rows(q), rows(k), rows(v), q.dt, q.N, a['dim'], a['scale'])
+        ws.blobs[op.outputs[0]] = Blob(y.view(tuple(q.t.shape[:3]) + (a['dim'],)), 'fmap', q.N, q.T, a['dim'], q.dt, q.five_d)
 
     def op_MaxPool(self, i, op):
         x = self.ws.blobs[op.inputs[0]]

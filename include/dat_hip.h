@@ -108,6 +108,9 @@ typedef struct {
                                 indexed like the output */
     int in_t0, in_tn;        /* in_tn > 0: input frames outside [in_t0, in_t0+in_tn) of every clip are known to be ZERO (a key-frame
                                 gradient embedded in its temporal window): the temporal taps that would read them are skipped */
+    int plan_frames;         /* 0, or the frames (rows) ONE image contributes to a per-RoI blob that holds several images: dat_conv3d_fwd then
+                                picks the split-K factor it would pick for plan_frames frames, so that an image's results do not depend on how
+                                many images share the forward (the factor fixes the order of the fp32 partial sums).  0 or >= frames: frames */
     int dil_h, dil_w;        /* spatial dilation d (MODEL.DILATION): tap (kh, kw) reads x[oh + kh*d - pad_h, ow + kw*d - pad_w]; 0 and 1 both mean
                                 "not dilated" (zero-initialised descriptors keep their meaning).  d > 1 needs dil_h == dil_w, spatial stride 1
                                 and the dense entry points (the grouped ones refuse it); there is no temporal dilation.  A 1x1 spatial kernel
@@ -749,6 +752,24 @@ int dat_oks_nms_host(const float* kps, const float* boxes, int box_ld, int n, in
 #define DAT_OKS_NMS_MAX_ROWS 1024
 int dat_oks_nms(dat_ctx* ctx, dat_stream s, const float* kps, const float* dets, int det_ld, const int* n_rows, int n_rows_stride, int cap,
                 int n_images, int T, int K, double thresh, int* keep, int* n_keep, float* dets_out, float* kps_out);
+
+/* ---- spacetime non-local block (HIP.NONLOCAL): fused q k^T -> softmax -> p v ---------------------------------- */
+/* Per clip c and query row i:  y[i, :] = sum_j softmax_j(scale * <q[i, :], k[j, :]>) v[j, :]  over that clip's Lk key rows.  The scores
+ * never reach memory: no workspace, no atomics, no host synchronisation (capturable), bitwise reproducible, and a clip's result does not
+ * depend on `clips`.  Scores, the denominator and the PV sums accumulate in fp32; scale is applied in fp32 to the accumulated score; the
+ * row maximum is subtracted.  DAT_BF16: MFMA path in the build's 16-bit format, p rounded to nearest once before the PV product, the
+ * output rounded once.  DAT_F32: exact fp32 fma chains (v_mfma_f32_32x32x2_f32) -- the parity path of HIP.DTYPE fp32 / bf16x3.  Only the
+ * D channels of each y row are written; k and v may be channel ranges of one blob.  Any other dtype or D is DAT_ERR_UNSUPPORTED, every other
+ * violation of the field comments DAT_ERR_ARG, both with a dat_last_error() text and no launch; there is no fall-back path. */
+typedef struct {
+    int dtype;               /* DAT_F32 | DAT_BF16 (the build's 16-bit format) */
+    int clips;               /* independent problems: rows of clip c are [c*Lq, (c+1)*Lq) of q / y, [c*Lk, (c+1)*Lk) of k / v */
+    long long Lq, Lk;        /* query / key rows per clip, >= 1 */
+    int D;                   /* channels of q, k, v, y: 64 | 128 | 256 | 512 */
+    int ldq, ldk, ldv, ldy;  /* row strides in elements: >= D, multiples of 8; pointers 16-byte aligned */
+    float scale;
+} dat_nonlocal_desc;
+int dat_nonlocal_attention(dat_ctx* ctx, dat_stream s, const dat_nonlocal_desc* d, const void* q, const void* k, const void* v, void* y);
 
 #ifdef __cplusplus
 }
