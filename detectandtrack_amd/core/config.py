@@ -254,7 +254,12 @@ def _build_defaults():
     # slot, completion-order read-back, uint8 frame upload on a copy stream, dat_preprocess_frames); 1 = strictly sequential;
     # 0 = the reference's eager loop through im_detect_all (host pre-processing, fp32 upload).  CLIP_GRAPH: every slot replays its
     # forward as one captured hipGraph.  IMS_PER_FORWARD: independent images (2D models) / clips (3D models) per forward -- the N
-    # axis of the blobs; every image keeps the results it gets alone (the reference runs one image per forward, core/test.py:212-214)
+    # axis of the blobs; every image keeps the results it gets alone (the reference runs one image per forward, core/test.py:212-214).
+    # What is held bit for bit (tests/test_gpu_batch_invariance.py): the HEADS -- given bit-equal RoI features an image's box-head and
+    # keypoint-head blobs do not depend on how many images share the forward (every per-RoI conv / FC / deconv is planned for one image's
+    # rows, dat_conv_desc.plan_frames) -- and, at a fixed number of images, a clip's results do not depend on its companions or its slot.
+    # The BODY convs are planned from the whole grid (planning the four-clip step from one clip's frames would change its plans): the
+    # features, and with them proposals and detections, of a clip in a batch equal those it gets alone where the body's plans coincide.
     # DEFER_WGRAD_FINISH (training): conv weight gradients accumulate in the kernels' own [tap][Cout][Cin] order in one flat buffer and ONE
     # launch per iteration turns them into gradients (training.py), instead of a memset + a finish launch around every layer's kernel.
     # MAX_GRAPHS_PER_SLOT: captured hipGraphs (one per input geometry, each with a private pool holding a forward's activations) kept

@@ -1091,12 +1091,24 @@ static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, c
     // The split-K factor decides the order in which a result's fp32 partial sums are added, so it must not depend on how many images
     // share a per-RoI blob: with d->plan_frames (the rows of ONE image) the factor is the one the model picks for that many frames, and
     // only the tile size follows the real grid -- an image's head results are then bit-equal to those it gets in a forward of its own.
-    const int plan_passes = (d->plan_frames > 0 && d->plan_frames < d->frames && !force_ks) ? 2 : 1;
+    // The rows of a per-RoI blob lie on its frames -- or, for the [1, 1, R, K] rows view of the FC layers (one frame, one map row), on W:
+    // plan_frames then counts map columns.  A layer with an output-frame window computes plan_frames / T * out_tn frames per image.
+    const bool plan_on_w = d->frames == 1 && d->H == 1;
+    const bool per_image = d->plan_frames > 0 && d->plan_frames < (plan_on_w ? d->W : d->frames);
+    DAT_ENFORCE(ctx, !per_image || plan_on_w || d->plan_frames % d->T == 0, "conv3d_fwd: plan_frames %d must be a multiple of T %d",
+                d->plan_frames, d->T);
+    ConvParams p1 = p;              // the launch as ONE image's rows would make it (p itself where the field does not apply)
+    dat_conv_desc d1 = *d;
+    if (per_image) {
+        if (plan_on_w) { d1.W = d->plan_frames; p1.W = d1.W; dat_conv3d_out_shape(&d1, &p1.Ho, &p1.Wo); }
+        else { d1.frames = d->plan_frames; p1.frames = d->plan_frames / d->T * p.otn; }
+        d1.plan_frames = 0;
+    }
+    const int plan_passes = (per_image && !force_ks) ? 2 : 1;
     int ks_fixed = force_ks;
     for (int pass = 0; pass < plan_passes; ++pass) {
         const bool model_pass = plan_passes == 2 && pass == 0;
-        ConvParams pm = p;
-        if (model_pass) pm.frames = d->plan_frames;
+        ConvParams pm = model_pass ? p1 : p;
         const ConvParams& p = pm;       // (shadows the launch parameters inside the model)
         const int force_ks = ks_fixed;
         bp = 128; ksplit = 1;

@@ -26,6 +26,8 @@ class DatError(RuntimeError):
 
 
 class ConvDesc(C.Structure):
+    # (plan_frames: the rows ONE image contributes to a per-RoI blob of several images -- input frames, or positions along W for the
+    #  [1, 1, R, K] rows view of an FC layer, frames == 1 and H == 1; 0 = plan from the whole grid.  include/dat_hip.h)
     _fields_ = [(n, C.c_int) for n in (
         'dtype', 'frames', 'T', 'H', 'W', 'Cin', 'Cout', 'out_cstride', 'KT', 'KH', 'KW',
         'stride_h', 'stride_w', 'pad_t', 'pad_h', 'pad_w', 'relu', 'res_mode', 'out_t0', 'out_tn', 'in_t0', 'in_tn', 'plan_frames', 'dil_h', 'dil_w')]

@@ -473,6 +473,14 @@ class Executor(object):
                 torch.cuda.current_stream().synchronize()
         return self.ws._layers[k]
 
+    @staticmethod
+    def _rows_per_image(x, rows):
+        """dat_conv_desc.plan_frames of a conv-type launch over `rows` rows (frames; FC: matrix rows) of the blob `x`: 0, or -- a per-RoI
+        blob of several images (one live count per image over equal row segments) -- one image's rows.  The layer's split-K factor is
+        then the one of one image's rows, so that an image's head results do not depend on how many images share the forward."""
+        n_img = x.count.numel() if (x.roi and isinstance(x.count, torch.Tensor)) else 1
+        return rows // n_img if (n_img > 1 and rows % n_img == 0) else 0
+
     def _log_conv(self, name, layer, frames, H, W, oframes=None, res_mode=0):
         """(name, algorithmic flops, algorithmic HBM bytes) of one conv launch, for bench.py's roofline leg."""
         if self.ws.conv_log is not None:
@@ -504,7 +512,7 @@ class Executor(object):
             kf, tfull = xin.tsel
             assert a['kernels'][0] == 1 and res is None
             self._log_conv(op.outputs[0], layer, xin.t.shape[0], xin.t.shape[1], xin.t.shape[2], oframes=xin.N)
-            y = layer(xin.t, T=tfull, out_t=(kf, 1))
+            y = layer(xin.t, T=tfull, out_t=(kf, 1), plan_frames=self._rows_per_image(xin, xin.t.shape[0]))
             b = Blob(y, 'fmap', xin.N, 1, a['dim_out'], dt, False)
             b.count, b.roi = xin.count, xin.roi
             ws.blobs[op.outputs[0]] = b
@@ -512,7 +520,7 @@ class Executor(object):
         k = self._keyframe.get(op.outputs[0])
         if k is not None and xin.T > 1 and xin.keyframe is None and res is None:
             self._log_conv(op.outputs[0], layer, xin.t.shape[0], xin.t.shape[1], xin.t.shape[2], oframes=xin.N)
-            y = layer(xin.t, T=xin.T, out_t=(k, 1), x_split=self._split_of(xin, layer))
+            y = layer(xin.t, T=xin.T, out_t=(k, 1), x_split=self._split_of(xin, layer), plan_frames=self._rows_per_image(xin, xin.t.shape[0]))
             b = Blob(y, 'fmap', xin.N, 1, a['dim_out'], dt, False)
             b.keyframe = k
             ws.blobs[op.outputs[0]] = b
@@ -520,12 +528,8 @@ class Executor(object):
         assert xin.keyframe is None or a['kernels'][0] == 1, 'temporal conv on a key-frame-only blob'
         self._log_conv(op.outputs[0], layer, xin.t.shape[0], xin.t.shape[1], xin.t.shape[2],
                        res_mode=(a['res_mode'] or 1) if res is not None else 0)
-        # a per-RoI blob of several images (one count per image): the layer is planned for one image's rows, so that an image's head
-        # results do not depend on how many images share the forward
-        n_img = xin.count.numel() if (xin.roi and isinstance(xin.count, torch.Tensor)) else 1
-        per_image = xin.t.shape[0] // n_img if (n_img > 1 and xin.t.shape[0] % n_img == 0) else 0
         y = layer(xin.t, T=xin.T, residual=res, res_mode=a['res_mode'], x_split=self._split_of(xin, layer),
-                  want_split=layer.x3 and self._read_by_a_conv(op.outputs[0]), plan_frames=per_image)
+                  want_split=layer.x3 and self._read_by_a_conv(op.outputs[0]), plan_frames=self._rows_per_image(xin, xin.t.shape[0]))
         b = Blob(y, 'fmap', xin.N, xin.T, a['dim_out'], dt, xin.five_d)
         b.split = getattr(y, '_split', None)      # (bf16x3: written by this conv's epilogue for the convs that read the blob)
         b.keyframe = xin.keyframe
@@ -577,8 +581,10 @@ class Executor(object):
                                  cin_stride=xin.t.shape[3], x3=_x3(self.ws))
         layer = self._layer(i, build)
         self._log_conv(op.outputs[0], layer, xin.t.shape[0], xin.t.shape[1], xin.t.shape[2], oframes=xin.N)
-        y = layer(xin.t, T=T, out_t=(0, 1))
-        ws.blobs[op.outputs[0]] = Blob(y, 'fmap', xin.N, 1, a['dim_out'], dt, False)
+        y = layer(xin.t, T=T, out_t=(0, 1), plan_frames=self._rows_per_image(xin, xin.t.shape[0]))
+        b = Blob(y, 'fmap', xin.N, 1, a['dim_out'], dt, False)
+        b.count, b.roi = xin.count, xin.roi
+        ws.blobs[op.outputs[0]] = b
 
     def _stem(self, i, op, xin):
         ws, a, dt = self.ws, op.args, _dt(self.ws)
@@ -809,6 +815,7 @@ class Executor(object):
             return
         b = Blob(x.t, 'fmap', x.N, x.T, x.C, x.dt, False)
         b.t2c = True
+        b.count, b.roi = x.count, x.roi      # (the keypoint head's deconv over time-moved-to-channels plans for one image's rows)
         self.ws.blobs[op.outputs[0]] = b
 
     def op_SpatialMean(self, i, op):
@@ -958,7 +965,8 @@ class Executor(object):
                                  pads=(0, 0, 0), relu=a['relu'], dtype=dt, cin_stride=xin.shape[3], x3=_x3(self.ws))
         layer = self._layer(i, build)
         self._log_conv(op.outputs[0], layer, 1, 1, xin.shape[2])
-        y = layer(xin, T=1, zero_pad=not self._pad_unread(op.outputs[0]))
+        # (the rows lie on the W axis of the [1, 1, R, K] view: plan_frames counts them there, include/dat_hip.h)
+        y = layer(xin, T=1, zero_pad=not self._pad_unread(op.outputs[0]), plan_frames=self._rows_per_image(x, xin.shape[2]))
         b = Blob(y, 'rows', 1, 1, a['dim_out'], dt)
         b.count, b.roi = x.count, x.roi
         ws.blobs[op.outputs[0]] = b
@@ -990,8 +998,9 @@ class Executor(object):
         if ws.conv_log is not None:   # algorithmic flops of the deconv itself: 16 taps / 4 outputs per input position
             ws.conv_log.append((op.outputs[0], 2.0 * a['dim_in'] * a['dim_out'] * 16 * x.t.shape[0] * x.t.shape[1] * x.t.shape[2],
                                 layer.hbm_bytes(x.t.shape[0], x.t.shape[1], x.t.shape[2])))
-        y = layer(x.t, T=1, zero_pad=not self._pad_unread(op.outputs[0]))
+        y = layer(x.t, T=1, zero_pad=not self._pad_unread(op.outputs[0]), plan_frames=self._rows_per_image(x, x.t.shape[0]))
         b = Blob(y, 'fmap', x.N, x.T, 4 * a['dim_out'], dt, x.five_d)
+        b.count, b.roi = x.count, x.roi
         ws.blobs[op.outputs[0]] = b
 
     @staticmethod
@@ -1037,7 +1046,7 @@ class Executor(object):
             g = self._deconv_group(a, ws.dev_param(a['w']))
             ws.conv_log.append((op.outputs[0], 2.0 * a['dim_in'] * a['dim_out'] / g * 16 * x.N * x.t.shape[1] * x.t.shape[2],
                                 layer.hbm_bytes(x.t.shape[0], x.t.shape[1], x.t.shape[2], oframes=x.N)))
-        y = layer(x.t, T=T, out_t=(0, 1), zero_pad=not self._pad_unread(op.outputs[0]))
+        y = layer(x.t, T=T, out_t=(0, 1), zero_pad=not self._pad_unread(op.outputs[0]), plan_frames=self._rows_per_image(x, x.t.shape[0]))
         b = Blob(y, 'fmap', x.N, 1, 4 * a['dim_out'], dt, False)
         b.count, b.roi = x.count, x.roi
         ws.blobs[op.outputs[0]] = b

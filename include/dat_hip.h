@@ -108,9 +108,12 @@ typedef struct {
                                 indexed like the output */
     int in_t0, in_tn;        /* in_tn > 0: input frames outside [in_t0, in_t0+in_tn) of every clip are known to be ZERO (a key-frame
                                 gradient embedded in its temporal window): the temporal taps that would read them are skipped */
-    int plan_frames;         /* 0, or the frames (rows) ONE image contributes to a per-RoI blob that holds several images: dat_conv3d_fwd then
-                                picks the split-K factor it would pick for plan_frames frames, so that an image's results do not depend on how
-                                many images share the forward (the factor fixes the order of the fp32 partial sums).  0 or >= frames: frames */
+    int plan_frames;         /* 0, or the rows ONE image contributes to a per-RoI blob that holds several images: dat_conv3d_fwd then
+                                picks the split-K factor it would pick for that many rows, so that an image's results do not depend on how
+                                many images share the forward (the factor fixes the order of the fp32 partial sums).  The rows are input
+                                frames (a multiple of T; with an output-frame window the model counts plan_frames / T * out_tn output frames)
+                                -- or, for the [1, 1, R, K] rows view of an FC layer (frames == 1 and H == 1), map columns: plan_frames then
+                                counts positions along W.  0, or >= frames (>= W for the rows view): the whole grid */
     int dil_h, dil_w;        /* spatial dilation d (MODEL.DILATION): tap (kh, kw) reads x[oh + kh*d - pad_h, ow + kw*d - pad_w]; 0 and 1 both mean
                                 "not dilated" (zero-initialised descriptors keep their meaning).  d > 1 needs dil_h == dil_w, spatial stride 1
                                 and the dense entry points (the grouped ones refuse it); there is no temporal dilation.  A 1x1 spatial kernel

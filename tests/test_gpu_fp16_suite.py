@@ -3,8 +3,8 @@
 The 16-bit format belongs to the loaded library, so the format-generic kernel tests run again in ONE child process started with
 DAT_H16=fp16: tests/test_gpu_kernels.py, tests/test_gpu_fp16_edges.py, tests/test_gpu_infer_kernels.py, tests/test_gpu_wgrad.py (the
 weight-gradient kernels), tests/test_gpu_temporal_windows.py (the conv frame windows), tests/test_gpu_weight_pack.py and tests/test_gpu_dgrad.py (the weight
-packers and the dense data gradient), tests/test_gpu_proposals.py (proposal selection, collect and the detection limit at their tie edges) and
-the persistent-kernel test of tests/test_gpu_model.py.
+packers and the dense data gradient), tests/test_gpu_proposals.py (proposal selection, collect and the detection limit at their tie edges),
+tests/test_gpu_batch_invariance.py (an image's head results do not depend on its batch) and the persistent-kernel test of tests/test_gpu_model.py.
 The parent reads the child's JUnit report: no failure or error, every skip is a bf16-only test, and one test per kernel family (plus
 the NMS and proposal goldens) is among the passed -- so that a collection mistake cannot pass for a green run.  The child is never
 retried."""
@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_FILES = ['tests/test_gpu_kernels.py', 'tests/test_gpu_fp16_edges.py', 'tests/test_gpu_infer_kernels.py', 'tests/test_gpu_wgrad.py',
                'tests/test_gpu_temporal_windows.py', 'tests/test_gpu_weight_pack.py', 'tests/test_gpu_dgrad.py', 'tests/test_gpu_proposals.py',
-               'tests/test_gpu_model.py::test_persistent_kernel_cu_share_does_not_change_results']
+               'tests/test_gpu_model.py::test_persistent_kernel_cu_share_does_not_change_results', 'tests/test_gpu_batch_invariance.py']
 
 K = 'tests.test_gpu_kernels::'
 E = 'tests.test_gpu_fp16_edges::'
@@ -30,6 +30,7 @@ W = 'tests.test_gpu_temporal_windows::'
 P = 'tests.test_gpu_weight_pack::'
 D = 'tests.test_gpu_dgrad::'
 R = 'tests.test_gpu_proposals::'
+B = 'tests.test_gpu_batch_invariance::'
 MUST_PASS = [
     K + 'test_layout_roundtrip[1]',
     K + 'test_conv3d[3x3x3-bf16]',                                   # generic kernel + the split-K finish
@@ -91,6 +92,11 @@ MUST_PASS = [
     D + 'test_zero_insertion_3x3x3_stride2[k333_s2_13x16]',
     D + 'test_weights_in_lds_1x1',
     R + 'test_16_bit_head',                                                     # proposals from a 16-bit head: equal keys, exact order
+    B + 'test_rows_of_an_image_in_a_batched_launch_equal_the_launch_alone[kps_conv3x3_512-20-2-h16]',   # per-RoI layers planned for one image's rows
+    B + 'test_rows_of_an_image_in_a_batched_launch_equal_the_launch_alone[fc6-300-4-h16]',               # ... with the rows on W
+    B + 'test_table_can_fail[deconv_subpixel]',
+    B + 'test_heads_on_one_image_of_a_batch_equal_the_heads_alone[r18_fpn3d-4-h16]',                      # the heads as the executor runs them, fp16 blobs
+    B + 'test_a_clip_does_not_depend_on_its_companion_or_its_slot[c4_tube_gn]',
 ]
 
 
