@@ -95,7 +95,8 @@ def test_bf16_clip_graph_replay_equals_eager():
     from detectandtrack_amd.core.clip_graph import ClipGraph
     from detectandtrack_amd.core.config import cfg
     from detectandtrack_amd.ops import hip_ops as ops
-    model, ws, _ = build_product(dr.c5_dilated_cfg('18', T=T, dilation=2, pre=PRE, post=POST, dtype='bf16'))
+    mode = 'fp16' if ops.H16_DTYPE == torch.float16 else 'bf16'         # (the loaded build's 16-bit mode)
+    model, ws, _ = build_product(dr.c5_dilated_cfg('18', T=T, dilation=2, pre=PRE, post=POST, dtype=mode))
     cfg.TEST.SCORE_THRESH = 0.0
     im_info = np.array([[H, W, 1.0]], dtype=np.float32)
     clips = [torch.from_numpy(synthetic_clip(T, H, W, seed=s)).cuda() for s in (3, 4)]

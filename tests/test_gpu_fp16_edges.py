@@ -2,25 +2,35 @@
 IEEE half under DAT_H16=fp16, tests/test_gpu_fp16_suite.py): fp32 sums beyond the half range that an affine scale brings back,
 outputs that saturate, subnormal operands and outputs, and the exactness of the fp32 -> 16-bit layout conversion.  Each conv edge
 runs through the planner's kernel choice, a forced split-K plan, and on shapes that select the weights-stationary 3x3 (ws64), the
-big-tile 3x3, the weights-in-LDS 1x1 (lw) and the K-streaming 1x1 (ks) kernels; every expectation is stated per format."""
+big-tile 3x3, the weights-in-LDS 1x1 (lw) and the K-streaming 1x1 (ks) kernels, the grouped 3x3 kernel (two 64-channel slabs of 16
+groups) and the dilated 3x3 path of the generic kernel (dilation 2 on a 5 x 5 map: the smallest with an interior output, and the -2
+taps leave it on one side, the +2 taps on the other); every expectation is stated per format.  The operand sets and the checks live
+in tests/fp16_edge_cases.py, where tests/test_fp16_edges_cpu.py holds them against simulated defects without a GPU."""
 import numpy as np
 import pytest
 import torch
 
+from tests import fp16_edge_cases as fe
 from tests import numerics as nm
+from tests.dilated_ref import inflate
+from tests.grouped_ref import grouped_conv_ref64
 from tests.test_gpu_kernels import _dev, _in_fresh_context
 
 pytestmark = pytest.mark.gpu
 
-# name: (kernel taps, Cin, Cout, frames, H, W, environment, forced plan, the kernel's profiler tag or None)
+# name: (kernel taps, Cin, Cout, frames, H, W, environment, forced plan, the kernel's profiler tag(s) or None, groups, dilation)
 SELECT = {
-    'plan_3x3x3': ((3, 3, 3), 64, 128, 3, 14, 18, {}, None, None),
-    'splitk_3x3x3': ((3, 3, 3), 64, 128, 3, 14, 18, {}, (128, 2), None),
-    'splitk_1x1': ((1, 1, 1), 64, 128, 2, 12, 20, {}, (128, 2), None),
-    'ws64_3x3': ((1, 3, 3), 64, 64, 2, 37, 53, {}, None, None),                      # tests/test_gpu_kernels.py WS64_CASES
-    'big_tile_3x3': ((1, 3, 3), 64, 256, 4, 120, 256, {'DAT_CONV_BT': '2'}, None, None),  # BT_CASES '2d_8x32_tiles'
-    'lw_1x1': ((1, 1, 1), 64, 64, 2, 192, 200, {}, None, 2560331),                     # LW_CASES 'k64_c64'
-    'ks_1x1': ((1, 1, 1), 1024, 256, 2, 192, 200, {}, None, 2560341),                  # KS_CASES 'k1024_c256'
+    'plan_3x3x3': ((3, 3, 3), 64, 128, 3, 14, 18, {}, None, None, 1, 1),
+    'splitk_3x3x3': ((3, 3, 3), 64, 128, 3, 14, 18, {}, (128, 2), None, 1, 1),
+    'splitk_1x1': ((1, 1, 1), 64, 128, 2, 12, 20, {}, (128, 2), None, 1, 1),
+    'ws64_3x3': ((1, 3, 3), 64, 64, 2, 37, 53, {}, None, None, 1, 1),                      # tests/test_gpu_kernels.py WS64_CASES
+    'big_tile_3x3': ((1, 3, 3), 64, 256, 4, 120, 256, {'DAT_CONV_BT': '2'}, None, None, 1, 1),  # BT_CASES '2d_8x32_tiles'
+    'lw_1x1': ((1, 1, 1), 64, 64, 2, 192, 200, {}, None, 2560331, 1, 1),                     # LW_CASES 'k64_c64'
+    'ks_1x1': ((1, 1, 1), 1024, 256, 2, 192, 200, {}, None, 2560341, 1, 1),                  # KS_CASES 'k1024_c256'
+    # tests/test_gpu_grouped_conv.py CASES 'c128_g32x4_1x3x3', one clip: the grouped kernel's tag on 16-bit tensors, as that file asserts it
+    'grouped_3x3': ((1, 3, 3), 128, 128, 1, 19, 23, {}, None, 642571, 32, 1),
+    # the generic kernel with the dilated mark (tests/test_gpu_dilated_conv.py): 64 channels per block, 128 or 256 positions
+    'dilated_3x3': ((1, 3, 3), 64, 64, 2, 5, 5, {}, None, (641286, 642566), 1, 2),
 }
 IDS = sorted(SELECT)
 
@@ -35,9 +45,10 @@ def ops():
 def _conv(ops, sel, x, w, scale, bias):
     """The conv of SELECT[sel] on fp32 operands (quantised to the build's format by the layout conversion and the weight pack);
     returns the stored 16-bit output as (1, Cout, T, H, W) and the float64 (ref, absref)."""
-    k, cin, cout, T, H, W, env, plan, tag = SELECT[sel]
-    pads = (k[0] // 2, k[1] // 2, k[2] // 2)
-    layer = ops.ConvLayer(_dev(w), _dev(scale), _dev(bias), stride=(1, 1), pads=pads, relu=False, dtype=ops.BF16)
+    k, cin, cout, T, H, W, env, plan, tag, groups, dil = SELECT[sel]
+    pads = (k[0] // 2, dil * (k[1] // 2), dil * (k[2] // 2))
+    layer = ops.ConvLayer(_dev(w), _dev(scale), _dev(bias), stride=(1, 1), pads=pads, relu=False, dtype=ops.BF16, groups=groups,
+                          dilation=dil)
     xd = ops.to_ndhwc(_dev(x), ops.BF16)
 
     def run():
@@ -51,37 +62,41 @@ def _conv(ops, sel, x, w, scale, bias):
         finally:
             ops.tune_plan(0, 0)
         if tag is not None:
-            assert [t for t, _, _ in rec] == [tag], 'the layer did not take the %s kernel: tags %r' % (sel, [t for t, _, _ in rec])
+            tags = [t for t, _, _ in rec]
+            assert len(tags) == 1 and tags[0] in (tag if isinstance(tag, tuple) else (tag,)), \
+                'the layer did not take the %s kernel: tags %r' % (sel, tags)
         return y_
     y = _in_fresh_context(env, run) if env else run()
     assert y.dtype == nm.h16()
     got = y[..., :cout].reshape(1, T, H, W, cout).permute(0, 4, 1, 2, 3).cpu()
-    ref64, abs64 = nm.conv_ref64(nm.q16(x), nm.q16(w), scale, bias, None, (1, 1), pads)
+    # float64: per-group dense convs (tests/grouped_ref.py; one group: numerics.conv_ref64 itself) of the zero-inflated filter
+    # (tests/dilated_ref.py; dilation 1: the filter itself)
+    ref64, abs64 = grouped_conv_ref64(nm.q16(x), inflate(nm.q16(w), dil), groups, scale, bias, None, (1, 1), pads)
     return got, ref64, abs64
 
 
 def _shape(sel):
+    """(taps, reduction length K = Cin / groups x taps, Cout, shape of x, shape of w)"""
     k, cin, cout, T, H, W = SELECT[sel][:6]
-    return k, cin, cout, (1, cin, T, H, W), (cout, cin) + k
+    groups = SELECT[sel][9]
+    return k, nm.conv_k(cin // groups, k), cout, (1, cin, T, H, W), (cout, cin // groups) + k
+
+
+def _interior(sel):
+    """Index of the outputs whose every tap lies inside the clip."""
+    k, dil = SELECT[sel][0], SELECT[sel][10]
+    hw = slice(dil, -dil) if k[1] == 3 else slice(None)
+    return (slice(None), slice(None), slice(1, -1) if k[0] == 3 else slice(None), hw, hw)
 
 
 @pytest.mark.parametrize('sel', IDS)
 def test_sums_beyond_the_half_range_brought_back_by_the_affine_scale(ops, sel):
     """Non-negative activations and mostly positive weights: the fp32 sums reach ~4 x 65504, the affine scale 1/16 brings the outputs
     back into the half range.  Finite outputs within the per-element bound: no 16-bit partial sum, split-K partial or staging copy."""
-    k, cin, cout, xs, ws = _shape(sel)
-    K = nm.conv_k(cin, k)
-    rs = np.random.RandomState(K + cout)
-    a = np.sqrt(262144.0 / K)
-    x = (rs.uniform(0.5, 1.5, xs) * a).astype(np.float32)
-    w = (rs.uniform(0.5, 1.5, ws) * a * np.where(rs.uniform(size=ws) < 0.1, -1.0, 1.0)).astype(np.float32)
-    scale = np.full(cout, 1.0 / 16, np.float32)
-    bias = (rs.randn(cout) * 4).astype(np.float32)
+    k, K, cout, xs, ws = _shape(sel)
+    x, w, scale, bias = fe.conv_large_sums_operands(K, cout, xs, ws)
     got, ref64, abs64 = _conv(ops, sel, x, w, scale, bias)
-    assert (np.abs(ref64 - bias.reshape(1, -1, 1, 1, 1)) * 16).max() > 2 * 65504, 'the sums do not leave the half range'
-    assert np.abs(ref64).max() < 65504 / 2
-    assert torch.isfinite(got).all()
-    nm.assert_elementwise(got, ref64, abs64, K, nm.h16(), 'large sums ' + sel)
+    fe.check_conv_large_sums(got, ref64, abs64, bias, K, nm.h16(), sel)
 
 
 @pytest.mark.parametrize('sel', IDS)
@@ -89,26 +104,11 @@ def test_outputs_beyond_the_range_saturate_with_round_to_nearest_even(ops, sel):
     """Every product is 64 * 64 and every sum an exact fp32 integer, so the kernel's fp32 value is sum * scale rounded once; per
     output channel the scale puts the interior outputs at 65504, 65519, 65520, -65520, 65535, 2^17 ...  The stored output equals torch's
     conversion of that fp32 value: fp16 rounds to nearest even (65519 -> 65504, >= 65520 -> +-inf); bf16 keeps them finite."""
-    k, cin, cout, xs, ws = _shape(sel)
-    x = np.full(xs, 64.0, np.float32)
-    w = np.full(ws, 64.0, np.float32)
-    interior = float(nm.conv_k(cin, k) * 64 * 64)                 # the sum of an interior output (all taps inside the map)
-    targets = np.array([65504, 65519, 65520, -65520, 65535, -65519, 131072, 60000, -70000, 1.0e6, 32768, 65520.5], np.float64)
-    scale = (targets[np.arange(cout) % len(targets)] / interior).astype(np.float32)
-    bias = np.zeros(cout, np.float32)
+    k, K, cout, xs, ws = _shape(sel)
+    x, w, scale, bias = fe.conv_saturation_operands(K, cout, xs, ws)
     got, ref64, _ = _conv(ops, sel, x, w, scale, bias)
-    # the kernel's fp32 result: the exact sum times the fp32 scale, one fp32 rounding (bias 0 adds nothing)
-    sums = ref64 / scale.astype(np.float64).reshape(1, -1, 1, 1, 1)
-    want32 = (torch.from_numpy(np.rint(sums).astype(np.float32)) * torch.from_numpy(scale).view(1, -1, 1, 1, 1))
-    want = want32.to(nm.h16())
-    inner = (slice(None), slice(None), slice(1, -1) if k[0] == 3 else slice(None), slice(1, -1), slice(1, -1))
-    if nm.h16() == torch.float16:
-        assert torch.isinf(got[inner]).any() and (got[inner] == 65504).any(), 'no saturated / clamped interior outputs'
-    else:
-        assert torch.isfinite(got).all()
-    bad = got.float() != want.float()
-    assert not bad.any(), '%s: %d outputs differ from torch\'s rounding, e.g. got %r want %r' % (
-        sel, int(bad.sum()), got[bad][:4].tolist(), want[bad][:4].tolist())
+    # (the sum of an interior output, all taps inside the map: K * 64 * 64)
+    fe.check_conv_saturation(got, ref64, scale, float(K * 64 * 64), _interior(sel), nm.h16(), sel)
 
 
 @pytest.mark.parametrize('sel', IDS)
@@ -116,23 +116,11 @@ def test_subnormal_operands_and_outputs(ops, sel):
     """Activations and weights are small multiples of 2^-24 (fp16 subnormals; normal in bf16) -- converted by the layout kernel and the
     weight pack -- and the scales 2^19 .. 2^21 put the outputs in the half format's subnormal range.  Every product and sum is exact
     in fp32, so the stored output must equal torch's rounding of the exact result: subnormals kept, ties to even, no flush to zero."""
-    k, cin, cout, xs, ws = _shape(sel)
-    rs = np.random.RandomState(nm.conv_k(cin, k) + 3)
-    x = (rs.randint(-15, 16, xs) * 2.0 ** -24).astype(np.float32)
-    w = (rs.randint(-15, 16, ws) * 2.0 ** -24).astype(np.float32)
-    scale = (2.0 ** rs.randint(19, 22, cout)).astype(np.float32)
-    bias = np.zeros(cout, np.float32)
+    k, K, cout, xs, ws = _shape(sel)
+    x, w, scale, bias = fe.conv_subnormal_operands(K, cout, xs, ws)
     np.testing.assert_array_equal(nm.q16(x), x)                  # (representable in both formats: the pack and the layout are exact)
     got, ref64, abs64 = _conv(ops, sel, x, w, scale, bias)
-    want = torch.from_numpy(ref64).to(nm.h16())                  # exact in fp32, so one rounding of the exact value
-    if nm.h16() == torch.float16:
-        sub = (want != 0) & (want.abs() < 2.0 ** -14)
-        assert sub.float().mean() > 0.3, 'too few subnormal outputs: %.3f' % sub.float().mean()
-        assert (got[sub] != 0).all(), 'subnormal outputs flushed to zero'
-    bad = got.float() != want.float()
-    assert not bad.any(), '%s: %d of %d outputs differ from torch\'s rounding, e.g. got %r want %r' % (
-        sel, int(bad.sum()), bad.numel(), got[bad][:4].tolist(), want[bad][:4].tolist())
-    nm.assert_elementwise(got, ref64, abs64, nm.conv_k(cin, k), nm.h16(), 'subnormals ' + sel)
+    fe.check_conv_subnormals(got, ref64, abs64, K, nm.h16(), sel)
 
 
 def test_layout_conversion_is_torch_rounding_bit_for_bit(ops):

@@ -8,6 +8,9 @@ format.  The references and bounds are those of tests/group_norm_ref.py with N =
     bit-identical across two calls.
 Shapes: the issue's cases, plus one per register-resident instantiation of the kernels (row slots 4 / 7 / 10 / 13 / 20), the split of a
 large RoI into channel slabs (with a slab that is half or all padding), the re-reading path and the stride limit 2048.  Padding channels of every input hold junk.  Every test prints its worst err / bound.
+
+Edges of the 16-bit formats (tests/fp16_edge_cases.py) on `two_per_group`, in fp32 and the build's 16-bit format: inputs in the fp16
+subnormal range, outputs on and beyond the largest finite half, a mean of 3e4.
 """
 import ctypes
 
@@ -15,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import fp16_edge_cases as fe
 from tests import numerics as nm
 from tests import group_norm_ref as ref
 
@@ -327,3 +331,82 @@ def test_argument_errors_launch_nothing(ops, dtype_name):
         bwd(ws_bytes=ws.numel() - 1)
     torch.cuda.synchronize()
     assert torch.all(y == 3.0) and torch.all(mean == 5.0) and torch.all(sums == 7.0) and torch.all(dbeta == 9.0)
+
+
+# ---- edges of the 16-bit formats (operands and expectations: tests/fp16_edge_cases.py), on the smallest case ---------------------------------
+EDGE = 'two_per_group'
+SENTINEL = 77.0
+
+
+def _edge_forward(ops, dtype_name, z, s, b, eps, what, exact=None):
+    """The fused forward on one edge input ([R, M, C], already in the tensor format) written between two sentinel RoIs: mean / rstd inside
+    `table_bounds` (exact: equal to these tables), the rows outside the output untouched.  -> (tables, y [R, M, C] tensor, its check)"""
+    R, f, H, W, C, cs, G = CASES[EDGE]
+    dt, fmt = _dt(ops, dtype_name), _fmt(dtype_name)
+    s64, b64 = s.astype(np.float64), b.astype(np.float64)
+    tables, dtables = ref.table_bounds(z, G, s64, b64, eps)
+    zd = _dev(z, CASES[EDGE], dtype_name)
+    big = torch.full((R * f + 2, H, W, cs), SENTINEL, dtype=torch.float32).to(fmt).cuda()
+    y, mean, rstd = ops.gn_roi_fwd(zd, dt, C, G, _vec(s), _vec(b), eps, R=R, out=big[1:1 + R * f])
+    torch.cuda.synchronize()
+    assert torch.all(big[0] == SENTINEL) and torch.all(big[-1] == SENTINEL), 'rows outside the output were written'
+    ratios = []
+    for got, k, label in ((mean, 0, 'mean'), (rstd, 1, 'rstd')):
+        if exact is not None:
+            assert np.array_equal(_per_channel(got, C), np.broadcast_to(exact[k].astype(np.float64), (R, C))), 'the table %s is not exact' % label
+        err, bd = np.abs(_per_channel(got, C) - tables[k]), dtables[k]
+        ratios.append(_worst(err, bd))
+        assert np.all(err <= bd), '%s %s: worst err/bound %.3g' % (what, label, ratios[-1])
+    yv, ypad = _host(y, R, C)
+    assert np.all(ypad == 0)
+    check = lambda: ref.check_forward(yv, z, G, s64, b64, eps, fmt, '%s y' % what)
+    return tables, y[..., :C].reshape(R, -1, C).cpu(), ratios, check
+
+
+@pytest.mark.parametrize('dtype_name', ['fp32', 'h16'])
+def test_subnormal_inputs_give_normal_outputs(ops, dtype_name):
+    """Every z is k 2^-24, |k| < 1024: fp16 subnormals (exact) in the fp16 build's 16-bit mode, ordinary normals in bf16 (rounded to 8 bits)
+    and fp32.  rstd ~ eps^-1/2 and the outputs are normal numbers around 1e-2 inside the forward bound; a kernel that flushes subnormal
+    loads returns zeros."""
+    R, f, H, W, C, cs, G = CASES[EDGE]
+    z, s, b = fe.gn_subnormal_case(R, f * H * W, C)
+    if dtype_name == 'h16':
+        z = nm.q16(z)
+        if nm.h16() == torch.float16:
+            assert np.array_equal(z, fe.gn_subnormal_case(R, f * H * W, C)[0]) and np.all(np.abs(z) < 2.0 ** -14)
+        else:
+            assert np.all((z == 0) | (np.abs(z) >= 2.0 ** -126))
+    tables, y, ratios, check = _edge_forward(ops, dtype_name, z, s, b, EPS, 'subnormal inputs')
+    w = check()
+    print('subnormal inputs %s: err/bound mean %.3f rstd %.3f y %.3f' % (dtype_name, ratios[0], ratios[1], w))
+    assert np.all(tables[1] > 0.99 / np.sqrt(EPS))
+    y = y.double().numpy()
+    assert (y != 0).mean() > 0.95 and np.median(np.abs(y)) > 1e-3, 'the outputs vanished: subnormal inputs flushed to zero'
+
+
+@pytest.mark.parametrize('dtype_name', ['fp32', 'h16'])
+def test_saturating_outputs_are_the_conversion_of_the_fp32_value(ops, dtype_name):
+    """A group of the two values +1, -1 and eps = 3: mean 0 and rstd 1/2 exactly (asserted), a = s / 2, b' = b, and the fp32 value
+    z a + b' is exactly the channel's target (65504, 65519, 65520, -65520, 2^17, ...).  The stored output equals torch's conversion: +-inf
+    at and beyond 65520 in fp16, finite in bf16 and fp32; the RoIs before and behind the output keep their sentinel."""
+    R, f, H, W, C, cs, G = CASES[EDGE]
+    z, s, b, eps, want32, exact = fe.gn_saturation_case(R, f * H * W, C, G)
+    assert eps == 3.0 and (dtype_name != 'h16' or np.array_equal(nm.q16(z), z))
+    _, y, _, _ = _edge_forward(ops, dtype_name, z, s, b, eps, 'saturation', exact=exact)
+    fe.check_gn_saturation(y, want32, _fmt(dtype_name), '%s %s' % (EDGE, dtype_name))
+
+
+@pytest.mark.parametrize('dtype_name', ['fp32', 'h16'])
+def test_a_mean_near_the_top_of_the_half_range(ops, dtype_name):
+    """z = 3e4 + N(0, 100^2) rounded to the tensor format: mean, rstd and y inside the bounds of the other forward tests (not vacuous
+    in fp32 and fp16: tests/test_fp16_edges_cpu.py).  Left out in bf16: its spacing at 3e4 is 128, the two values of a group are often
+    equal, the variance is 0, and the bound of y grows to 40 times |y| (the same CPU test) -- a check that could not fail."""
+    R, f, H, W, C, cs, G = CASES[EDGE]
+    if dtype_name == 'h16' and nm.h16() == torch.bfloat16:
+        pytest.skip('fp16 build only: with two bf16 values per group near 3e4 the bound is vacuous')
+    z, s, b = fe.gn_high_mean_case(R, f * H * W, C)
+    z = nm.q16(z) if dtype_name == 'h16' else z
+    assert np.isfinite(z).all() and z.min() > 2.9e4
+    _, _, ratios, check = _edge_forward(ops, dtype_name, z, s, b, EPS, 'high mean')
+    w = check()
+    print('high mean %s: err/bound mean %.3f rstd %.3f y %.3f' % (dtype_name, ratios[0], ratios[1], w))

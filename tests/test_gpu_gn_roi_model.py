@@ -98,7 +98,9 @@ def test_c4_bf16_graph_replay_equals_eager():
     from detectandtrack_amd.core import test as engine
     from detectandtrack_amd.core.clip_graph import ClipGraph
     from detectandtrack_amd.core.config import cfg
-    model, ws, _ = build_product(_c4_cfg('bf16'))
+    from detectandtrack_amd.ops import hip_ops
+    mode = 'fp16' if hip_ops.H16_DTYPE == torch.float16 else 'bf16'     # (the loaded build's 16-bit mode)
+    model, ws, _ = build_product(_c4_cfg(mode))
     cfg.TEST.SCORE_THRESH = 0.0
     im_info = np.array([[H, W, 1.0]], dtype=np.float32)
     clips = [torch.from_numpy(synthetic_clip(T_C4, H, W, seed=s)).cuda() for s in (3, 4, 5)]

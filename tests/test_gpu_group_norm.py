@@ -13,11 +13,16 @@ Bounds (derived in tests/group_norm_ref.py, from `numerics.sum_bound` / `numeric
     from the sums the kernel returned: the group coefficients q, r carry the sum bound of their cg-term sums A, B, and dz is held to
     K = 3 on absref = |a g| + |q| + |r (z - mu)| with extra = d_q + |z - mu| d_r.
 Every test prints its worst err / bound.
+
+Edges of the 16-bit formats (tests/fp16_edge_cases.py), in fp32 and the build's 16-bit format on `two_per_group` and `straddle`: inputs
+in the fp16 subnormal range, outputs on and beyond the largest finite half (exact tables, so the stored value is torch's conversion
+of a known fp32 value), and a mean of 3e4.
 """
 import numpy as np
 import pytest
 import torch
 
+from tests import fp16_edge_cases as fe
 from tests import numerics as nm
 from tests import group_norm_ref as ref
 
@@ -276,3 +281,92 @@ def test_unsupported_backward_shapes_are_argument_errors_and_launch_nothing(ops,
         ops.gn_stats(torch.zeros((1, 1, 1, 64), device='cuda').to(fmt), dt, 64, 64, one, one, EPS, clips=1)
     torch.cuda.synchronize()
     assert torch.all(dy == 3.0) and torch.all(dbeta == 7.0) and torch.all(dgamma == 9.0)
+
+
+# ---- edges of the 16-bit formats (operands and expectations: tests/fp16_edge_cases.py) ------------------------------------------------------
+EDGE_CASES = ['two_per_group', 'straddle']     # a group inside one thread's vector; groups that straddle the chunks, padding channels
+SENTINEL = 77.0
+
+
+def _edge_forward(ops, name, dtype_name, z, s, b, eps, what):
+    """stats + apply of one edge input ([clips, M, C], already in the tensor format): the tables inside `table_bounds`, y inside
+    `check_forward`, zero padding channels, and the rows before and behind the output untouched.  -> (tables, y [clips, M, C] tensor)"""
+    N, f, H, W, C, cs, G = CASES[name]
+    dt, fmt = _dt(ops, dtype_name), _fmt(dtype_name)
+    s64, b64 = s.astype(np.float64), b.astype(np.float64)
+    tables, dtables = ref.table_bounds(z, G, s64, b64, eps)
+    zd = _dev(z, CASES[name], dtype_name)
+    st = ops.gn_stats(zd, dt, C, G, _vec(s), _vec(b), eps, clips=N)
+    got = st.cpu().numpy().astype(np.float64)
+    ratios = []
+    for k, label in enumerate(('mean', 'rstd', 'a', "b'")):
+        err, bd = np.abs(got[k, :, :C] - tables[k]), dtables[k]
+        ratios.append(_worst(err, bd))
+        assert np.all(err <= bd), '%s %s %s: worst err/bound %.3g' % (what, name, label, ratios[-1])
+    big = torch.full((N * f + 2, H, W, cs), SENTINEL, dtype=torch.float32).to(fmt).cuda()
+    y = ops.gn_apply(zd, dt, C, st[2], st[3], clips=N, out=big[1:1 + N * f])
+    torch.cuda.synchronize()
+    assert torch.all(big[0] == SENTINEL) and torch.all(big[-1] == SENTINEL), 'rows outside the output were written'
+    yv, ypad = _host(y, N, C)
+    assert np.all(ypad == 0), 'padding channels of y are not zero'
+    w1 = ref.check_forward(yv, z, G, s64, b64, eps, fmt, '%s %s y' % (what, name))
+    print('%s %s %s: err/bound mean %.3f rstd %.3f a %.3f b\' %.3f y %.3f' % ((what, name, dtype_name) + tuple(ratios) + (w1,)))
+    return tables, y[..., :C].reshape(N, -1, C).cpu()
+
+
+@pytest.mark.parametrize('dtype_name', ['fp32', 'h16'])
+@pytest.mark.parametrize('name', EDGE_CASES)
+def test_subnormal_inputs_give_normal_outputs(ops, name, dtype_name):
+    """Every z is k 2^-24, |k| < 1024: in the fp16 build's 16-bit mode all of them are subnormals (and exact); in bf16 they are ordinary
+    normals rounded to 8 bits, in fp32 exact normals.  The variance (~1e-9) is far below eps, rstd ~ eps^-1/2, and the outputs
+    s (z - mu) rstd are normal numbers around 1e-2 held to the forward bound; a kernel that flushes subnormal loads returns zeros."""
+    N, f, H, W, C, cs, G = CASES[name]
+    z, s, b = fe.gn_subnormal_case(N, f * H * W, C)
+    if dtype_name == 'h16':
+        z = nm.q16(z)
+        if nm.h16() == torch.float16:
+            assert np.array_equal(z, fe.gn_subnormal_case(N, f * H * W, C)[0]) and np.all(np.abs(z) < 2.0 ** -14)
+        else:
+            assert np.all((z == 0) | (np.abs(z) >= 2.0 ** -126))
+    assert (z != 0).mean() > 0.99
+    tables, y = _edge_forward(ops, name, dtype_name, z, s, b, EPS, 'subnormal inputs')
+    assert np.all(tables[1] > 0.99 / np.sqrt(EPS))
+    y = y.double().numpy()
+    assert (y != 0).mean() > 0.99 and np.median(np.abs(y)) > 1e-3, 'the outputs vanished: subnormal inputs flushed to zero'
+
+
+@pytest.mark.parametrize('dtype_name', ['fp32', 'h16'])
+@pytest.mark.parametrize('name', EDGE_CASES)
+def test_saturating_outputs_are_the_conversion_of_the_fp32_value(ops, name, dtype_name):
+    """Constant channels +1, -1, 0, ... per group and eps = 4 - var: every table is exact (mean 0, rstd 1/2, a = s / 2, b' = b) -- asserted --
+    and the fp32 value z a + b' is exactly the channel's target (65504, 65519, 65520, -65520, 2^17, ...).  The stored output equals torch's
+    conversion: +-inf at and beyond 65520 in fp16, finite in bf16 and fp32.  The padding channels of z hold 1000 (times a = 2e6 it would
+    overflow every format) and come out as zeros; the rows before and behind the output keep their sentinel."""
+    N, f, H, W, C, cs, G = CASES[name]
+    z, s, b, eps, want32, exact = fe.gn_saturation_case(N, f * H * W, C, G)
+    if dtype_name == 'h16':
+        assert np.array_equal(nm.q16(z), z)
+    dt, fmt = _dt(ops, dtype_name), _fmt(dtype_name)
+    zd = _dev(z, CASES[name], dtype_name)
+    st = ops.gn_stats(zd, dt, C, G, _vec(s), _vec(b), eps, clips=N)
+    got = st.cpu().numpy()
+    for k, label in enumerate(('mean', 'rstd', 'a', "b'")):
+        assert np.array_equal(got[k, :, :C], np.broadcast_to(exact[k], (N, C))), '%s: the table %s is not exact' % (name, label)
+    big = torch.full((N * f + 2, H, W, cs), SENTINEL, dtype=torch.float32).to(fmt).cuda()
+    y = ops.gn_apply(zd, dt, C, st[2], st[3], clips=N, out=big[1:1 + N * f])
+    torch.cuda.synchronize()
+    assert torch.all(big[0] == SENTINEL) and torch.all(big[-1] == SENTINEL), 'rows outside the output were written'
+    assert torch.all(y[..., C:] == 0), 'padding channels of y are not zero'
+    fe.check_gn_saturation(y[..., :C].reshape(N, -1, C).cpu(), want32, fmt, '%s %s' % (name, dtype_name))
+
+
+@pytest.mark.parametrize('dtype_name', ['fp32', 'h16'])
+@pytest.mark.parametrize('name', EDGE_CASES)
+def test_a_mean_near_the_top_of_the_half_range(ops, name, dtype_name):
+    """z = 3e4 + N(0, 100^2) rounded to the tensor format (fp16: multiples of 16, bf16: of 128): statistics and outputs inside the
+    bounds of the other forward tests.  They are not vacuous here: tests/test_fp16_edges_cpu.py shows bound / |ref| of y below 1."""
+    N, f, H, W, C, cs, G = CASES[name]
+    z, s, b = fe.gn_high_mean_case(N, f * H * W, C)
+    z = nm.q16(z) if dtype_name == 'h16' else z
+    assert np.isfinite(z).all() and z.min() > 2.9e4
+    _edge_forward(ops, name, dtype_name, z, s, b, EPS, 'high mean')

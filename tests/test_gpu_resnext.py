@@ -60,8 +60,10 @@ def test_bf16_clip_graph_replay_equals_eager():
     from detectandtrack_amd.core import test as engine
     from detectandtrack_amd.core.clip_graph import ClipGraph
     from detectandtrack_amd.core.config import cfg
+    from detectandtrack_amd.ops import hip_ops
     T, H, W = 3, 128, 160
-    model, ws, _ = build_product(_cfg(T=T, dtype='bf16', pre=300, post=100))
+    mode = 'fp16' if hip_ops.H16_DTYPE == torch.float16 else 'bf16'     # (the loaded build's 16-bit mode)
+    model, ws, _ = build_product(_cfg(T=T, dtype=mode, pre=300, post=100))
     cfg.TEST.SCORE_THRESH = 0.0
     im_info = np.array([[H, W, 1.0]], dtype=np.float32)
     clips = [torch.from_numpy(synthetic_clip(T, H, W, seed=s)).cuda() for s in (3, 4)]
