@@ -26,6 +26,35 @@ int dat_ensure_ws(dat_ctx* ctx, size_t bytes) {
     return DAT_OK;
 }
 
+// the launch-plan and debug knobs of a context, from the environment (dat_ctx_create; dat_conv3d_plan without a context)
+void dat_ctx_read_env(dat_ctx* c) {
+    auto env_int = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    c->force_bp = env_int("DAT_CONV_BP", 0);
+    c->force_ks = env_int("DAT_CONV_KSPLIT", 0);
+    c->dbg_ablate = env_int("DAT_CONV_ABLATE", 0);
+    c->dbg_ntap = env_int("DAT_CONV_NTAP", 1);   // 0 off, 1 default rule; bit 1 (2/3): unrolled 1x1 variant for every 1x1 layer; bit 2 (5): no dense stride-2 patches
+    c->dbg_ws64 = env_int("DAT_CONV_WS64", 1);
+    c->dbg_pwlw = env_int("DAT_CONV_PWLW", 1);
+    c->dbg_pwks = env_int("DAT_CONV_PWKS", 8);
+    c->dbg_temporal = env_int("DAT_CONV_TEMPORAL", 1);
+    c->dbg_wgrad_direct = env_int("DAT_WGRAD_DIRECT", 1);
+    c->dbg_wgrad_ks = env_int("DAT_WGRAD_KS", 0);
+    c->dbg_ablate_wgrad = env_int("DAT_WGRAD_ABLATE", 0);
+    c->dbg_wgrad_sub = env_int("DAT_WGRAD_SUB", 2);
+    c->dbg_pw_xcd = env_int("DAT_CONV_PW_XCD", 1);
+    c->dbg_wgrad_pw = env_int("DAT_WGRAD_PW", 1);
+    c->dbg_kps_sep = env_int("DAT_KPS_DECODE_SEP", 1);
+    c->dbg_linear = env_int("DAT_CONV_LINEAR", 1);
+    c->dbg_order = env_int("DAT_CONV_ORDER", 0);
+    c->dbg_persist_pct = env_int("DAT_PERSIST_PCT", 100);
+    c->dbg_bt_min = env_int("DAT_CONV_BT_MIN", 390);   // smallest grid of the big-tile kernel, in hundredths of a round of the CUs
+    c->dbg_bt = env_int("DAT_CONV_BT", 1);   // round 6: on for grids of >= 3.9 even rounds (FPN P2 output conv, conv_rpn_fpn2): +1.3 % on the R-18 forward, same box
+    c->dbg_mfma = env_int("DAT_CONV_MFMA", 1) == 1;   // MFMA shape of the two dominant 3x3 kernels: 0 = 32x32x16, 1 = 16x16x32 (default: +4.6 % on the R-18 forward, same box, every run of three pairs: DESIGN.md section 3.1)
+    c->dbg_roi_fold = env_int("DAT_ROI_BWD_FOLD", 1);
+    c->dbg_ws_poison = env_int("DAT_WS_POISON", 0);
+    c->num_cu = 0;
+}
+
 extern "C" {
 
 int dat_version(void) { return 1; }
@@ -47,33 +76,7 @@ int dat_ctx_create(dat_ctx** out, int device) {
     c->ws_bytes = 0;
     c->ws_generation = 0;
     c->zeros = nullptr;
-    {
-        auto env_int = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
-        c->force_bp = env_int("DAT_CONV_BP", 0);
-        c->force_ks = env_int("DAT_CONV_KSPLIT", 0);
-        c->dbg_ablate = env_int("DAT_CONV_ABLATE", 0);
-        c->dbg_ntap = env_int("DAT_CONV_NTAP", 1);   // 0 off, 1 default rule; bit 1 (2/3): unrolled 1x1 variant for every 1x1 layer; bit 2 (5): no dense stride-2 patches
-        c->dbg_ws64 = env_int("DAT_CONV_WS64", 1);
-        c->dbg_pwlw = env_int("DAT_CONV_PWLW", 1);
-        c->dbg_pwks = env_int("DAT_CONV_PWKS", 8);
-        c->dbg_temporal = env_int("DAT_CONV_TEMPORAL", 1);
-        c->dbg_wgrad_direct = env_int("DAT_WGRAD_DIRECT", 1);
-        c->dbg_wgrad_ks = env_int("DAT_WGRAD_KS", 0);
-        c->dbg_ablate_wgrad = env_int("DAT_WGRAD_ABLATE", 0);
-        c->dbg_wgrad_sub = env_int("DAT_WGRAD_SUB", 2);
-        c->dbg_pw_xcd = env_int("DAT_CONV_PW_XCD", 1);
-        c->dbg_wgrad_pw = env_int("DAT_WGRAD_PW", 1);
-        c->dbg_kps_sep = env_int("DAT_KPS_DECODE_SEP", 1);
-        c->dbg_linear = env_int("DAT_CONV_LINEAR", 1);
-        c->dbg_order = env_int("DAT_CONV_ORDER", 0);
-        c->dbg_persist_pct = env_int("DAT_PERSIST_PCT", 100);
-        c->dbg_bt_min = env_int("DAT_CONV_BT_MIN", 390);   // smallest grid of the big-tile kernel, in hundredths of a round of the CUs
-        c->dbg_bt = env_int("DAT_CONV_BT", 1);   // round 6: on for grids of >= 3.9 even rounds (FPN P2 output conv, conv_rpn_fpn2): +1.3 % on the R-18 forward, same box
-        c->dbg_mfma = env_int("DAT_CONV_MFMA", 1) == 1;   // MFMA shape of the two dominant 3x3 kernels: 0 = 32x32x16, 1 = 16x16x32 (default: +4.6 % on the R-18 forward, same box, every run of three pairs: DESIGN.md section 3.1)
-        c->dbg_roi_fold = env_int("DAT_ROI_BWD_FOLD", 1);
-        c->dbg_ws_poison = env_int("DAT_WS_POISON", 0);
-        c->num_cu = 0;
-    }
+    dat_ctx_read_env(c);
     // a private non-blocking stream + a pinned word buffer for the context's own small device <-> host transfers: the synchronous
     // hipMemcpy / hipMemset entry points are avoided after start-up (measured on ROCm 7.2: a synchronous device -> host hipMemcpy
     // between two replays of a captured hipGraph made the next replay fault)

@@ -839,11 +839,209 @@ int conv_set_frame_window(dat_ctx* ctx, const dat_conv_desc* d, ConvParams& p, c
 
 namespace {
 
+// what the descriptor says about per-RoI blobs (dat_conv_desc::plan_frames): the split-K factor is planned for ONE image's rows
+bool conv_plans_per_image(const dat_conv_desc* d) {
+    const bool plan_on_w = d->frames == 1 && d->H == 1;
+    return d->plan_frames > 0 && d->plan_frames < (plan_on_w ? d->W : d->frames);
+}
+
+// bytes of the generic kernel's LDS patch: whole 1-KiB DMA pieces
+size_t conv_patch_lds(const ConvPlan& plan) { return ((size_t)plan.patch_h * plan.patch_w * PPITCH + 1023) & ~(size_t)1023; }
+
+// One candidate of the makespan model: `bp` positions per block, the 2-D tile choose_tile gives them, and whether the layer runs LINEAR
+// strips instead (small maps, RoI heads: when they save >= 10 % of the tiles, see launch_conv); `tiles` counts whichever it is, `tiles_2d`
+// the 2-D tiles (the strips are a form of the dense 3x3 variant: a layer whose 2-D patch does not fit that variant runs 2-D tiles after all).
+struct TileCand {
+    int bp;
+    TileChoice tc;
+    bool lin;
+    long long tiles, tiles_2d;
+};
+TileCand tile_cand(const dat_ctx* ctx, const dat_conv_desc* d, const ConvParams& p, int dil, int bp) {
+    const TileChoice tc = choose_tile(p.Ho, p.Wo, bp == 256 ? 8 : 7, p.sh, p.sw, (p.KH - 1) * dil + 1, (p.KW - 1) * dil + 1);
+    const long long t2d = cdiv_ll(p.Ho, 1ll << tc.th_log2) * cdiv_ll(p.Wo, 1ll << tc.tw_log2) * p.frames;
+    const long long tlin = linear_tiles(ctx, d, p, bp);
+    const bool lin = tlin > 0 && tlin * 10 <= t2d * 9;
+    return TileCand{bp, tc, lin, lin ? tlin : t2d, t2d};
+}
+
+// ---- positions per block (128 | 256) and split-K factor of the generic kernel from a small makespan model ----------------
+// A block runs steps = ceil(npatch/ks) * taps tap-steps; 2 blocks share a CU (512 slots).  Measured on MI355X:
+// a BP=128 step costs ~1.35 us, a BP=256 step ~2.15 us (2x the work).  The grid runs in "rounds" of 512 blocks;
+// with few rounds the last partial round costs a full one.  Split-K adds an fp32 partial round trip.
+// `p` is the grid the model sees (one image's rows in the first pass of a per-RoI blob); force_ks > 0 pins the factor.
+struct BlockChoice {
+    TileCand tile;
+    int ksplit;
+};
+BlockChoice plan_block(const dat_ctx* ctx, const dat_conv_desc* d, const ConvParams& p, int dil, int force_ks) {
+    const int force_bp = ctx->force_bp;
+    const bool small_n = d->Cout <= 64;
+    const int ncc = p.x3 ? d->Cin / 64 * 3 : d->Cin / (d->dtype == DAT_F32 ? 32 : 64);
+    const int npatch = d->KT * ncc, npatch_min = (d->KT > 1 ? d->KT - 1 : 1) * ncc;
+    const int ntaps = d->KH * d->KW;
+    const long long nbn = p.Cout_pad / (small_n ? 64 : 128);
+    BlockChoice pick{TileCand{0, TileChoice{0, 0}, false, 0, 0}, 1};
+    double best = 1e30;
+    const bool deep_1x1 = (ntaps == 1 && ncc >= 16);
+    for (int cand_bp = 128; cand_bp <= 256; cand_bp += 128) {
+        if (cand_bp == 256 && (small_n || ntaps == 1)) continue;   // the 64-channel and 1x1 variants do not profit
+        // strided 3x3: the dense-patch variant exists for 128-position tiles only and beats the 256-position table-driven loop
+        // (res4_0_branch2a 0.128 -> 0.081 ms, res3_0_branch2a 0.086 -> 0.081, cold caches)
+        if (cand_bp == 256 && !force_bp && ctx->dbg_ntap && !(ctx->dbg_ntap & 4) && d->KH == 3 && d->KW == 3 && d->stride_h == 2 && d->stride_w == 2) continue;
+        if (force_bp && cand_bp != force_bp && !(force_bp == 256 && (small_n || ntaps == 1))) continue;
+        const TileCand cand = tile_cand(ctx, d, p, dil, cand_bp);
+        const int ks_max = (ntaps > 1 || deep_1x1) ? (deep_1x1 ? 8 : 4) : 1;
+        for (int ks = 1; ks <= ks_max && ks <= npatch_min; ++ks) {
+            if (force_ks && ks != std::min(force_ks, npatch_min)) continue;
+            const double nblk = (double)cand.tiles * nbn * ks;
+            const double slots = 512.0;
+            double rounds = nblk / slots;
+            if (rounds <= 3.0) rounds = ceil(rounds); else rounds += 0.5;
+            const double steps = ceil((double)npatch / ks) * ntaps;
+            // (stride-2 3x3 convs run the table-driven loop with four stride-parity patches per chunk: the 256-position tile pays
+            //  more per step there -- tools/tune_plan.py, round 2: res4_0_branch2a 0.114 ms at 256 positions vs 0.089 at 128)
+            const bool strided_taps = ntaps > 1 && (d->stride_h > 1 || d->stride_w > 1);
+            const double step_us = cand_bp == 256 ? (strided_taps ? 2.8 : 2.15) : 1.35;
+            const double fixed_us = 2.0 + 0.6 * ceil((double)npatch / ks);      // epilogue + exposed patch loads
+            double t = rounds * (steps * step_us + fixed_us);
+            if (ks > 1) t += 4.0 + 2.0 * ks * (double)p.frames * p.Ho * p.Wo * d->Cout * 4.0 / 3.0e6;  // us @3 TB/s
+            if (t < best) { best = t; pick = BlockChoice{cand, ks}; }
+        }
+    }
+    if (!pick.tile.bp) pick.tile = tile_cand(ctx, d, p, dil, 128);   // (a forced plan no candidate matches: 128 positions, no split)
+    return pick;
+}
+
+// The launch plan of a validated descriptor (`p`: its geometry as conv_validate derived it; no pointer is read): a pure function of the
+// context's KNOBS, the CU count and the descriptor -- no HIP call, no allocation, no state.  A layer the kernels cannot run returns an
+// error code with its text in `why`.
+int conv_plan(const dat_ctx* ctx, int num_cu, const dat_conv_desc* d, const ConvParams& p, ConvPlan* out, char (&why)[256]) {
+    ConvPlan pl;
+    memset(&pl, 0, sizeof(pl));
+    const int dil = conv_dilation(d);
+    const bool x3 = p.x3, small_n = d->Cout <= 64;
+    // forced plans (dat_conv3d_tune_plan, DAT_CONV_BP / DAT_CONV_KSPLIT) are plans of the generic kernel
+    const bool forced = ctx->force_bp || ctx->force_ks;
+    const bool mask_mode = d->res_mode >= 3;     // the masking combines (3: mask, 4: in-place sum + mask) live in the generic kernel and the lw / ks 1x1 kernels
+    // The split-K factor decides the order in which a result's fp32 partial sums are added, so it must not depend on how many images
+    // share a per-RoI blob: with d->plan_frames (the rows of ONE image) the factor is the one the model picks for that many frames, and
+    // only the tile size follows the real grid -- an image's head results are then bit-equal to those it gets in a forward of its own.
+    // The rows of a per-RoI blob lie on its frames -- or, for the [1, 1, R, K] rows view of the FC layers (one frame, one map row), on W:
+    // plan_frames then counts map columns.  A layer with an output-frame window computes plan_frames / T * out_tn frames per image.
+    int force_ks = ctx->force_ks;
+    if (conv_plans_per_image(d) && !force_ks) {
+        ConvParams p1 = p;              // the launch as ONE image's rows would make it
+        if (d->frames == 1 && d->H == 1) {
+            dat_conv_desc d1 = *d;
+            d1.W = p1.W = d->plan_frames;
+            dat_conv3d_out_shape(&d1, &p1.Ho, &p1.Wo);
+        } else {
+            p1.frames = d->plan_frames / d->T * p.otn;
+        }
+        force_ks = plan_block(ctx, d, p1, dil, 0).ksplit;
+    }
+    const BlockChoice bc = plan_block(ctx, d, p, dil, force_ks);
+    // big-tile kernel: one block per CU at a time, so the grid has to fill the chip several times and evenly (FPN P2: 2016 blocks on
+    // 256 CUs = 7.9 rounds; P3's 528 blocks would run 3 rounds for 2.06 of work: 0.45 ms against 0.34 ms with the generic kernel)
+    long long bt_blocks = 0, blocks = 0;
+    const int bt_twl = bt_eligible(ctx, d) ? bt_tile_twl(p, &bt_blocks) : 0;
+    const long long ncu = num_cu, bt_rounds = cdiv_ll(bt_blocks, ncu);
+    const bool bt_fits = bt_twl && (ctx->dbg_bt >= 2 ? bt_blocks * 2 >= 3 * ncu : (bt_blocks * 100 >= (long long)ctx->dbg_bt_min * ncu && bt_blocks * 100 >= bt_rounds * ncu * 95));   // (3.9: conv_rpn_fpn2 at 4 clips is 1 008 blocks on 256 CUs)
+    if (!forced && bt_fits && bc.ksplit == 1 && !mask_mode) {
+        pl.family = DAT_CONV_BIGTILE;
+        pl.tag = 256 * 10000 + 2560 + d->dtype;
+        pl.twl = bt_twl;
+        blocks = bt_blocks;
+    } else if (!forced && pw256_eligible(ctx, d) && !mask_mode) {
+        pl.family = DAT_CONV_PW256;
+        pl.tag = 256 * 10000 + 320 + d->dtype;     // (256 channels x 32 positions per wave: the weights-stationary 1x1 kernel)
+        blocks = pw256_grid(ctx, num_cu, p);
+    } else if (!forced && pwks_eligible(ctx, num_cu, d)) {       // (its epilogue knows the masking combines too)
+        pl.family = DAT_CONV_PWKS;
+        pl.tag = 256 * 10000 + 340 + d->dtype;     // (the K-streaming 1x1 kernel: 256 positions x 256 channels per block)
+        blocks = ks_grid(p);
+    } else if (!forced && tks_eligible(ctx, num_cu, d)) {
+        pl.family = DAT_CONV_TKS;
+        pl.tag = 256 * 10000 + 350 + d->dtype;     // (the temporal-tap K-streaming kernel: kT x 1 x 1, 256 positions x 256 channels per block)
+        blocks = ks_grid(p);
+    } else if (!forced && pwlw_eligible(ctx, num_cu, d) && d->res_mode != 3) {   // (knows the sum + mask combine; plain mask layers -- K >= 512 data
+                                                                                 //  gradients of `branch2c` on small maps -- measured faster on the generic kernel)
+        pl.family = DAT_CONV_PWLW;
+        pl.tag = 256 * 10000 + 330 + d->dtype;     // (the weights-in-LDS 1x1 kernel: 32 positions per wave tile)
+        blocks = pwlw_grid(ctx, num_cu, p);
+    } else if (!forced && ws64_eligible(ctx, d) && !mask_mode) {
+        long long ntiles = 0;
+        pl.family = DAT_CONV_WS64;
+        pl.tag = 64 * 10000 + 9990 + d->dtype;    // ("999 positions": the persistent weights-stationary kernel)
+        pl.twl = ws64_tile_twl(ctx, num_cu, p, &ntiles);
+        blocks = ws64_grid(ctx, num_cu, ntiles);
+    } else {   // the implicit-GEMM kernel: weights straight into the MFMA registers
+        // unrolled-tap variants: dense 3x3 (stride 1) and 1x1 (any stride: one tap, one plane); the patch must fit the per-wave
+        // piece registers (tile shapes with very long rows fall back to the table-driven loop).  1x1 layers with a large output
+        // grid are bandwidth-bound and do better with the leaner table-driven loop (one block more per CU), measured.
+        const int bp = bc.tile.bp;
+        const bool big = bp == 256;
+        const long long th = 1ll << bc.tile.tc.th_log2, tw = 1ll << bc.tile.tc.tw_log2;
+        // (a dilated 3x3 keeps the unrolled variant while its wider patch fits the piece registers -- < 64 KiB, so the packed 16-bit
+        //  addresses hold too; beyond that it takes the table-driven loop)
+        const long long prow = (th + (p.KH - 1) * dil / p.sh) * (tw + (p.KW - 1) * dil / p.sw);
+        const bool fits = ((prow * 8 + 63) >> 6) <= 4 * patch_pieces_per_wave(9, bp);
+        const bool pw_small = (long long)p.frames * p.Ho * p.Wo <= 65536;
+        // strided 3x3: ONE dense patch of (2*TH+1) x (2*TW+1) cells serves all 9 taps (the table-driven loop stages four stride-parity
+        // patches per channel chunk and synchronises around each); 128-position tiles only (the patch is 70 KiB: two blocks per CU)
+        const long long drow = ((th - 1) * p.sh + p.KH) * ((tw - 1) * p.sw + p.KW);
+        const bool dense2 = ctx->dbg_ntap && !big && d->KH == 3 && d->KW == 3 && d->stride_h == 2 && d->stride_w == 2 && !(ctx->dbg_ntap & 4) &&
+                            ((drow * 8 + 63) >> 6) <= 4 * 19;
+        const int ntapv = dense2 ? 10 : !ctx->dbg_ntap || !fits ? 0 : (d->KH == 3 && d->KW == 3 && d->stride_h == 1 && d->stride_w == 1) ? 9 :
+                          (d->KH == 1 && d->KW == 1 && (pw_small || (ctx->dbg_ntap & 2))) ? 1 : 0;
+        const bool lin = ntapv == 9 && bc.tile.lin;
+        pl.family = DAT_CONV_GENERIC;
+        pl.tag = (small_n ? 64 : 128) * 10000 + bp * 10 + d->dtype + (dil > 1 ? 5 : 0);   // (last digit 5-7: a dilated layer, always this kernel)
+        pl.bn = small_n ? 64 : 128;
+        pl.bp = bp;
+        pl.ksplit = bc.ksplit;          // (the model never goes beyond npatch_min, forced or not)
+        pl.npatch_min = (d->KT > 1 ? d->KT - 1 : 1) * (x3 ? d->Cin / 64 * 3 : d->Cin / (d->dtype == DAT_F32 ? 32 : 64));
+        pl.ntap = lin && dil > 1 ? 19 : ntapv;
+        pl.linear = lin;
+        // DAT_CONV_MFMA=1: the bf16 128-channel dense 3x3 variants (2-D tiles, linear strips, split-K) on 16x16x32, like the big-tile kernel
+        pl.mfma = ctx->dbg_mfma && ntapv == 9 && !x3 && !small_n && d->dtype == DAT_BF16 && !(lin && dil > 1);   // (dilated strips: 32x32x16 only)
+        pl.in_dtype = d->dtype == DAT_F32 ? DAT_F32 : DAT_BF16;
+        pl.out_dtype = d->dtype == DAT_BF16 ? DAT_BF16 : DAT_F32;
+        if (lin) {           // a 1 x bp strip; its patch is the strip widened by dil * (W + 1) positions on either side, and one all-zero row
+            pl.th_log2 = 0; pl.tw_log2 = big ? 8 : 7;
+            pl.patch_h = 1; pl.patch_w = bp + 2 * dil * (p.W + 1) + 1;
+        } else {
+            pl.th_log2 = bc.tile.tc.th_log2; pl.tw_log2 = bc.tile.tc.tw_log2;
+            pl.patch_h = (int)(ntapv == 10 ? (th - 1) * p.sh + p.KH : th + (p.KH - 1) * dil / p.sh);
+            pl.patch_w = (int)(ntapv == 10 ? (tw - 1) * p.sw + p.KW : tw + (p.KW - 1) * dil / p.sw);
+        }
+        blocks = (lin ? bc.tile.tiles : bc.tile.tiles_2d) * (p.Cout_pad / pl.bn) * pl.ksplit;
+    }
+#define DAT_PLAN_FAIL(code, ...) do { snprintf(why, sizeof(why), __VA_ARGS__); return (code); } while (0)
+    if (!(blocks > 0 && blocks < (1ll << 31))) DAT_PLAN_FAIL(DAT_ERR_ARG, "conv3d: grid of %lld blocks unsupported", blocks);
+    pl.blocks = (int)blocks;
+    if (pl.family == DAT_CONV_GENERIC && conv_patch_lds(pl) > 160 * 1024) {
+        if (dil > 1)
+            DAT_PLAN_FAIL(DAT_ERR_UNSUPPORTED, "conv3d: dilation %d is unsupported for this layer: the %dx%d patch of a %dx%d tile takes %zu bytes of LDS (limit 160 KiB)",
+                          dil, pl.patch_h, pl.patch_w, 1 << pl.th_log2, 1 << pl.tw_log2, conv_patch_lds(pl));
+        DAT_PLAN_FAIL(DAT_ERR_ARG, "conv3d: LDS patch of %zu bytes exceeds 160 KiB (tile %dx%d, stride %dx%d)", conv_patch_lds(pl),
+                      1 << pl.th_log2, 1 << pl.tw_log2, p.sh, p.sw);
+    }
+#undef DAT_PLAN_FAIL
+    *out = pl;
+    return DAT_OK;
+}
+
 template <int DT, int BN, int BP, int WAVES_N, int NTAP, int ODT, int MF = 0>
-int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ksplit, bool linear = false, int dil = 1) {
+int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, const ConvPlan& plan, int dil) {
+    // The tile, the patch, the strip flag, the split-K factor and the grid are the plan's (conv_plan); this builds the kernel's geometry from them.
     // dil > 1 (stride 1, checked by the caller): the same loops over a wider patch -- the halo is (K - 1) * dil cells and tap (kh, kw) sits
     // kh * dil rows and kw * dil columns into it.  Only this host-built geometry knows the dilation; the kernels read it from the table.
-    TileChoice tc = choose_tile(p.Ho, p.Wo, bp_log2, p.sh, p.sw, (p.KH - 1) * dil + 1, (p.KW - 1) * dil + 1);
+    const bool linear = plan.linear;
+    const int th = 1 << plan.th_log2, tw = 1 << plan.tw_log2;
+    p.th_log2 = plan.th_log2; p.tw_log2 = plan.tw_log2;
+    p.PH = plan.patch_h; p.PW = plan.patch_w;
     p.lin_h = p.lin_w = 0;
     p.lin_zero_row = -1;
     if (linear) {
@@ -862,39 +1060,29 @@ int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ks
                              total * std::max(p.Cin, std::max(p.out_cs, p.Cout)) * 4 < (1ll << 31),
                     "conv3d: linear tiling on an unsupported layer");
         p.lin_h = p.H; p.lin_w = p.W;
-        const int wr = p.W, nr = BP + 2 * dil * (wr + 1) + 1;
-        tc = TileChoice{0, bp_log2};
+        const int wr = p.W, nr = plan.patch_w;      // (BP + 2 * dil * (W + 1) + 1 rows: the strip, its halo and the zero row)
         p.H = p.Ho = 1; p.W = p.Wo = (int)total;
         if (!per_frame) { p.frames = 1; p.T = 1; p.ot0 = 0; p.otn = 1; p.in_lo = 0; p.in_hi = 1; }
         p.ph = 0; p.pw = dil * (wr + 1);
         p.lin_zero_row = nr - 1;
-        p.th_log2 = 0; p.tw_log2 = bp_log2;
         p.tile_w = BP;
         p.tiles_h = 1; p.tiles_w = (int)cdiv_ll(total, BP);
         p.psh = p.psw = 1; p.rsh = p.rsw = 1;
-        p.PH = 1; p.PW = nr;
         p.tab_new = 1u; p.tab_n = 9;
         for (int i = 0; i < 9; ++i) { p.tab_tap[i] = i; p.tab_rowoff[i] = (i / 3) * dil * wr + (i % 3) * dil; p.tab_dy[i] = p.tab_dx[i] = 0; }
     }
-    const int th = 1 << tc.th_log2, tw = 1 << tc.tw_log2;
     if (!linear) {
-    p.th_log2 = tc.th_log2;
-    p.tw_log2 = tc.tw_log2;
-    p.tile_w = tw;
-    p.tiles_h = (p.Ho + th - 1) / th;
-    p.tiles_w = (p.Wo + tw - 1) / tw;
-    p.psh = p.sh;
-    p.psw = p.sw;
-    p.rsh = p.rsw = 1;
-    p.PH = th + (p.KH - 1) * dil / p.sh;
-    p.PW = tw + (p.KW - 1) * dil / p.sw;
+        p.tile_w = tw;
+        p.tiles_h = (p.Ho + th - 1) / th;
+        p.tiles_w = (p.Wo + tw - 1) / tw;
+        p.psh = p.sh;
+        p.psw = p.sw;
+        p.rsh = p.rsw = 1;
     }
     if (linear) {
     } else if (NTAP == 10) {   // one DENSE patch for all 9 taps of a strided 3x3: neighbouring outputs are `stride` patch cells apart
         p.psh = p.psw = 1;
         p.rsh = p.sh; p.rsw = p.sw;
-        p.PH = (th - 1) * p.sh + p.KH;
-        p.PW = (tw - 1) * p.sw + p.KW;
         p.tab_new = 1u;
         p.tab_n = p.KH * p.KW;
         for (int i = 0; i < p.tab_n; ++i) {
@@ -912,41 +1100,29 @@ int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ks
     p.n_cchunks = p.x3 ? p.Cin / Mma<DT>::CK / 2 * 3 : p.Cin / Mma<DT>::CK;   // bf16x3: [hi | hi | lo] against [W_hi | W_lo | W_hi]
     p.ablate = ctx->dbg_ablate;
     p.nblk_n = p.Cout_pad / BN;
-    long long nblocks = (long long)p.frames * p.tiles_h * p.tiles_w * p.nblk_n;
-    // split-K (chosen by plan_conv): fp32 partial sums in the ctx workspace, finished by splitk_finish_kernel
-    {
-        const int npatch_min = (p.KT > 1 ? p.KT - 1 : 1) * p.n_cchunks;
-        int ks = ksplit < 1 ? 1 : (ksplit > npatch_min ? npatch_min : ksplit);
-        p.ksplit = ks;
-        p.part = nullptr;
-        if (ks > 1) {
-            const size_t bytes = (size_t)ks * p.frames * p.Ho * p.Wo * p.Cout * sizeof(float);
-            int rc = dat_ensure_ws(ctx, bytes);
-            if (rc != DAT_OK) return rc;
-            p.part = (float*)ctx->ws;
-        }
-        nblocks *= ks;
+    // split-K (chosen by conv_plan): fp32 partial sums in the ctx workspace, finished by splitk_finish_kernel
+    p.ksplit = plan.ksplit;
+    p.part = nullptr;
+    if (p.ksplit > 1) {
+        const size_t bytes = (size_t)p.ksplit * p.frames * p.Ho * p.Wo * p.Cout * sizeof(float);
+        int rc = dat_ensure_ws(ctx, bytes);
+        if (rc != DAT_OK) return rc;
+        p.part = (float*)ctx->ws;
     }
-    DAT_ENFORCE(ctx, nblocks > 0 && nblocks < (1ll << 31), "conv3d: grid of %lld blocks unsupported", nblocks);
     DAT_ENFORCE(ctx, (long long)p.Ho * p.Wo * std::max(p.out_cs, p.Cout) * 4 < (1ll << 31),
                 "conv3d: one output frame of %dx%dx%d exceeds the 2-GB range of the epilogue's 32-bit offsets", p.Ho, p.Wo, p.out_cs);
-    p.nblocks = (unsigned)nblocks;
-    p.ntiles = (unsigned)(nblocks / ((long long)p.ksplit * p.nblk_n));
+    p.nblocks = (unsigned)plan.blocks;
+    p.ntiles = (unsigned)(plan.blocks / (p.ksplit * p.nblk_n));
     // Which blocks are neighbours in an XCD's queue (DAT_CONV_ORDER, default 0).  The ~64 resident blocks of an XCD read the weight slices
     // of every (cout block, split) they cover and the patches of their tiles through one 4-MB L2.  Order 1 (tile fastest) keeps ONE weight
     // slice resident and re-reads the input once per (cout block, split).  Measured: fabric reads -41 % over
     // the forward (res5's 512 -> 512 x 27 taps 2.09 -> 0.46 GB per launch, P2 7.8 -> 4.6 GB) and every such layer 2-4 % SLOWER -- the
     // sibling cout block no longer finds the patch in L2, and patch misses are waited for while weight misses are not.  Kept as a switch.
     p.order = ctx->dbg_order > 0;
-    size_t lds = ((size_t)p.PH * p.PW * PPITCH + 1023) & ~(size_t)1023;     // whole 1-KiB DMA pieces
+    size_t lds = conv_patch_lds(plan);                                      // (conv_plan refuses a patch beyond 160 KiB)
     if (lds < EPI_SLICES_BYTES) lds = EPI_SLICES_BYTES;                     // epilogue staging slices
-    if (lds > 160 * 1024 && dil > 1)
-        DAT_FAIL(ctx, DAT_ERR_UNSUPPORTED, "conv3d: dilation %d is unsupported for this layer: the %dx%d patch of a %dx%d tile takes %zu bytes of LDS (limit 160 KiB)",
-                 dil, p.PH, p.PW, th, tw, lds);
-    DAT_ENFORCE(ctx, lds <= 160 * 1024, "conv3d: LDS patch of %zu bytes exceeds 160 KiB (tile %dx%d, stride %dx%d)", lds,
-                th, tw, p.sh, p.sw);
     auto kern = conv3d_igemm_kernel<DT, BN, BP, WAVES_N, 1, NTAP, ODT, MF>;
-    if (NTAP > 0) {   // what the unrolled variant assumes (the dispatcher only picks it for these shapes)
+    if (NTAP > 0) {   // what the unrolled variant assumes (conv_plan only picks it for these shapes)
         DAT_ENFORCE(ctx, NTAP != 19 || linear, "conv3d: the dilated-strip variant runs linear strips only");
         DAT_ENFORCE(ctx, p.tab_n == (NTAP == 10 || NTAP == 19 ? 9 : NTAP) && p.tab_new == 1u &&
                              (((size_t)p.PH * p.PW * 8 + 63) >> 6) <= (size_t)4 * patch_pieces_per_wave(NTAP, BP) && (NTAP == 10 || (size_t)p.PH * p.PW * PPITCH < 65536),
@@ -986,6 +1162,80 @@ int launch_conv(dat_ctx* ctx, hipStream_t st, ConvParams& p, int bp_log2, int ks
     }
     DAT_CHECK_LAUNCH(ctx, "conv3d_igemm");
     return DAT_OK;
+}
+
+// step 1 of a forward: what the entry points refuse, and the launch parameters `p` the descriptor and the tensors give
+int conv_validate(dat_ctx* ctx, const dat_conv_desc* d, const void* x, const void* w_packed, const float* scale, const float* bias,
+                         const void* residual, void* y, void* y_split, const void* addend, ConvParams& p) {
+    DAT_ENFORCE(ctx, d && x && w_packed && y, "conv3d_fwd: null argument");
+    DAT_ENFORCE(ctx, d->dtype == DAT_F32 || d->dtype == DAT_BF16 || d->dtype == DAT_BF16X3, "conv3d_fwd: bad dtype %d", d->dtype);
+    const bool x3 = d->dtype == DAT_BF16X3;
+    DAT_ENFORCE(ctx, !x3 || DAT_H16_FORMAT == 0, "conv3d_fwd: DAT_BF16X3 needs the bf16 build of the library (this one holds IEEE half in its 16-bit tensors)");
+    DAT_ENFORCE(ctx, d->Cin % 64 == 0, "conv3d_fwd: Cin (channel stride) %d must be a multiple of 64", d->Cin);
+    DAT_ENFORCE(ctx, d->Cout % 4 == 0 && d->out_cstride % 4 == 0 && d->out_cstride >= d->Cout,
+                "conv3d_fwd: Cout %d / out_cstride %d must be multiples of 4", d->Cout, d->out_cstride);
+    DAT_ENFORCE(ctx, d->frames % d->T == 0, "conv3d_fwd: frames %d not a multiple of T %d", d->frames, d->T);
+    DAT_ENFORCE(ctx, d->res_mode >= 0 && d->res_mode <= 4, "conv3d_fwd: res_mode %d", d->res_mode);
+    DAT_ENFORCE(ctx, d->res_mode != 4 || (!x3 && !y_split && addend), "conv3d_fwd: res_mode 4 (sum + mask) goes through dat_conv3d_fwd_sum_mask, bf16 / fp32 only");
+    DAT_ENFORCE(ctx, d->res_mode == 0 || residual, "conv3d_fwd: res_mode %d needs a residual pointer", d->res_mode);
+    // full-length outputs need "same" temporal padding; an explicit output-frame window may use any pad_t (taps that
+    // fall outside [0, T) read zeros) -- e.g. KT == T, pad_t == 0, window {0}: a 1x1 conv over time-moved-to-channels
+    DAT_ENFORCE(ctx, d->pad_t * 2 + 1 == d->KT || d->out_tn > 0,
+                "conv3d_fwd: temporal pad %d must be (KT-1)/2 for KT %d unless out_t0/out_tn select the output frames",
+                d->pad_t, d->KT);
+    if (const char* why = conv_dilation_refusal(d)) DAT_FAIL(ctx, DAT_ERR_UNSUPPORTED, "conv3d_fwd: %s (dil %dx%d, stride %dx%d)", why, d->dil_h, d->dil_w, d->stride_h, d->stride_w);
+    memset(&p, 0, sizeof(p));
+    p.x = (const char*)x; p.w = (const char*)w_packed; p.scale = scale; p.bias = bias;
+    p.res = (const char*)residual; p.res2 = (const char*)addend; p.y = (char*)y; p.y_split = (char*)y_split;
+    p.zeros = (const char*)ctx->zeros;
+    p.clk = ctx->prof_enabled ? (unsigned long long*)((char*)ctx->zeros + 256) : nullptr;
+    {
+        const int rcw = conv_set_frame_window(ctx, d, p, "conv3d_fwd");
+        if (rcw != DAT_OK) return rcw;
+    }
+    p.T = d->T; p.H = d->H; p.W = d->W; p.Cin = x3 ? 2 * d->Cin : d->Cin;   // (x3: pixel pitch of the hi / lo split tensor)
+    p.x3 = x3;
+    dat_conv3d_out_shape(d, &p.Ho, &p.Wo);
+    DAT_ENFORCE(ctx, p.Ho > 0 && p.Wo > 0, "conv3d_fwd: empty output %dx%d", p.Ho, p.Wo);
+    DAT_ENFORCE(ctx, d->res_mode != 2 || (p.Ho % 2 == 0 && p.Wo % 2 == 0), "conv3d_fwd: res_mode 2 needs even output dims");
+    p.Cout = d->Cout; p.out_cs = d->out_cstride; p.Cout_pad = cout_pad_of(d);
+    p.KT = d->KT; p.KH = d->KH; p.KW = d->KW; p.sh = d->stride_h; p.sw = d->stride_w;
+    p.pt = d->pad_t; p.ph = d->pad_h; p.pw = d->pad_w; p.relu = d->relu; p.res_mode = d->res_mode;
+    DAT_ENFORCE(ctx, !conv_plans_per_image(d) || (d->frames == 1 && d->H == 1) || d->plan_frames % d->T == 0, "conv3d_fwd: plan_frames %d must be a multiple of T %d",
+                d->plan_frames, d->T);
+    return DAT_OK;
+}
+
+// step 3: the plan's kernel on the stream.  The generic kernel's instantiation follows the plan's fields one to one.
+template <int DT, int BN, int WN, int ODT>
+int launch_generic(dat_ctx* ctx, hipStream_t st, ConvParams& p, const ConvPlan& plan, int dil) {
+    const bool big = plan.bp == 256;
+    switch (plan.ntap) {
+    case 19: return big ? launch_conv<DT, BN, 256, WN, 19, ODT>(ctx, st, p, plan, dil) : launch_conv<DT, BN, 128, WN, 19, ODT>(ctx, st, p, plan, dil);
+    case 10: return launch_conv<DT, BN, 128, WN, 10, ODT>(ctx, st, p, plan, dil);      // (128-position tiles only)
+    case 9: return big ? launch_conv<DT, BN, 256, WN, 9, ODT>(ctx, st, p, plan, dil) : launch_conv<DT, BN, 128, WN, 9, ODT>(ctx, st, p, plan, dil);
+    case 1: return big ? launch_conv<DT, BN, 256, WN, 1, ODT>(ctx, st, p, plan, dil) : launch_conv<DT, BN, 128, WN, 1, ODT>(ctx, st, p, plan, dil);
+    default: return big ? launch_conv<DT, BN, 256, WN, 0, ODT>(ctx, st, p, plan, dil) : launch_conv<DT, BN, 128, WN, 0, ODT>(ctx, st, p, plan, dil);
+    }
+}
+
+int conv_launch(dat_ctx* ctx, hipStream_t st, ConvParams& p, const ConvPlan& plan, int dil) {
+    switch (plan.family) {
+    case DAT_CONV_BIGTILE: return launch_bt(ctx, st, p, plan);
+    case DAT_CONV_PW256: return launch_pw256(ctx, st, p, plan);
+    case DAT_CONV_PWKS: return launch_pwks(ctx, st, p, plan);
+    case DAT_CONV_TKS: return launch_tks(ctx, st, p, plan);
+    case DAT_CONV_PWLW: return launch_pwlw(ctx, st, p, plan);
+    case DAT_CONV_WS64: return launch_ws64(ctx, st, p, plan);
+    default: break;
+    }
+    const bool small_n = plan.bn == 64;
+    if (plan.mfma)
+        return plan.bp == 256 ? launch_conv<DAT_BF16, 128, 256, 2, 9, DAT_BF16, 1>(ctx, st, p, plan, dil) : launch_conv<DAT_BF16, 128, 128, 2, 9, DAT_BF16, 1>(ctx, st, p, plan, dil);
+    if (plan.in_dtype == DAT_F32) return small_n ? launch_generic<DAT_F32, 64, 1, DAT_F32>(ctx, st, p, plan, dil) : launch_generic<DAT_F32, 128, 2, DAT_F32>(ctx, st, p, plan, dil);
+    if (plan.out_dtype == DAT_F32)      // (bf16x3)
+        return small_n ? launch_generic<DAT_BF16, 64, 1, DAT_F32>(ctx, st, p, plan, dil) : launch_generic<DAT_BF16, 128, 2, DAT_F32>(ctx, st, p, plan, dil);
+    return small_n ? launch_generic<DAT_BF16, 64, 1, DAT_BF16>(ctx, st, p, plan, dil) : launch_generic<DAT_BF16, 128, 2, DAT_BF16>(ctx, st, p, plan, dil);
 }
 
 }  // namespace
@@ -1038,182 +1288,32 @@ int dat_conv3d_fwd_sum_mask(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, 
 
 static int conv3d_fwd_impl(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, const void* x, const void* w_packed,
                            const float* scale, const float* bias, const void* residual, void* y, void* y_split, const void* addend) {
-    DAT_ENFORCE(ctx, d && x && w_packed && y, "conv3d_fwd: null argument");
-    DAT_ENFORCE(ctx, d->dtype == DAT_F32 || d->dtype == DAT_BF16 || d->dtype == DAT_BF16X3, "conv3d_fwd: bad dtype %d", d->dtype);
-    const bool x3 = d->dtype == DAT_BF16X3;
-    DAT_ENFORCE(ctx, !x3 || DAT_H16_FORMAT == 0, "conv3d_fwd: DAT_BF16X3 needs the bf16 build of the library (this one holds IEEE half in its 16-bit tensors)");
-    DAT_ENFORCE(ctx, d->Cin % 64 == 0, "conv3d_fwd: Cin (channel stride) %d must be a multiple of 64", d->Cin);
-    DAT_ENFORCE(ctx, d->Cout % 4 == 0 && d->out_cstride % 4 == 0 && d->out_cstride >= d->Cout,
-                "conv3d_fwd: Cout %d / out_cstride %d must be multiples of 4", d->Cout, d->out_cstride);
-    DAT_ENFORCE(ctx, d->frames % d->T == 0, "conv3d_fwd: frames %d not a multiple of T %d", d->frames, d->T);
-    DAT_ENFORCE(ctx, d->res_mode >= 0 && d->res_mode <= 4, "conv3d_fwd: res_mode %d", d->res_mode);
-    DAT_ENFORCE(ctx, d->res_mode != 4 || (!x3 && !y_split && addend), "conv3d_fwd: res_mode 4 (sum + mask) goes through dat_conv3d_fwd_sum_mask, bf16 / fp32 only");
-    DAT_ENFORCE(ctx, d->res_mode == 0 || residual, "conv3d_fwd: res_mode %d needs a residual pointer", d->res_mode);
-    // full-length outputs need "same" temporal padding; an explicit output-frame window may use any pad_t (taps that
-    // fall outside [0, T) read zeros) -- e.g. KT == T, pad_t == 0, window {0}: a 1x1 conv over time-moved-to-channels
-    DAT_ENFORCE(ctx, d->pad_t * 2 + 1 == d->KT || d->out_tn > 0,
-                "conv3d_fwd: temporal pad %d must be (KT-1)/2 for KT %d unless out_t0/out_tn select the output frames",
-                d->pad_t, d->KT);
-    if (const char* why = conv_dilation_refusal(d)) DAT_FAIL(ctx, DAT_ERR_UNSUPPORTED, "conv3d_fwd: %s (dil %dx%d, stride %dx%d)", why, d->dil_h, d->dil_w, d->stride_h, d->stride_w);
-    const int dil = conv_dilation(d);
     ConvParams p;
-    memset(&p, 0, sizeof(p));
-    p.x = (const char*)x; p.w = (const char*)w_packed; p.scale = scale; p.bias = bias;
-    p.res = (const char*)residual; p.res2 = (const char*)addend; p.y = (char*)y; p.y_split = (char*)y_split;
-    p.zeros = (const char*)ctx->zeros;
-    p.clk = ctx->prof_enabled ? (unsigned long long*)((char*)ctx->zeros + 256) : nullptr;
-    {
-        const int rcw = conv_set_frame_window(ctx, d, p, "conv3d_fwd");
-        if (rcw != DAT_OK) return rcw;
-    }
-    p.T = d->T; p.H = d->H; p.W = d->W; p.Cin = x3 ? 2 * d->Cin : d->Cin;   // (x3: pixel pitch of the hi / lo split tensor)
-    p.x3 = x3;
-    dat_conv3d_out_shape(d, &p.Ho, &p.Wo);
-    DAT_ENFORCE(ctx, p.Ho > 0 && p.Wo > 0, "conv3d_fwd: empty output %dx%d", p.Ho, p.Wo);
-    DAT_ENFORCE(ctx, d->res_mode != 2 || (p.Ho % 2 == 0 && p.Wo % 2 == 0), "conv3d_fwd: res_mode 2 needs even output dims");
-    p.Cout = d->Cout; p.out_cs = d->out_cstride; p.Cout_pad = cout_pad_of(d);
-    p.KT = d->KT; p.KH = d->KH; p.KW = d->KW; p.sh = d->stride_h; p.sw = d->stride_w;
-    p.pt = d->pad_t; p.ph = d->pad_h; p.pw = d->pad_w; p.relu = d->relu; p.res_mode = d->res_mode;
+    ConvPlan plan;
+    char why[256];
+    int rc = conv_validate(ctx, d, x, w_packed, scale, bias, residual, y, y_split, addend, p);
+    if (rc != DAT_OK) return rc;
+    rc = conv_plan(ctx, ctx_num_cu(ctx), d, p, &plan, why);
+    if (rc != DAT_OK) DAT_FAIL(ctx, rc, "%s", why);
     hipStream_t st = (hipStream_t)s;
-
-    const bool small_n = d->Cout <= 64;
-    // ---- plan: positions per block (128 | 256) and split-K factor from a small makespan model ----------------
-    // A block runs steps = ceil(npatch/ks) * taps tap-steps; 2 blocks share a CU (512 slots).  Measured on MI355X:
-    // a BP=128 step costs ~1.35 us, a BP=256 step ~2.15 us (2x the work).  The grid runs in "rounds" of 512 blocks;
-    // with few rounds the last partial round costs a full one.  Split-K adds an fp32 partial round trip.
-    const int force_bp = ctx->force_bp, force_ks = ctx->force_ks;
-    const int ck = d->dtype == DAT_F32 ? 32 : 64;
-    const int ncc = x3 ? d->Cin / 64 * 3 : d->Cin / ck;
-    const int npatch = d->KT * ncc, npatch_min = (d->KT > 1 ? d->KT - 1 : 1) * ncc;
-    const int ntaps = d->KH * d->KW;
-    const long long nbn = p.Cout_pad / (small_n ? 64 : 128);
-    int bp = 128, ksplit = 1;
-    // The split-K factor decides the order in which a result's fp32 partial sums are added, so it must not depend on how many images
-    // share a per-RoI blob: with d->plan_frames (the rows of ONE image) the factor is the one the model picks for that many frames, and
-    // only the tile size follows the real grid -- an image's head results are then bit-equal to those it gets in a forward of its own.
-    // The rows of a per-RoI blob lie on its frames -- or, for the [1, 1, R, K] rows view of the FC layers (one frame, one map row), on W:
-    // plan_frames then counts map columns.  A layer with an output-frame window computes plan_frames / T * out_tn frames per image.
-    const bool plan_on_w = d->frames == 1 && d->H == 1;
-    const bool per_image = d->plan_frames > 0 && d->plan_frames < (plan_on_w ? d->W : d->frames);
-    DAT_ENFORCE(ctx, !per_image || plan_on_w || d->plan_frames % d->T == 0, "conv3d_fwd: plan_frames %d must be a multiple of T %d",
-                d->plan_frames, d->T);
-    ConvParams p1 = p;              // the launch as ONE image's rows would make it (p itself where the field does not apply)
-    dat_conv_desc d1 = *d;
-    if (per_image) {
-        if (plan_on_w) { d1.W = d->plan_frames; p1.W = d1.W; dat_conv3d_out_shape(&d1, &p1.Ho, &p1.Wo); }
-        else { d1.frames = d->plan_frames; p1.frames = d->plan_frames / d->T * p.otn; }
-        d1.plan_frames = 0;
-    }
-    const int plan_passes = (per_image && !force_ks) ? 2 : 1;
-    int ks_fixed = force_ks;
-    for (int pass = 0; pass < plan_passes; ++pass) {
-        const bool model_pass = plan_passes == 2 && pass == 0;
-        ConvParams pm = model_pass ? p1 : p;
-        const ConvParams& p = pm;       // (shadows the launch parameters inside the model)
-        const int force_ks = ks_fixed;
-        bp = 128; ksplit = 1;
-        double best = 1e30;
-        const bool deep_1x1 = (ntaps == 1 && ncc >= 16);
-        for (int cand_bp = 128; cand_bp <= 256; cand_bp += 128) {
-            if (cand_bp == 256 && (small_n || ntaps == 1)) continue;   // the 64-channel and 1x1 variants do not profit
-            // strided 3x3: the dense-patch variant exists for 128-position tiles only and beats the 256-position table-driven loop
-            // (res4_0_branch2a 0.128 -> 0.081 ms, res3_0_branch2a 0.086 -> 0.081, cold caches)
-            if (cand_bp == 256 && !force_bp && ctx->dbg_ntap && !(ctx->dbg_ntap & 4) && d->KH == 3 && d->KW == 3 && d->stride_h == 2 && d->stride_w == 2) continue;
-            if (force_bp && cand_bp != force_bp && !(force_bp == 256 && (small_n || ntaps == 1))) continue;
-            const int lg = cand_bp == 256 ? 8 : 7;
-            const TileChoice tc = choose_tile(p.Ho, p.Wo, lg, p.sh, p.sw, (p.KH - 1) * dil + 1, (p.KW - 1) * dil + 1);
-            long long tiles = cdiv_ll(p.Ho, 1ll << tc.th_log2) * cdiv_ll(p.Wo, 1ll << tc.tw_log2) * p.frames;
-            {   // (the dispatcher's rule below: linear tiles when they save >= 10 %)
-                const long long tl = linear_tiles(ctx, d, p, cand_bp);
-                if (tl > 0 && tl * 10 <= tiles * 9) tiles = tl;
-            }
-            const int ks_max = (ntaps > 1 || deep_1x1) ? (deep_1x1 ? 8 : 4) : 1;
-            for (int ks = 1; ks <= ks_max && ks <= npatch_min; ++ks) {
-                if (force_ks && ks != std::min(force_ks, npatch_min)) continue;
-                const double nblk = (double)tiles * nbn * ks;
-                const double slots = 512.0;
-                double rounds = nblk / slots;
-                if (rounds <= 3.0) rounds = ceil(rounds); else rounds += 0.5;
-                const double steps = ceil((double)npatch / ks) * ntaps;
-                // (stride-2 3x3 convs run the table-driven loop with four stride-parity patches per chunk: the 256-position tile pays
-                //  more per step there -- tools/tune_plan.py, round 2: res4_0_branch2a 0.114 ms at 256 positions vs 0.089 at 128)
-                const bool strided_taps = ntaps > 1 && (d->stride_h > 1 || d->stride_w > 1);
-                const double step_us = cand_bp == 256 ? (strided_taps ? 2.8 : 2.15) : 1.35;
-                const double fixed_us = 2.0 + 0.6 * ceil((double)npatch / ks);      // epilogue + exposed patch loads
-                double t = rounds * (steps * step_us + fixed_us);
-                if (ks > 1) t += 4.0 + 2.0 * ks * (double)p.frames * p.Ho * p.Wo * d->Cout * 4.0 / 3.0e6;  // us @3 TB/s
-                if (t < best) { best = t; bp = cand_bp; ksplit = ks; }
-            }
-        }
-        if (model_pass) ks_fixed = ksplit;
-    }
-    const bool big = bp == 256;
-    int tag = (small_n ? 64 : 128) * 10000 + bp * 10 + d->dtype + (dil > 1 ? 5 : 0);   // (last digit 5-7: a dilated layer, always this kernel)
     ProfBracket prof(ctx, st);
-    int rc;
-    // big-tile kernel: one block per CU at a time, so the grid has to fill the chip several times and evenly (FPN P2: 2016 blocks on
-    // 256 CUs = 7.9 rounds; P3's 528 blocks would run 3 rounds for 2.06 of work: 0.45 ms against 0.34 ms with the generic kernel)
-    long long bt_blocks = 0;
-    if (bt_eligible(ctx, d)) bt_tile_twl(p, &bt_blocks);
-    const long long ncu = ctx_num_cu(ctx), bt_rounds = cdiv_ll(bt_blocks, ncu);
-    const bool bt_fits = ctx->dbg_bt >= 2 ? bt_blocks * 2 >= 3 * ncu : (bt_blocks * 100 >= (long long)ctx->dbg_bt_min * ncu && bt_blocks * 100 >= bt_rounds * ncu * 95);   // (3.9: conv_rpn_fpn2 at 4 clips is 1 008 blocks on 256 CUs)
-    const bool mask_mode = d->res_mode >= 3;     // the masking combines (3: mask, 4: in-place sum + mask) live in the generic kernel and the lw / ks 1x1 kernels
-    if (bt_fits && ksplit == 1 && !force_bp && !force_ks && !mask_mode) {
-        tag = 256 * 10000 + 2560 + d->dtype;
-        rc = launch_bt(ctx, st, p);
-    } else if (pw256_eligible(ctx, d) && !force_bp && !force_ks && !mask_mode) {
-        tag = 256 * 10000 + 320 + d->dtype;     // (256 channels x 32 positions per wave: the weights-stationary 1x1 kernel)
-        rc = launch_pw256(ctx, st, p);
-    } else if (pwks_eligible(ctx, d) && !force_bp && !force_ks) {       // (its epilogue knows the masking combine too)
-        tag = 256 * 10000 + 340 + d->dtype;     // (the K-streaming 1x1 kernel: 256 positions x 256 channels per block)
-        rc = launch_pwks(ctx, st, p);
-    } else if (tks_eligible(ctx, d) && !force_bp && !force_ks) {
-        tag = 256 * 10000 + 350 + d->dtype;     // (the temporal-tap K-streaming kernel: kT x 1 x 1, 256 positions x 256 channels per block)
-        rc = launch_tks(ctx, st, p);
-    } else if (pwlw_eligible(ctx, d) && !force_bp && !force_ks && d->res_mode != 3) {   // (knows the sum + mask combine; plain mask layers -- K >= 512 data
-                                                                                        //  gradients of `branch2c` on small maps -- measured faster on the generic kernel)
-        tag = 256 * 10000 + 330 + d->dtype;     // (the weights-in-LDS 1x1 kernel: 32 positions per wave tile)
-        rc = launch_pwlw(ctx, st, p, d);
-    } else if (ws64_eligible(ctx, d) && !force_bp && !force_ks && !mask_mode) {
-        tag = 64 * 10000 + 9990 + d->dtype;    // ("999 positions": the persistent weights-stationary kernel)
-        rc = launch_ws64(ctx, st, p);
-    } else {   // the implicit-GEMM kernel: weights straight into the MFMA registers
-        // unrolled-tap variants: dense 3x3 (stride 1) and 1x1 (any stride: one tap, one plane); the patch must fit the per-wave
-        // piece registers (tile shapes with very long rows fall back to the table-driven loop).  1x1 layers with a large output
-        // grid are bandwidth-bound and do better with the leaner table-driven loop (one block more per CU), measured.
-        const TileChoice tc = choose_tile(p.Ho, p.Wo, big ? 8 : 7, p.sh, p.sw, (p.KH - 1) * dil + 1, (p.KW - 1) * dil + 1);
-        // (a dilated 3x3 keeps the unrolled variant while its wider patch fits the piece registers -- < 64 KiB, so the packed 16-bit
-        //  addresses hold too; beyond that it takes the table-driven loop)
-        const long long prow = ((1ll << tc.th_log2) + (p.KH - 1) * dil / p.sh) * ((1ll << tc.tw_log2) + (p.KW - 1) * dil / p.sw);
-        const bool fits = ((prow * 8 + 63) >> 6) <= 4 * patch_pieces_per_wave(9, big ? 256 : 128);
-        const bool pw_small = (long long)p.frames * p.Ho * p.Wo <= 65536;
-        // strided 3x3: ONE dense patch of (2*TH+1) x (2*TW+1) cells serves all 9 taps (the table-driven loop stages four stride-parity
-        // patches per channel chunk and synchronises around each); 128-position tiles only (the patch is 70 KiB: two blocks per CU)
-        const long long drow = (((1ll << tc.th_log2) - 1) * p.sh + p.KH) * (((1ll << tc.tw_log2) - 1) * p.sw + p.KW);
-        const bool dense2 = ctx->dbg_ntap && !big && d->KH == 3 && d->KW == 3 && d->stride_h == 2 && d->stride_w == 2 && !(ctx->dbg_ntap & 4) &&
-                            ((drow * 8 + 63) >> 6) <= 4 * 19;
-        const int ntapv = dense2 ? 10 : !ctx->dbg_ntap || !fits ? 0 : (d->KH == 3 && d->KW == 3 && d->stride_h == 1 && d->stride_w == 1) ? 9 :
-                          (d->KH == 1 && d->KW == 1 && (pw_small || (ctx->dbg_ntap & 2))) ? 1 : 0;
-        // small maps (RoI heads): linear position tiling when it saves >= 10 % of the tiles (see launch_conv)
-        bool lin = false;
-        const long long tlin = ntapv == 9 ? linear_tiles(ctx, d, p, big ? 256 : 128) : 0;
-        if (tlin > 0) {
-            const long long t2d = (long long)p.frames * cdiv_ll(p.Ho, 1ll << tc.th_log2) * cdiv_ll(p.Wo, 1ll << tc.tw_log2);
-            lin = tlin * 10 <= t2d * 9;
-        }
-#define DAT_CONV_LAUNCH(DT_, BN_, WN_, ODT_) (lin && dil > 1 ? (big ? launch_conv<DT_, BN_, 256, WN_, 19, ODT_>(ctx, st, p, 8, ksplit, lin, dil) : launch_conv<DT_, BN_, 128, WN_, 19, ODT_>(ctx, st, p, 7, ksplit, lin, dil)) : ntapv == 10 ? launch_conv<DT_, BN_, 128, WN_, 10, ODT_>(ctx, st, p, 7, ksplit) : ntapv == 9 ? (big ? launch_conv<DT_, BN_, 256, WN_, 9, ODT_>(ctx, st, p, 8, ksplit, lin, dil) : launch_conv<DT_, BN_, 128, WN_, 9, ODT_>(ctx, st, p, 7, ksplit, lin, dil)) \
-                            : ntapv == 1 ? (big ? launch_conv<DT_, BN_, 256, WN_, 1, ODT_>(ctx, st, p, 8, ksplit) : launch_conv<DT_, BN_, 128, WN_, 1, ODT_>(ctx, st, p, 7, ksplit)) \
-                            : (big ? launch_conv<DT_, BN_, 256, WN_, 0, ODT_>(ctx, st, p, 8, ksplit, false, dil) : launch_conv<DT_, BN_, 128, WN_, 0, ODT_>(ctx, st, p, 7, ksplit, false, dil)))
-        // DAT_CONV_MFMA=1: the bf16 128-channel dense 3x3 variants (2-D tiles, linear strips, split-K) on 16x16x32, like the big-tile kernel
-        if (ctx->dbg_mfma && ntapv == 9 && !x3 && !small_n && d->dtype == DAT_BF16 && !(lin && dil > 1))   // (dilated strips: 32x32x16 only)
-            rc = big ? launch_conv<DAT_BF16, 128, 256, 2, 9, DAT_BF16, 1>(ctx, st, p, 8, ksplit, lin, dil) : launch_conv<DAT_BF16, 128, 128, 2, 9, DAT_BF16, 1>(ctx, st, p, 7, ksplit, lin, dil);
-        else if (x3) rc = small_n ? DAT_CONV_LAUNCH(DAT_BF16, 64, 1, DAT_F32) : DAT_CONV_LAUNCH(DAT_BF16, 128, 2, DAT_F32);
-        else if (small_n) rc = d->dtype == DAT_BF16 ? DAT_CONV_LAUNCH(DAT_BF16, 64, 1, DAT_BF16) : DAT_CONV_LAUNCH(DAT_F32, 64, 1, DAT_F32);
-        else rc = d->dtype == DAT_BF16 ? DAT_CONV_LAUNCH(DAT_BF16, 128, 2, DAT_BF16) : DAT_CONV_LAUNCH(DAT_F32, 128, 2, DAT_F32);
-#undef DAT_CONV_LAUNCH
-    }
-    prof.end(2.0 * d->Cout * d->Cin * d->KT * d->KH * d->KW * (double)p.frames * p.Ho * p.Wo, tag);
+    rc = conv_launch(ctx, st, p, plan, conv_dilation(d));
+    prof.end(2.0 * d->Cout * d->Cin * d->KT * d->KH * d->KW * (double)p.frames * p.Ho * p.Wo, plan.tag);
     return rc;
+}
+
+int dat_conv3d_plan(dat_ctx* ctx, const dat_conv_desc* d, int num_cu, dat_conv_plan* out) {
+    if (!d || !out || num_cu < 0 || (!ctx && num_cu == 0)) return DAT_ERR_ARG;
+    dat_ctx env{};                  // ctx == NULL: nothing but the knobs, as dat_ctx_create reads them
+    if (!ctx) dat_ctx_read_env(&env);
+    dat_ctx* c = ctx ? ctx : &env;
+    char none = 0, why[256];        // (`none` stands for the tensors: validation only asks whether they are there)
+    ConvParams p;
+    int rc = conv_validate(c, d, &none, &none, nullptr, nullptr, &none, &none, nullptr, &none, p);
+    if (rc != DAT_OK) return rc;
+    rc = conv_plan(c, num_cu ? num_cu : ctx_num_cu(ctx), d, p, out, why);
+    if (rc != DAT_OK) DAT_FAIL(c, rc, "%s", why);
+    return DAT_OK;
 }
 
 int dat_conv3d_persistent_share(dat_ctx* ctx, int percent) {

@@ -1,6 +1,6 @@
-// Internal header of the conv translation units (conv3d_igemm.hip: the generic implicit-GEMM kernel, its plan, the dispatcher and the
-// launch prologue helpers below; conv_special.hip: the weights-stationary, K-streaming and big-tile kernels; conv_grouped.hip: the grouped
-// kernel; conv_pack.hip: weight packing).  conv_epilogue.h, included below, holds the device pieces the kernels share.  Not part of the C ABI.
+// Internal header of the conv translation units (conv3d_igemm.hip: the generic implicit-GEMM kernel, the launch plan of every dense forward
+// (conv_plan -> ConvPlan, below) and the launch prologue helpers below; conv_special.hip: the weights-stationary, K-streaming and big-tile
+// kernels with their eligibility rules; conv_grouped.hip: the grouped kernel and its own plan; conv_pack.hip: weight packing).  conv_epilogue.h, included below, holds the device pieces the kernels share.  Not part of the C ABI.
 #ifndef DAT_CONV_INTERNAL_H
 #define DAT_CONV_INTERNAL_H
 
@@ -186,21 +186,32 @@ struct ProfBracket {
     }
 };
 
-// conv_special.hip
+// What a dense conv launch does with a descriptor, and nothing about its tensors (the C ABI's dat_conv_plan: dat_conv3d_plan shows it).
+// conv_plan (conv3d_igemm.hip) derives it once per launch from the context's knobs, the CU count and the descriptor; the launchers below
+// take their tile, split-K factor and grid from it.
+typedef dat_conv_plan ConvPlan;
+
+// conv_special.hip: what each special kernel assumes about a layer (its grid rule included: `num_cu` compute units), the tile / grid
+// it would run, and its launcher
 int ctx_num_cu(dat_ctx* ctx);
 bool ws64_eligible(const dat_ctx* ctx, const dat_conv_desc* d);
-int launch_ws64(dat_ctx* ctx, hipStream_t st, const ConvParams& cp);
+int ws64_tile_twl(const dat_ctx* ctx, int num_cu, const ConvParams& p, long long* ntiles);
+long long ws64_grid(const dat_ctx* ctx, int num_cu, long long ntiles);
+int launch_ws64(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const ConvPlan& plan);
 bool pw256_eligible(const dat_ctx* ctx, const dat_conv_desc* d);
-int launch_pw256(dat_ctx* ctx, hipStream_t st, const ConvParams& cp);
-bool pwlw_eligible(dat_ctx* ctx, const dat_conv_desc* d);
-int launch_pwlw(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const dat_conv_desc* d);
-bool pwks_eligible(dat_ctx* ctx, const dat_conv_desc* d);
-int launch_pwks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp);
-bool tks_eligible(dat_ctx* ctx, const dat_conv_desc* d);
-int launch_tks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp);
+long long pw256_grid(const dat_ctx* ctx, int num_cu, const ConvParams& cp);
+int launch_pw256(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const ConvPlan& plan);
+bool pwlw_eligible(const dat_ctx* ctx, int num_cu, const dat_conv_desc* d);
+long long pwlw_grid(const dat_ctx* ctx, int num_cu, const ConvParams& cp);
+int launch_pwlw(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const ConvPlan& plan);
+bool pwks_eligible(const dat_ctx* ctx, int num_cu, const dat_conv_desc* d);
+bool tks_eligible(const dat_ctx* ctx, int num_cu, const dat_conv_desc* d);
+long long ks_grid(const ConvParams& cp);
+int launch_pwks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const ConvPlan& plan);
+int launch_tks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const ConvPlan& plan);
 bool bt_eligible(const dat_ctx* ctx, const dat_conv_desc* d);
 int bt_tile_twl(const ConvParams& p, long long* nblocks);
-int launch_bt(dat_ctx* ctx, hipStream_t st, ConvParams& p);
+int launch_bt(dat_ctx* ctx, hipStream_t st, ConvParams& p, const ConvPlan& plan);
 
 // train_ops.hip: dW[co][ci][tap] = scale[co] * Gt[tap][co][ci] (wgrad_finish_kernel; scale NULL = 1)
 int launch_wgrad_finish(dat_ctx* ctx, hipStream_t st, const float* Gt, const float* scale, float* dW, int Cout, int Cin, int ntaps);

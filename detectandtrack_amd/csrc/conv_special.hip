@@ -1201,9 +1201,8 @@ bool ws64_eligible(const dat_ctx* ctx, const dat_conv_desc* d) {
 
 // CUs a persistent HBM-bound kernel (one block per CU) takes: all of them, or DAT_PERSIST_PCT percent (an experiment: does leaving CUs to the
 // other forwards' MFMA kernels raise the step rate?), rounded down to a multiple of `mult`
-int ctx_num_cu(dat_ctx* ctx);
-static long long persist_cus(dat_ctx* ctx, int mult) {
-    long long n = ctx_num_cu(ctx);
+static long long persist_cus(const dat_ctx* ctx, int num_cu, int mult) {
+    long long n = num_cu;
     if (ctx->dbg_persist_pct > 0 && ctx->dbg_persist_pct < 100) n = std::max<long long>(mult, n * ctx->dbg_persist_pct / 100 / mult * mult);
     return n;
 }
@@ -1234,9 +1233,9 @@ int bt_tile_twl(const ConvParams& p, long long* nblocks) {
     return best;
 }
 
-int launch_bt(dat_ctx* ctx, hipStream_t st, ConvParams& p) {
-    long long nblocks = 0;
-    const int twl = bt_tile_twl(p, &nblocks);
+int launch_bt(dat_ctx* ctx, hipStream_t st, ConvParams& p, const ConvPlan& plan) {
+    const long long nblocks = plan.blocks;
+    const int twl = plan.twl;
     const int tw = 1 << twl, th = 256 >> twl;
     p.th_log2 = 8 - twl; p.tw_log2 = twl; p.tile_w = tw;
     p.tiles_h = (int)cdiv_ll(p.Ho, th); p.tiles_w = (int)cdiv_ll(p.Wo, tw);
@@ -1274,7 +1273,11 @@ bool pw256_eligible(const dat_ctx* ctx, const dat_conv_desc* d) {
            (long long)d->frames * d->H * d->W * std::max(d->out_cstride, 64) * 2 < (1ll << 32);
 }
 
-int launch_pw256(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
+long long pw256_grid(const dat_ctx* ctx, int num_cu, const ConvParams& cp) {
+    return std::min<long long>(cdiv_ll(cdiv_ll((long long)cp.frames * cp.H * cp.W, 32), 4), persist_cus(ctx, num_cu, 8));
+}
+
+int launch_pw256(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const ConvPlan& plan) {
     Pw256Params p;
     p.x = cp.x; p.w = cp.w; p.scale = cp.scale; p.bias = cp.bias; p.res = cp.res; p.y = cp.y;
     p.npos = (long long)cp.frames * cp.H * cp.W;
@@ -1284,7 +1287,7 @@ int launch_pw256(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
     p.ntiles = (int)ntiles;
     p.hw = (unsigned)(cp.H * cp.W);
     p.w_magic = cp.W == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)cp.W - 1) / (unsigned)cp.W);
-    const unsigned grid = (unsigned)std::min<long long>(cdiv_ll(ntiles, 4), persist_cus(ctx, 8));
+    const unsigned grid = (unsigned)plan.blocks;
     const size_t lds = (size_t)4 * 32 * (256 * 4 + 16);
     if (dat_ensure_lds(ctx, (const void*)conv1x1_k64_c256_ws_kernel, 160 * 1024) != DAT_OK) return DAT_ERR_LAUNCH;
     hipLaunchKernelGGL(conv1x1_k64_c256_ws_kernel, dim3(grid), dim3(NTHREADS), lds, st, p);
@@ -1294,20 +1297,20 @@ int launch_pw256(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
 
 // weights-in-LDS 1x1 kernel (conv1x1_lw_kernel): layers whose weights fit LDS in <= 4 cout parts and that have enough positions
 // for a persistent grid to amortise the weight copy (>= 2 wave tiles per wave)
-static int lw_nsplit(const dat_conv_desc* d) {
-    const long long wbytes = (long long)d->Cin * cout_pad_of(d) * 2;
+static int lw_nsplit(int Cin, int Cout_pad) {
+    const long long wbytes = (long long)Cin * Cout_pad * 2;
     int ns = 1;
     while (wbytes / ns > 128 * 1024) ns *= 2;
     return ns;
 }
 
-bool pwlw_eligible(dat_ctx* ctx, const dat_conv_desc* d) {
+bool pwlw_eligible(const dat_ctx* ctx, int num_cu, const dat_conv_desc* d) {
     if (!(ctx->dbg_pwlw && d->dtype == DAT_BF16 && d->KT == 1 && d->KH == 1 && d->KW == 1 && d->pad_h == 0 && d->pad_w == 0 && d->pad_t == 0 &&
           d->out_tn <= 0 && d->stride_h == d->stride_w && (d->stride_h == 1 || d->stride_h == 2)))
         return false;
     const int kc = d->Cin / 64;
     if (d->Cin % 64 || !(kc == 1 || kc == 2 || kc == 4 || kc == 8)) return false;
-    const int ns = lw_nsplit(d), mbt = cout_pad_of(d) / 32;
+    const int ns = lw_nsplit(d->Cin, cout_pad_of(d)), mbt = cout_pad_of(d) / 32;
     if (ns > 4 || mbt % ns) return false;
     const int mbp = mbt / ns;
     if (!(mbp == 2 || mbp == 4 || mbp == 8 || mbp == 16) || (kc == 8 && mbp > 4)) return false;
@@ -1319,7 +1322,7 @@ bool pwlw_eligible(dat_ctx* ctx, const dat_conv_desc* d) {
     if ((long long)Ho * Wo < 32 || (long long)Ho * Wo * Wo >= (1ll << 32)) return false;
     if (npos >= (1ll << 31) || (long long)d->frames * d->H * d->W >= (1ll << 31)) return false;
     // enough work per wave: 256 CUs x 4 waves, at least 2 tiles each per cout part
-    return npos / 32 >= 2ll * 4 * ctx_num_cu(ctx) / ns;
+    return npos / 32 >= 2ll * 4 * num_cu / ns;
 }
 
 template <int KC, int MBW, int NPASS>
@@ -1334,7 +1337,13 @@ static int launch_pwlw_t(dat_ctx* ctx, hipStream_t st, const PwLwParams& p, unsi
     return DAT_OK;
 }
 
-int launch_pwlw(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const dat_conv_desc* d) {
+long long pwlw_grid(const dat_ctx* ctx, int num_cu, const ConvParams& cp) {
+    const int ns = lw_nsplit(cp.Cin, cp.Cout_pad);
+    const long long ntiles = cdiv_ll((long long)cp.frames * cp.Ho * cp.Wo, 32);
+    return std::min<long long>(cdiv_ll(ntiles, 4), persist_cus(ctx, num_cu, 8 * ns) / ns) * ns;
+}
+
+int launch_pwlw(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const ConvPlan& plan) {
     PwLwParams p;
     p.x = cp.x; p.w = cp.w; p.scale = cp.scale; p.bias = cp.bias; p.res = cp.res; p.y = cp.y; p.res2 = cp.res2;
     p.npos = (unsigned)((long long)cp.frames * cp.Ho * cp.Wo);
@@ -1343,11 +1352,10 @@ int launch_pwlw(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const dat_co
     p.ntiles = (int)cdiv_ll(p.npos, 32);
     p.how = (unsigned)(cp.Ho * cp.Wo);
     p.wo_magic = cp.Wo == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)cp.Wo - 1) / (unsigned)cp.Wo);
-    p.nsplit = lw_nsplit(d); p.mb_total = cp.Cout_pad / 32;
+    p.nsplit = lw_nsplit(cp.Cin, cp.Cout_pad); p.mb_total = cp.Cout_pad / 32;
     const int kc = cp.Cin / 64, mbp = p.mb_total / p.nsplit;
     const int mbw = kc <= 4 ? std::min(mbp, 8) : std::min(mbp, 4), npass = mbp / mbw;
-    const long long per_part = std::min<long long>(cdiv_ll(p.ntiles, 4), persist_cus(ctx, 8 * p.nsplit) / p.nsplit);
-    const unsigned grid = (unsigned)(per_part * p.nsplit);
+    const unsigned grid = (unsigned)plan.blocks;
     p.xcd = ctx->dbg_pw_xcd && p.nsplit > 1 && grid % (8u * (unsigned)p.nsplit) == 0;
     const size_t lds = (size_t)kc * mbp * 4096 + (size_t)mbp * 32 * 8 + 4 * 32 * (32 * 4 + 16);
     DAT_ENFORCE(ctx, lds <= 160 * 1024, "conv1x1_lw: %zu bytes of LDS", lds);
@@ -1366,7 +1374,7 @@ int launch_pwlw(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const dat_co
 // K-streaming 1x1 kernel: K >= 512 (DAT_CONV_PWKS chunks of 64; same-box A/B of the R-50 forward, round 6: off 175.6, K >= 1024 179.0, K >= 512
 // 180.8 clips/s -- the K = 512 layers it takes from the weights-in-LDS kernel are the ones that needed two cout parts there), cout a multiple
 // of 256 after padding, enough 256-position tiles to give most CUs a block (one block per CU at a time: all 160 KB of LDS)
-bool pwks_eligible(dat_ctx* ctx, const dat_conv_desc* d) {
+bool pwks_eligible(const dat_ctx* ctx, int num_cu, const dat_conv_desc* d) {
     if (!(ctx->dbg_pwks > 0 && d->dtype == DAT_BF16 && d->KT == 1 && d->KH == 1 && d->KW == 1 && d->pad_h == 0 && d->pad_w == 0 && d->pad_t == 0 &&
           d->out_tn <= 0 && d->stride_h == d->stride_w && (d->stride_h == 1 || d->stride_h == 2)))
         return false;
@@ -1378,10 +1386,13 @@ bool pwks_eligible(dat_ctx* ctx, const dat_conv_desc* d) {
     if ((long long)Ho * Wo < 1 || (long long)Ho * Wo * Wo >= (1ll << 32)) return false;
     if (npos >= (1ll << 31) || (long long)d->frames * d->H * d->W >= (1ll << 31)) return false;
     const long long blocks = cdiv_ll(npos, 256) * (cout_pad_of(d) / 256);
-    return npos >= 256 && blocks * 4 >= 3ll * ctx_num_cu(ctx);
+    return npos >= 256 && blocks * 4 >= 3ll * num_cu;
 }
 
-int launch_pwks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
+// grid of the two K-streaming kernels: 256 positions x 256 channels per block
+long long ks_grid(const ConvParams& cp) { return cdiv_ll((long long)cp.frames * cp.Ho * cp.Wo, 256) * (cp.Cout_pad / 256); }
+
+int launch_pwks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const ConvPlan& plan) {
     PwKsParams p;
     p.x = cp.x; p.w = cp.w; p.scale = cp.scale; p.bias = cp.bias; p.res = cp.res; p.y = cp.y; p.res2 = cp.res2;
     p.npos = (unsigned)((long long)cp.frames * cp.Ho * cp.Wo);
@@ -1392,7 +1403,7 @@ int launch_pwks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
     p.wo_magic = cp.Wo == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)cp.Wo - 1) / (unsigned)cp.Wo);
     p.ablate = ctx->dbg_ablate;
     p.xcd = ctx->dbg_pw_xcd && p.ncb > 1;
-    const long long blocks = cdiv_ll(p.npos, 256) * p.ncb;
+    const long long blocks = plan.blocks;
     DAT_ENFORCE(ctx, blocks > 0 && blocks < (1ll << 31), "conv1x1_ks: grid of %lld blocks unsupported", blocks);
     const size_t lds = (size_t)3 * KS_XBYTES + 2 * KS_WBYTES;     // 160 KB: three input buffers, two weight buffers (the epilogue reuses them)
     if (dat_ensure_lds(ctx, (const void*)conv1x1_ks_kernel, 160 * 1024) != DAT_OK) return DAT_ERR_LAUNCH;
@@ -1408,7 +1419,7 @@ int launch_pwks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
 // layers at one clip (64-126 blocks: under one block per CU the generic kernel's 2-4x more blocks win), so it takes grids of >= 3/4
 // block per CU; Cout 128 (res3) measured slower at every size and stays generic (Cout must pad to a multiple of 256).
 // DAT_CONV_TEMPORAL=2 drops the grid rule (tests, the probe).
-bool tks_eligible(dat_ctx* ctx, const dat_conv_desc* d) {
+bool tks_eligible(const dat_ctx* ctx, int num_cu, const dat_conv_desc* d) {
     if (!(ctx->dbg_temporal > 0 && DAT_H16_FORMAT == 0 && d->dtype == DAT_BF16 && d->KT > 1 && d->KH == 1 && d->KW == 1 && d->pad_h == 0 &&
           d->pad_w == 0 && d->pad_t * 2 + 1 == d->KT && d->out_tn <= 0 && d->in_tn <= 0 && d->stride_h == 1 && d->stride_w == 1 &&
           (d->res_mode == 0 || d->res_mode == 1)))
@@ -1418,10 +1429,10 @@ bool tks_eligible(dat_ctx* ctx, const dat_conv_desc* d) {
     const long long how = (long long)d->H * d->W, npos = (long long)d->frames * how;
     if (how < 1 || npos >= (1ll << 31) || npos * d->Cin >= (1ll << 40)) return false;
     const long long blocks = cdiv_ll(npos, 256) * (cout_pad_of(d) / 256);
-    return npos >= 256 && (ctx->dbg_temporal >= 2 || blocks * 4 >= 3ll * ctx_num_cu(ctx));
+    return npos >= 256 && (ctx->dbg_temporal >= 2 || blocks * 4 >= 3ll * num_cu);
 }
 
-int launch_tks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
+int launch_tks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const ConvPlan& plan) {
     TkParams p;
     p.x = cp.x; p.w = cp.w; p.scale = cp.scale; p.bias = cp.bias; p.res = cp.res; p.zeros = cp.zeros; p.y = cp.y;
     p.npos = (unsigned)((long long)cp.frames * cp.Ho * cp.Wo);
@@ -1430,7 +1441,7 @@ int launch_tks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
     p.in_cs = cp.Cin; p.out_cs = cp.out_cs; p.cout = cp.Cout; p.relu = cp.relu; p.res_mode = cp.res_mode;
     p.ncb = cp.Cout_pad / 256; p.ncc = cp.Cin / 64; p.kchunks = cp.KT * p.ncc; p.mb_total = cp.Cout_pad / 32;
     p.xcd = ctx->dbg_pw_xcd && p.ncb > 1;
-    const long long blocks = cdiv_ll(p.npos, 256) * p.ncb;
+    const long long blocks = plan.blocks;
     DAT_ENFORCE(ctx, blocks > 0 && blocks < (1ll << 31), "conv_kt1x1_ks: grid of %lld blocks unsupported", blocks);
     DAT_ENFORCE(ctx, cp.Ho == cp.H && cp.Wo == cp.W && cp.res_mode <= 1 && cp.Cout_pad % 256 == 0 && cp.zeros,
                 "conv_kt1x1_ks: unsupported call");
@@ -1441,29 +1452,35 @@ int launch_tks(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
     return DAT_OK;
 }
 
-int launch_ws64(dat_ctx* ctx, hipStream_t st, const ConvParams& cp) {
+// 8 x 32 or 16 x 16 positions per tile: fewest rounds of the persistent grid (ties: the smaller 16 x 16 patch)
+int ws64_tile_twl(const dat_ctx* ctx, int num_cu, const ConvParams& p, long long* ntiles) {
+    int best_twl = 4;
+    long long best_rounds = -1;
+    for (int twl = 4; twl <= 5; ++twl) {
+        if ((ctx->dbg_ws64 == 2 && twl != 5) || (ctx->dbg_ws64 == 3 && twl != 4)) continue;   // DEBUG: DAT_CONV_WS64=2 / 3 force 8x32 / 16x16
+        const int tw = 1 << twl, th = 256 >> twl;
+        const long long tiles = (long long)p.frames * cdiv_ll(p.H, th) * cdiv_ll(p.W, tw);
+        const long long rounds = cdiv_ll(tiles, num_cu);
+        if (best_rounds < 0 || rounds < best_rounds) { best_rounds = rounds; best_twl = twl; *ntiles = tiles; }
+    }
+    return best_twl;
+}
+long long ws64_grid(const dat_ctx* ctx, int num_cu, long long ntiles) { return std::min<long long>(ntiles, persist_cus(ctx, num_cu, 8)); }
+
+int launch_ws64(dat_ctx* ctx, hipStream_t st, const ConvParams& cp, const ConvPlan& plan) {
     Ws64Params p;
     p.x = cp.x; p.w = cp.w; p.scale = cp.scale; p.bias = cp.bias; p.res = cp.res; p.y = cp.y; p.zeros = cp.zeros;
     p.frames = cp.frames; p.H = cp.H; p.W = cp.W; p.out_cs = cp.out_cs; p.relu = cp.relu; p.res_mode = cp.res_mode;
     p.ablate = ctx->dbg_ablate;
     DAT_ENFORCE(ctx, (long long)p.H * p.W * std::max(p.out_cs, 64) * 2 < (1ll << 31), "conv3d: frame of %dx%d exceeds 32-bit offsets", p.H, p.W);
-    // 8 x 32 or 16 x 16 positions per tile: fewest rounds of the persistent grid (ties: the smaller 16 x 16 patch)
-    int best_twl = 4;
-    long long best_rounds = -1, best_tiles = 0;
-    for (int twl = 4; twl <= 5; ++twl) {
-        if ((ctx->dbg_ws64 == 2 && twl != 5) || (ctx->dbg_ws64 == 3 && twl != 4)) continue;   // DEBUG: DAT_CONV_WS64=2 / 3 force 8x32 / 16x16
-        const int tw = 1 << twl, th = 256 >> twl;
-        const long long tiles = (long long)p.frames * cdiv_ll(p.H, th) * cdiv_ll(p.W, tw);
-        const long long rounds = cdiv_ll(tiles, ctx_num_cu(ctx));
-        if (best_rounds < 0 || rounds < best_rounds) { best_rounds = rounds; best_twl = twl; best_tiles = tiles; }
-    }
-    const int tw = 1 << best_twl, th = 256 >> best_twl;
+    const int best_twl = plan.twl, tw = 1 << best_twl, th = 256 >> best_twl;
     p.tiles_h = (int)cdiv_ll(p.H, th); p.tiles_w = (int)cdiv_ll(p.W, tw);
+    const long long best_tiles = (long long)p.frames * p.tiles_h * p.tiles_w;
     DAT_ENFORCE(ctx, best_tiles > 0 && best_tiles < (1ll << 31), "conv3d: %lld tiles unsupported", best_tiles);
     p.ntiles = (int)best_tiles;
     const int npiece = ((th + 2) * (tw + 2) * 8 + 63) / 64;
     const size_t lds = (size_t)2 * npiece * 1024 + EPI_SLICES_BYTES;
-    const unsigned grid = (unsigned)std::min<long long>(best_tiles, persist_cus(ctx, 8));
+    const unsigned grid = (unsigned)plan.blocks;
     if (best_twl == 5) {
         if (dat_ensure_lds(ctx, (const void*)conv3x3_c64_ws_kernel<5>, 160 * 1024) != DAT_OK) return DAT_ERR_LAUNCH;
         hipLaunchKernelGGL(conv3x3_c64_ws_kernel<5>, dim3(grid), dim3(NTHREADS), lds, st, p);

@@ -162,6 +162,8 @@ __device__ __forceinline__ T dat_pick(const T (&a)[N], int i) {
 
 // grow the ctx-owned scratch (synchronises + reallocates only when it must grow); defined in c_api.hip
 int dat_ensure_ws(dat_ctx* ctx, size_t bytes);
+// the DAT_* knobs of `ctx` from the environment, num_cu = 0 (not asked yet); defined in c_api.hip
+void dat_ctx_read_env(dat_ctx* ctx);
 
 static inline int dat_esize(int dtype) { return dtype == DAT_BF16 ? 2 : 4; }
 static inline long long cdiv_ll(long long a, long long b) { return (a + b - 1) / b; }

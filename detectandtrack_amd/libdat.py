@@ -33,6 +33,20 @@ class ConvDesc(C.Structure):
         'stride_h', 'stride_w', 'pad_t', 'pad_h', 'pad_w', 'relu', 'res_mode', 'out_t0', 'out_tn', 'in_t0', 'in_tn', 'plan_frames', 'dil_h', 'dil_w')]
 
 
+# dat_conv_plan.family
+CONV_GENERIC, CONV_BIGTILE, CONV_PW256, CONV_PWKS, CONV_TKS, CONV_PWLW, CONV_WS64 = range(7)
+
+
+class ConvPlan(C.Structure):
+    # what dat_conv3d_plan says a dense conv launch does with a descriptor (dat_conv_plan, include/dat_hip.h)
+    _fields_ = [(n, C.c_int) for n in (
+        'family', 'tag', 'blocks', 'twl', 'bn', 'bp', 'ksplit', 'npatch_min', 'ntap', 'linear', 'mfma', 'th_log2', 'tw_log2',
+        'patch_h', 'patch_w', 'in_dtype', 'out_dtype')]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class PackItem(C.Structure):
     _fields_ = [('w', C.c_void_p), ('packed', C.c_void_p), ('scale', C.c_void_p)] + \
                [(n, C.c_int) for n in ('rows', 'cols', 'ntap', 'cout_pad', 'cin', 'dgrad', 'dtype', 'tile0', 'tiles_x', 'cit')]
@@ -117,6 +131,7 @@ _PROTOS = {
     'dat_conv3d_fwd_x3': (_i, [_p, _p, C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _p]),
     'dat_conv3d_fwd_sum_mask': (_i, [_p, _p, C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _p]),
     'dat_conv3d_tune_plan': (_i, [_p, _i, _i]),
+    'dat_conv3d_plan': (_i, [_p, C.POINTER(ConvDesc), _i, C.POINTER(ConvPlan)]),
     'dat_conv3d_persistent_share': (_i, [_p, _i]),
     'dat_conv3d_flops': (_d, [C.POINTER(ConvDesc), _i, _i]),
     'dat_conv3d_grouped_packed_weight_bytes': (C.c_size_t, [C.POINTER(ConvDesc), _i]),

@@ -283,6 +283,14 @@ class ConvLayer(object):
             d.dil_h = d.dil_w = self.dilation
         return d
 
+    def plan(self, frames, T, H, W, num_cu=0, **desc_args):
+        """The launch plan the current context gives this layer at that shape (dat_conv3d_plan: kernel family, tag, tile, split-K
+        factor ...) as a dict; desc_args as for desc().  num_cu 0 = the device's CU count.  The grouped conv has its own plan."""
+        assert self.groups == 1, 'dat_conv3d_plan describes the dense conv launches'
+        d, out = self.desc(frames, T, H, W, **desc_args), L.ConvPlan()
+        ctx().call('dat_conv3d_plan', C.byref(d), int(num_cu), C.byref(out))
+        return out.as_dict()
+
     def out_hw(self, H, W):
         dl = self.dilation if (self.kh > 1 or self.kw > 1) else 1
         return ((H + 2 * self.pads[1] - dl * (self.kh - 1) - 1) // self.stride[0] + 1,

@@ -458,6 +458,36 @@ int dat_kps_finalize(dat_ctx* ctx, dat_stream s, int dtype, const void* sub, int
  * Per-context state (no process globals): other contexts / devices of the process are unaffected.  Used by
  * tools/tune_plan.py to check the model against measured per-layer timings. */
 int dat_conv3d_tune_plan(dat_ctx* ctx, int positions_per_block, int ksplit);
+/* The launch plan of a dat_conv3d_fwd / _fwd_x3 / _fwd_sum_mask call: which kernel runs a descriptor, and how.  A pure function of the
+ * context's knobs, the CU count and the descriptor -- it makes no HIP call and needs no GPU. */
+enum { DAT_CONV_GENERIC = 0,   /* the implicit-GEMM kernel; the fields from bn to out_dtype describe its variant */
+       DAT_CONV_BIGTILE = 1,   /* 3x3, 256 channels x 256 positions per block */
+       DAT_CONV_PW256 = 2,     /* weights-stationary 1x1 64 -> 256 */
+       DAT_CONV_PWKS = 3,      /* K-streaming 1x1 */
+       DAT_CONV_TKS = 4,       /* temporal-tap K-streaming kT x 1 x 1 */
+       DAT_CONV_PWLW = 5,      /* weights-in-LDS 1x1 */
+       DAT_CONV_WS64 = 6 };    /* weights-stationary persistent 3x3 64 -> 64 */
+typedef struct dat_conv_plan {
+    int family;              /* DAT_CONV_* above */
+    int tag;                 /* what dat_prof_read reports for the launch: channels per block * 10000 + positions per block * 10 + dtype
+                                (+ 5: a dilated layer); the special kernels carry 2560 / 320 / 340 / 350 / 330 / 9990 as their "positions" */
+    int blocks;              /* thread blocks of the launch (the persistent kernels: after the context's CU share) */
+    int twl;                 /* big-tile and ws64: the tile is (256 >> twl) x (1 << twl) positions; 0 otherwise */
+    /* the generic kernel only (0 for the others) */
+    int bn, bp;              /* output channels (64 | 128) and positions (128 | 256) per block */
+    int ksplit;              /* split-K factor, 1 <= ksplit <= npatch_min; > 1: fp32 partials and a splitk_finish launch */
+    int npatch_min;          /* the bound: (KT > 1 ? KT - 1 : 1) * channel chunks */
+    int ntap;                /* tap variant: 0 table-driven | 1 | 9 | 10 dense stride-2 patch | 19 dilated strips */
+    int linear;              /* 1: linear strips of bp consecutive positions instead of 2-D tiles */
+    int mfma;                /* 0: 32x32x16 (fp32: 32x32x2) | 1: 16x16x32 */
+    int th_log2, tw_log2;    /* the tile: 2^th x 2^tw positions (strips: 1 x bp) */
+    int patch_h, patch_w;    /* LDS patch rows x columns of 128 bytes */
+    int in_dtype, out_dtype; /* DAT_F32 | DAT_BF16: the kernel's operand and output element types (bf16x3: DAT_BF16 in, DAT_F32 out) */
+} dat_conv_plan;
+/* ctx != NULL: the plan that context's next launch of `d` takes (its knobs, dat_conv3d_tune_plan included); num_cu 0 = the device's.
+ * ctx == NULL: the knobs as dat_ctx_create reads them from the environment, and num_cu > 0 compute units.  Returns what the launch would
+ * return for a descriptor it refuses. */
+int dat_conv3d_plan(dat_ctx* ctx, const dat_conv_desc* d, int num_cu, dat_conv_plan* out);
 /* Engine hook (not a reference interface): the share of the CUs the PERSISTENT HBM-bound conv kernels (one block per CU: res2's 3x3
  * convs, the 64 -> 256 lateral, the weights-in-LDS 1x1 kernel) launched ON THIS CONTEXT take, 1..100 percent (default 100, or
  * DAT_PERSIST_PCT).  An engine that keeps several forwards in flight on their own streams lowers it so that the other forwards'
