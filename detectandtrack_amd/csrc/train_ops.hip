@@ -1247,6 +1247,25 @@ size_t dat_conv3d_wgrad_workspace_bytes(const dat_conv_desc* d, int Cin_real, in
            (size_t)Cout_real * Cin_real * d->KT * d->KH * d->KW * sizeof(float);
 }
 
+// ---- the dense weight gradient in three steps: wgrad_validate, wgrad_plan, wgrad_launch -----------------------------------------------------
+// What a launch does with a layer, and nothing about its tensors (the C ABI's dat_wgrad_plan: dat_conv3d_wgrad_plan shows it)
+typedef dat_wgrad_plan WgradPlan;
+
+// ---- the kernel families: one predicate each ----
+// nine spatial taps from one staged patch (wgrad_dma9_kernel): 3 x 3, stride 1, pad 1
+// (a dilated 3 x 3 is not a nine-tap layer: that kernel's 10 x 10 patch holds the taps one row / column away)
+static bool wgrad_nine_tap(const dat_ctx* ctx, const dat_conv_desc* d) {
+    return d->KH == 3 && d->KW == 3 && d->stride_h == 1 && d->pad_h == 1 && d->pad_w == 1 && (ctx->dbg_wgrad_direct & 2) == 0 &&
+           dat_conv::conv_dilation(d) == 1;
+}
+
+// pointwise layers (1 x 1 x 1 convs, FC; stride 1 | 2): eight-wave blocks, 64 K accumulators per tile (wgrad_pw_kernel)
+static bool wgrad_pointwise(const dat_ctx* ctx, const dat_conv_desc* d) {
+    return d->KT == 1 && d->KH == 1 && d->KW == 1 && d->pad_h == 0 && d->pad_w == 0 && d->pad_t == 0 && ctx->dbg_wgrad_pw;
+}
+
+// 16-bit: the kernels that read the NDHWC tensors themselves (no re-pack passes; transposing LDS reads) -- the two above and, for every
+// other layer this accepts, wgrad_direct_kernel
 static bool wgrad_direct_eligible(const dat_ctx* ctx, const dat_conv_desc* d, int g_cstride) {
     int Ho, Wo;
     dat_conv3d_out_shape(d, &Ho, &Wo);
@@ -1256,11 +1275,8 @@ static bool wgrad_direct_eligible(const dat_ctx* ctx, const dat_conv_desc* d, in
     // map the same way, as ONE row of Ho columns (column_strip below) -- possible when the layer has no spatial taps, i.e. no bound to check
     // across the relabelled axis; a layer WITH spatial taps on such a map (3 x 3 at stride 2 on a map one or two columns wide) takes the
     // re-pack kernels.  The nine-tap kernel walks 8 x 8 patches and has no such split.
-    // (a dilated 3 x 3 is not a nine-tap layer: that kernel's 10 x 10 patch holds the taps one row / column away)
-    const bool nine_tap = d->KH == 3 && d->KW == 3 && d->stride_h == 1 && d->pad_h == 1 && d->pad_w == 1 && (ctx->dbg_wgrad_direct & 2) == 0 &&
-                          dat_conv::conv_dilation(d) == 1;
     const bool no_spatial_taps = d->KH == 1 && d->KW == 1 && d->pad_h == 0 && d->pad_w == 0;
-    if (Wo == 1 && Ho > 1 && !nine_tap && !no_spatial_taps) return false;
+    if (Wo == 1 && Ho > 1 && !wgrad_nine_tap(ctx, d) && !no_spatial_taps) return false;
     // (the multiply-high is exact while position-in-frame x divisor < 2^32; the relabelled strip divides its positions, < Ho, by Ho)
     const long long split_range = Wo == 1 ? (long long)Ho * Ho : (long long)Ho * Wo * Wo;
     return d->dtype == DAT_BF16 && ctx->dbg_wgrad_direct && d->Cin % 64 == 0 && g_cstride % 64 == 0 && npos_out < (1ll << 31) && npos_in < (1ll << 31) &&
@@ -1280,39 +1296,88 @@ static void column_strip(int* Ho, int* Wo, int* H, int* W, int* stride) {
     *H = 1;
 }
 
-// ---- pointwise layers: plan (tile shape, geometry) and grouped launch ------------------------------------------------------------
-struct PwPlan {
-    WgradPwItem it;
-    long long tiles, nchunks;
-};
-
-static bool pw_eligible(const dat_ctx* ctx, const dat_conv_desc* d) {
-    return d->KT == 1 && d->KH == 1 && d->KW == 1 && d->pad_h == 0 && d->pad_w == 0 && d->pad_t == 0 && ctx->dbg_wgrad_pw;
+// ---- validate: everything the entry points refuse about a layer (null pointers aside), before anything is launched or zeroed ----
+// acc_mode: the deferred-finish entry points, which have only the direct kernels
+static int wgrad_validate(dat_ctx* ctx, const dat_conv_desc* d, int g_cstride, int acc_mode, const char* who) {
+    DAT_ENFORCE(ctx, d->dtype == DAT_F32 || d->dtype == DAT_BF16, "%s: bad dtype %d", who, d->dtype);
+    DAT_ENFORCE(ctx, d->stride_h == d->stride_w && (d->stride_h == 1 || d->stride_h == 2), "%s: stride %dx%d", who, d->stride_h, d->stride_w);
+    DAT_ENFORCE(ctx, d->T > 0 && d->frames % d->T == 0 && d->pad_t * 2 + 1 == d->KT, "%s: needs same-T convs", who);
+    DAT_ENFORCE(ctx, d->KT * d->KH * d->KW <= 32, "%s: %d taps exceed 32", who, d->KT * d->KH * d->KW);
+    DAT_ENFORCE(ctx, d->Cin % 8 == 0 && g_cstride % 8 == 0, "%s: channel strides must be multiples of 8", who);
+    if (const char* why = dat_conv::conv_dilation_refusal(d)) DAT_FAIL(ctx, DAT_ERR_UNSUPPORTED, "%s: %s (dil %dx%d, stride %dx%d)", who, why, d->dil_h, d->dil_w, d->stride_h, d->stride_w);
+    DAT_ENFORCE(ctx, !acc_mode || wgrad_direct_eligible(ctx, d, g_cstride), "%s: the layer does not take the direct kernels (ask dat_conv3d_wgrad_acc_supported)", who);
+    // d->out_t0 / out_tn (optional): g is non-zero only in frames [out_t0, out_t0 + out_tn) of the clip (a key-frame gradient embedded
+    // in its temporal window): every family reduces over those frames' positions only
+    if (d->out_tn > 0 && d->frames / d->T == 1)
+        DAT_ENFORCE(ctx, d->out_t0 >= 0 && d->out_t0 + d->out_tn <= d->T, "%s: gradient frames [%d, %d) outside T %d", who, d->out_t0, d->out_t0 + d->out_tn, d->T);
+    return DAT_OK;
 }
 
-static int pw_plan(dat_ctx* ctx, const dat_conv_desc* d, const void* x, const void* g, int g_cstride, int Cin_real, int Cout_real, float* Gt,
-                   PwPlan* pl) {
-    int Ho, Wo;
-    dat_conv3d_out_shape(d, &Ho, &Wo);
-    const int clips = d->frames / d->T;
-    WgradPwItem& q = pl->it;
-    memset(&q, 0, sizeof(q));
-    q.g = (const char*)g; q.x = (const char*)x; q.G = Gt;
-    q.Cout = Cout_real; q.Cin = Cin_real; q.g_cs = g_cstride; q.x_cs = d->Cin;
-    q.H = d->H; q.W = d->W; q.stride = d->stride_h;
-    column_strip(&Ho, &Wo, &q.H, &q.W, &q.stride);      // (a one-column map becomes a one-row strip)
-    q.Wo = Wo;
-    q.how = (unsigned)(Ho * Wo);
-    q.how_magic = q.how == 1 ? 0xffffffffu : (unsigned)(0x100000000ull / q.how);
-    q.wo_magic = Wo == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)Wo - 1) / (unsigned)Wo);
-    q.p_begin = 0; q.p_end = (unsigned)((long long)d->frames * Ho * Wo);
-    if (d->out_tn > 0 && clips == 1) {      // g is non-zero only in frames [out_t0, out_t0 + out_tn) of the clip
-        DAT_ENFORCE(ctx, d->out_t0 >= 0 && d->out_t0 + d->out_tn <= d->T, "conv3d_wgrad: gradient frames [%d, %d) outside T %d",
-                    d->out_t0, d->out_t0 + d->out_tn, d->T);
-        q.p_begin = (unsigned)d->out_t0 * q.how; q.p_end = (unsigned)(d->out_t0 + d->out_tn) * q.how;
+// ---- the K-split rules: into how many ranges the reduced axis is cut (tiles: blocks of ONE range; nchunks: what a range is made of) ----
+// Nine-tap (nchunks: 8 x 8 patches).  Returns the ranges; *per_block = how many of them a block takes (the kernel's SUB).
+// K split (per-layer sweep of the LDS-DMA kernel, tools/probes/wgrad_bench.py, blocks = tiles x ks): ~384 blocks -- 1.5 per CU --
+// beat the 640 (1.25 rounds of the 512 slots) the register-staged kernel of rounds 1-3 liked: res3 (12 tiles) ks 53 -> 32 0.181 -> 0.157 ms,
+// res4 / P3 (48) 13 -> 8 0.192 -> 0.167 / 0.136 -> 0.109, P2 13 -> 8 0.328 -> 0.304; fewer, longer blocks mean fewer atomics and
+// fewer pipeline fills.  Layers with many tiles (res5: 192) want two blocks per CU again: ks 3 -> 4 0.224 -> 0.205.
+// Eight-wave blocks (DAT_WGRAD_SUB = 2, the default; round 4): one block per CU, two K ranges per block -- ks counts the RANGES, so it
+// is even; 2 * floor(256 / tiles) was the best of a sweep for every layer with <= 48 tiles (res3 0.164 -> 0.145 ms, res4 0.166 ->
+// 0.157, P2 0.306 -> 0.274, P3 0.109 -> 0.104).  Layers with more tiles than half the CUs (res5: 192) take ONE block per tile with
+// its two ranges -- no K split across blocks, so no contended atomics at all (plain stores outside the deferred-finish mode):
+// 0.210 -> 0.192 ms against the four-wave blocks' ks = 4 (768 blocks, 113 MB of atomics); two blocks per tile: 0.230.
+// DAT_WGRAD_KS forces the value before the clamp to the patch count; fewer than two ranges fall back to four-wave blocks.
+static long long nine_tap_ksplit(const dat_ctx* ctx, long long tiles, long long nchunks, int* per_block) {
+    const int sub = ctx->dbg_wgrad_sub >= 2 ? 2 : 1;
+    long long ks = tiles <= 96 ? (384 + tiles - 1) / tiles : (768 + tiles - 1) / tiles;
+    if (sub == 2) ks = tiles <= 128 ? 2 * (256 / tiles) : 2;
+    if (ks > nchunks / 4) ks = nchunks / 4;             // at least 4 patches per block
+    if (ctx->dbg_wgrad_ks > 0) ks = ctx->dbg_wgrad_ks;
+    if (ks > nchunks) ks = nchunks;
+    if (sub == 2) ks &= ~1ll;
+    *per_block = sub == 2 && ks >= 2 ? 2 : 1;
+    return ks < 1 ? 1 : ks;
+}
+
+// Pointwise, a layer on its own (nchunks: chunks of PW_KC positions): one block per CU -- every further block adds a partial tile of float
+// atomics (see WgradPwBatch).  DAT_WGRAD_KS forces the value before the clamp to the chunk count.
+static long long pointwise_ksplit(const dat_ctx* ctx, int num_cu, long long tiles, long long nchunks) {
+    long long ks = tiles >= num_cu ? 1 : num_cu / tiles;
+    if (ks > nchunks / 4) ks = nchunks / 4;             // at least 4 chunks per block
+    if (ctx->dbg_wgrad_ks > 0) ks = ctx->dbg_wgrad_ks;
+    if (ks > nchunks) ks = nchunks;
+    return ks < 1 ? 1 : ks;
+}
+
+// Pointwise, the n layers of a dat_conv3d_wgrad_acc_batch call on their shared grids: ~2 blocks per CU over ALL of them (one per CU for a
+// single layer), every block about the same number of chunks, at least 4.  Always atomics: the accumulators are the caller's.
+static void pointwise_batch_ksplit(const dat_ctx* ctx, int num_cu, WgradPlan* const* pls, size_t n) {
+    long long total = 0;
+    for (size_t i = 0; i < n; ++i) total += pls[i]->tiles * pls[i]->nchunks;
+    const long long target = (n == 1 ? 1 : 2) * (long long)num_cu;                 // blocks in the grid(s)
+    long long cpb = (total + target - 1) / target;                                  // chunks per block
+    if (cpb < 4) cpb = 4;
+    for (size_t i = 0; i < n; ++i) {
+        WgradPlan& pl = *pls[i];
+        long long ks = (pl.nchunks + cpb - 1) / cpb;
+        if (ctx->dbg_wgrad_ks > 0) ks = ctx->dbg_wgrad_ks;
+        if (ks > pl.nchunks) ks = pl.nchunks;
+        if (ks < 1) ks = 1;
+        pl.ksplit = (int)ks;
+        pl.atomic = 1;
+        pl.blocks = (int)(pl.tiles * ks);
     }
-    // tile shape: least padded MFMA work first, then least operand traffic (every g row is read once per ci tile, every x row once per
-    // co tile); ties go to the squarer tile
+}
+
+// Direct (nchunks: chunks of 64 positions, at least 8 per block) and re-pack (K-steps, at least 16 per block): ~2 rounds of the 512
+// resident blocks; every split costs a partial tile.  DAT_WGRAD_KS does not reach these two.
+static long long streamed_ksplit(long long tiles, long long nchunks, int min_chunks) {
+    long long ks = 1024 / tiles;
+    if (ks > nchunks / min_chunks) ks = nchunks / min_chunks;
+    return ks < 1 ? 1 : ks;
+}
+
+// pointwise tile shape (128 wm) co x (64 * 8 / wm) ci: least padded MFMA work first, then least operand traffic (every g row is read once
+// per ci tile, every x row once per co tile); ties go to the squarer tile
+static int pointwise_wm(const dat_ctx* ctx, const dat_conv_desc* d, int g_cstride, int Cin_real, int Cout_real) {
     int best_wm = 2;
     long long best_work = -1, best_traffic = 0;
     const int wm_order[3] = {2, 1, 4};
@@ -1325,16 +1390,111 @@ static int pw_plan(dat_ctx* ctx, const dat_conv_desc* d, const void* x, const vo
             best_work = work; best_traffic = traffic; best_wm = wm;
         }
     }
-    q.wm = best_wm;
-    const int tm = 128 * q.wm, tn = 64 * (8 / q.wm);
-    q.n_co_tiles = (Cout_real + tm - 1) / tm; q.n_ci_tiles = (Cin_real + tn - 1) / tn;
-    pl->tiles = (long long)q.n_co_tiles * q.n_ci_tiles;
-    pl->nchunks = ((long long)(q.p_end - q.p_begin) + PW_KC - 1) / PW_KC;
-    return DAT_OK;
+    return best_wm;
 }
 
-// launches the planned items (ksplit / atomic set by the caller): one grid per tile class (8 | 10 panels per stage), <= PW_MAX_ITEMS layers each
-static int pw_launch(dat_ctx* ctx, hipStream_t st, PwPlan* pls, int n) {
+static size_t pointwise_lds_bytes(int wm) { return 3 * (size_t)(wm == 2 ? 8 : 10) * PW_PANEL; }      // three stages of 8 | 10 panels
+
+// ---- plan: everything about a validated layer's launch that is not an address.  No HIP call, no state. ----
+static WgradPlan wgrad_plan(const dat_ctx* ctx, int num_cu, const dat_conv_desc* d, int g_cstride, int Cin_real, int Cout_real, int acc_mode) {
+    WgradPlan pl{};
+    int Ho, Wo, Tq, Hq, Wq, nc;
+    long long Qtot, Qa;
+    wgrad_geom(d, &Ho, &Wo, &Tq, &Hq, &Wq, &Qtot, &Qa, &nc);
+    const bool window = d->out_tn > 0 && d->frames / d->T == 1;        // (wgrad_validate: inside the clip)
+    const long long f_begin = window ? d->out_t0 : 0, f_end = window ? d->out_t0 + d->out_tn : d->frames, how = (long long)Ho * Wo;
+    pl.taps = d->KT * d->KH * d->KW;
+    auto set_tiles = [&](int tile_co, int tile_ci, int per_tile_pair) {
+        pl.tile_co = tile_co; pl.tile_ci = tile_ci;
+        pl.n_co_tiles = (Cout_real + tile_co - 1) / tile_co; pl.n_ci_tiles = (Cin_real + tile_ci - 1) / tile_ci;
+        pl.tiles = (long long)per_tile_pair * pl.n_co_tiles * pl.n_ci_tiles;
+    };
+    int ranges_per_block = 1;
+    long long ks;
+    if (!wgrad_direct_eligible(ctx, d, g_cstride)) {
+        pl.family = DAT_WGRAD_REPACK;
+        pl.variant = d->dtype;
+        pl.ncopies = nc;
+        pl.npack = 1 + d->stride_h * d->stride_h * nc;      // gT, then the xT planes (stride parity) x copies (element shift)
+        set_tiles(128, 128, pl.taps);
+        const int ck = d->dtype == DAT_BF16 ? 64 : 32;
+        pl.r_begin = 0; pl.r_end = (Qtot + ck - 1) / ck * ck;
+        if (window) {       // whole K-steps around the frames' padded positions
+            const long long fq = (long long)Hq * Wq, e0 = (f_end * fq + ck - 1) / ck * ck;
+            pl.r_begin = f_begin * fq / ck * ck;
+            if (e0 < pl.r_end) pl.r_end = e0;
+        }
+        pl.nchunks = (pl.r_end - pl.r_begin) / ck;
+        ks = streamed_ksplit(pl.tiles, pl.nchunks, 16);
+        pl.threads = NT;
+    } else if (wgrad_nine_tap(ctx, d)) {
+        pl.family = DAT_WGRAD_NINE_TAP;
+        set_tiles(64, 64, d->KT);                           // a block = (64 co x 64 ci) x one temporal tap, its nine spatial taps together
+        pl.r_begin = f_begin; pl.r_end = f_end;
+        pl.nchunks = (f_end - f_begin) * ((d->H + 7) / 8) * ((d->W + 7) / 8);
+        ks = nine_tap_ksplit(ctx, pl.tiles, pl.nchunks, &ranges_per_block);
+        pl.variant = ranges_per_block;
+        pl.threads = NT * ranges_per_block;
+        pl.lds_bytes = ranges_per_block * W9D_STAGES * W9D_STAGE;
+    } else {
+        int H = d->H, W = d->W, stride = d->stride_h, sHo = Ho, sWo = Wo;
+        column_strip(&sHo, &sWo, &H, &W, &stride);
+        pl.strip = sWo != Wo;
+        pl.r_begin = f_begin * how; pl.r_end = f_end * how;
+        if (wgrad_pointwise(ctx, d)) {
+            pl.family = DAT_WGRAD_POINTWISE;
+            pl.variant = pointwise_wm(ctx, d, g_cstride, Cin_real, Cout_real);
+            set_tiles(128 * pl.variant, 64 * (8 / pl.variant), 1);
+            pl.nchunks = (pl.r_end - pl.r_begin + PW_KC - 1) / PW_KC;
+            ks = pointwise_ksplit(ctx, num_cu, pl.tiles, pl.nchunks);
+            pl.threads = 512;
+            pl.lds_bytes = (int)pointwise_lds_bytes(pl.variant);
+        } else {
+            pl.family = DAT_WGRAD_DIRECT;                   // (dilated 3 x 3 layers land here: one block per tap, the tap's input offset scaled)
+            set_tiles(128, 128, pl.taps);
+            pl.nchunks = (pl.r_end - pl.r_begin + 63) / 64;
+            ks = streamed_ksplit(pl.tiles, pl.nchunks, 8);
+            pl.threads = NT;
+            pl.lds_bytes = 4 * WD_TILE;
+        }
+    }
+    pl.ksplit = (int)ks;
+    // acc_mode: the accumulator is the caller's -- no zeroing, always atomics, no finish launch (the caller zeroes it once per iteration
+    // and runs ONE dat_wgrad_finish_batch for all layers).  Otherwise the ranges meet in atomics, on zeroes, when several blocks share a tile.
+    pl.atomic = ks > ranges_per_block || acc_mode;
+    pl.memset_first = pl.atomic && !acc_mode;
+    pl.finish = !acc_mode;
+    pl.blocks = (int)(pl.tiles * ks / ranges_per_block);
+    return pl;
+}
+
+// ---- launch: the kernel parameters from the plan and the pointers; the one memset, the kernel(s), the finish ----
+// (a layer's tensors travel as a dat_wgrad_job: desc, x, g, g_cstride, Cin_real, Cout_real and Gt, the accumulator [tap][Cout][Cin])
+// the table entry of a planned pointwise layer (pw_launch sets block0)
+static WgradPwItem pw_item(const WgradPlan& pl, const dat_wgrad_job& j) {
+    const dat_conv_desc* d = j.desc;
+    int Ho, Wo;
+    dat_conv3d_out_shape(d, &Ho, &Wo);
+    WgradPwItem q;
+    memset(&q, 0, sizeof(q));
+    q.g = (const char*)j.g; q.x = (const char*)j.x; q.G = j.Gt;
+    q.Cout = j.Cout_real; q.Cin = j.Cin_real; q.g_cs = j.g_cstride; q.x_cs = d->Cin;
+    q.H = d->H; q.W = d->W; q.stride = d->stride_h;
+    column_strip(&Ho, &Wo, &q.H, &q.W, &q.stride);      // (a one-column map becomes a one-row strip)
+    q.Wo = Wo;
+    q.how = (unsigned)(Ho * Wo);
+    q.how_magic = q.how == 1 ? 0xffffffffu : (unsigned)(0x100000000ull / q.how);
+    q.wo_magic = Wo == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)Wo - 1) / (unsigned)Wo);
+    q.p_begin = (unsigned)pl.r_begin; q.p_end = (unsigned)pl.r_end;
+    q.wm = pl.variant;
+    q.n_co_tiles = pl.n_co_tiles; q.n_ci_tiles = pl.n_ci_tiles;
+    q.ksplit = pl.ksplit;
+    q.atomic = pl.atomic;
+    return q;
+}
+
+// launches the items: one grid per tile class (8 | 10 panels per stage), <= PW_MAX_ITEMS layers each
+static int pw_launch(dat_ctx* ctx, hipStream_t st, const WgradPwItem* items, int n) {
     for (int cls = 0; cls < 2; ++cls) {
         int i = 0;
         while (i < n) {
@@ -1343,19 +1503,18 @@ static int pw_launch(dat_ctx* ctx, hipStream_t st, PwPlan* pls, int n) {
             b.n = 0;
             unsigned blocks = 0;
             for (; i < n && b.n < PW_MAX_ITEMS; ++i) {
-                if ((pls[i].it.wm == 2) != (cls == 0)) continue;
+                if ((items[i].wm == 2) != (cls == 0)) continue;
                 WgradPwItem& q = b.item[b.n++];
-                q = pls[i].it;
+                q = items[i];
                 q.block0 = blocks;
-                blocks += (unsigned)(pls[i].tiles * q.ksplit);
+                blocks += (unsigned)((long long)q.n_co_tiles * q.n_ci_tiles * q.ksplit);
             }
             if (b.n == 0) continue;
+            const size_t lds = pointwise_lds_bytes(cls == 0 ? 2 : 1);
             if (cls == 0) {
-                const size_t lds = 3 * (size_t)8 * PW_PANEL;
                 if (dat_ensure_lds(ctx, (const void*)wgrad_pw_kernel<8>, (int)lds) != DAT_OK) return DAT_ERR_LAUNCH;
                 hipLaunchKernelGGL((wgrad_pw_kernel<8>), dim3(blocks), dim3(512), lds, st, b);
             } else {
-                const size_t lds = 3 * (size_t)10 * PW_PANEL;
                 if (dat_ensure_lds(ctx, (const void*)wgrad_pw_kernel<10>, (int)lds) != DAT_OK) return DAT_ERR_LAUNCH;
                 hipLaunchKernelGGL((wgrad_pw_kernel<10>), dim3(blocks), dim3(512), lds, st, b);
             }
@@ -1365,170 +1524,101 @@ static int pw_launch(dat_ctx* ctx, hipStream_t st, PwPlan* pls, int n) {
     return DAT_OK;
 }
 
-// acc_mode (dat_conv3d_wgrad_acc): `workspace` IS the caller's fp32 accumulator in the kernels' [tap][Cout][Cin] order -- no zeroing, always
-// atomics, no finish launch (the caller zeroes it once per iteration and runs ONE dat_wgrad_finish_batch for all layers)
-static int wgrad_impl(dat_ctx* ctx, dat_stream s_, const dat_conv_desc* d, const void* x, const void* g, int g_cstride,
-                      int Cin_real, int Cout_real, const float* scale, void* workspace, float* dW, int acc_mode) {
-    DAT_ENFORCE(ctx, d && x && g && workspace && (dW || acc_mode), "conv3d_wgrad: null argument");
-    DAT_ENFORCE(ctx, d->dtype == DAT_F32 || d->dtype == DAT_BF16, "conv3d_wgrad: bad dtype %d", d->dtype);
-    DAT_ENFORCE(ctx, d->stride_h == d->stride_w && (d->stride_h == 1 || d->stride_h == 2), "conv3d_wgrad: stride %dx%d", d->stride_h, d->stride_w);
-    DAT_ENFORCE(ctx, d->frames % d->T == 0 && d->pad_t * 2 + 1 == d->KT, "conv3d_wgrad: needs same-T convs");
-    DAT_ENFORCE(ctx, d->KT * d->KH * d->KW <= 32, "conv3d_wgrad: %d taps exceed 32", d->KT * d->KH * d->KW);
-    DAT_ENFORCE(ctx, d->Cin % 8 == 0 && g_cstride % 8 == 0, "conv3d_wgrad: channel strides must be multiples of 8");
-    if (const char* why = dat_conv::conv_dilation_refusal(d)) DAT_FAIL(ctx, DAT_ERR_UNSUPPORTED, "conv3d_wgrad: %s (dil %dx%d, stride %dx%d)", why, d->dil_h, d->dil_w, d->stride_h, d->stride_w);
-    const int dl = dat_conv::conv_dilation(d);
-    hipStream_t st = (hipStream_t)s_;
+static int launch_nine_tap(dat_ctx* ctx, hipStream_t st, const WgradPlan& pl, const dat_wgrad_job& j) {
+    const dat_conv_desc* d = j.desc;
+    Wgrad9Params q;
+    memset(&q, 0, sizeof(q));
+    q.g = (const char*)j.g; q.x = (const char*)j.x; q.G = j.Gt;
+    q.Cout = j.Cout_real; q.Cin = j.Cin_real; q.g_cs = j.g_cstride; q.x_cs = d->Cin;
+    q.T = d->T; q.H = d->H; q.W = d->W; q.KT = d->KT; q.pt = d->pad_t;
+    q.n_co_tiles = pl.n_co_tiles; q.n_ci_tiles = pl.n_ci_tiles;
+    q.f_begin = (int)pl.r_begin; q.f_end = (int)pl.r_end;
+    q.tiles_h = (d->H + 7) / 8; q.tiles_w = (d->W + 7) / 8;
+    q.ablate = ctx->dbg_ablate_wgrad;
+    q.ksplit = pl.ksplit;
+    q.atomic = pl.atomic;
+    q.zeros = (const char*)ctx->zeros;
+    switch (pl.variant) {
+        case 2:
+            if (dat_ensure_lds(ctx, (const void*)wgrad_dma9_kernel<2>, pl.lds_bytes) != DAT_OK) return DAT_ERR_LAUNCH;
+            hipLaunchKernelGGL((wgrad_dma9_kernel<2>), dim3((unsigned)pl.blocks), dim3(pl.threads), pl.lds_bytes, st, q);
+            break;
+        default:
+            if (dat_ensure_lds(ctx, (const void*)wgrad_dma9_kernel<1>, pl.lds_bytes) != DAT_OK) return DAT_ERR_LAUNCH;
+            hipLaunchKernelGGL((wgrad_dma9_kernel<1>), dim3((unsigned)pl.blocks), dim3(pl.threads), pl.lds_bytes, st, q);
+    }
+    DAT_CHECK_LAUNCH(ctx, "conv3d_wgrad direct9");
+    return DAT_OK;
+}
+
+static int launch_direct(dat_ctx* ctx, hipStream_t st, const WgradPlan& pl, const dat_wgrad_job& j) {
+    const dat_conv_desc* d = j.desc;
+    WgradDirectParams wp;
+    memset(&wp, 0, sizeof(wp));
+    wp.g = (const char*)j.g; wp.x = (const char*)j.x; wp.G = j.Gt;
+    wp.Cout = j.Cout_real; wp.Cin = j.Cin_real; wp.g_cs = j.g_cstride; wp.x_cs = d->Cin;
+    wp.T = d->T; wp.H = d->H; wp.W = d->W; wp.stride = d->stride_h;
+    dat_conv3d_out_shape(d, &wp.Ho, &wp.Wo);
+    wp.how = (unsigned)(wp.Ho * wp.Wo);
+    column_strip(&wp.Ho, &wp.Wo, &wp.H, &wp.W, &wp.stride);     // (kT x 1 x 1 on a one-column map, see wgrad_direct_eligible: a one-row strip)
+    wp.KT = d->KT; wp.KH = d->KH; wp.KW = d->KW; wp.pt = d->pad_t; wp.ph = d->pad_h; wp.pw = d->pad_w;
+    wp.dil = dat_conv::conv_dilation(d);
+    wp.ntaps = pl.taps;
+    wp.n_co_tiles = pl.n_co_tiles; wp.n_ci_tiles = pl.n_ci_tiles;
+    // (__umulhi(p, ceil(2^32 / n)) == p / n needs p * n < 2^32 or so: checked exactly for the ranges used, wgrad_direct_eligible)
+    wp.wo_magic = wp.Wo == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)wp.Wo - 1) / (unsigned)wp.Wo);
+    wp.p_begin = (unsigned)pl.r_begin; wp.p_end = (unsigned)pl.r_end;
+    wp.ksplit = pl.ksplit;
+    wp.atomic = pl.atomic;
+    if (dat_ensure_lds(ctx, (const void*)wgrad_direct_kernel, pl.lds_bytes) != DAT_OK) return DAT_ERR_LAUNCH;
+    hipLaunchKernelGGL(wgrad_direct_kernel, dim3((unsigned)pl.blocks), dim3(pl.threads), pl.lds_bytes, st, wp);
+    DAT_CHECK_LAUNCH(ctx, "conv3d_wgrad direct");
+    return DAT_OK;
+}
+
+// The re-pack path's workspace: gT [Cout][Qa], the xT planes [Cin][Qa] (stride parity x shifted copies), then the accumulator
+struct RepackWs {
     int Ho, Wo, Tq, Hq, Wq, nc;
     long long Qtot, Qa;
-    wgrad_geom(d, &Ho, &Wo, &Tq, &Hq, &Wq, &Qtot, &Qa, &nc);
-    const int s = d->stride_h;
-    const size_t es = dat_esize(d->dtype);
-    const int clips = d->frames / d->T;
-    // ---- bf16: the direct kernel (no re-pack passes; transposing LDS reads) ----
-    const long long npos_out = (long long)d->frames * Ho * Wo, npos_in = (long long)d->frames * d->H * d->W;
-    (void)npos_out; (void)npos_in;
-    DAT_ENFORCE(ctx, !acc_mode || wgrad_direct_eligible(ctx, d, g_cstride), "conv3d_wgrad_acc: the layer does not take the direct kernels (ask dat_conv3d_wgrad_acc_supported)");
-    if (wgrad_direct_eligible(ctx, d, g_cstride)) {
-        float* Gt = (float*)workspace;
-        if (d->KH == 3 && d->KW == 3 && s == 1 && d->pad_h == 1 && d->pad_w == 1 && (ctx->dbg_wgrad_direct & 2) == 0 && dl == 1) {
-            // nine spatial taps from one staged patch (wgrad_dma9_kernel)
-            Wgrad9Params q;
-            memset(&q, 0, sizeof(q));
-            q.g = (const char*)g; q.x = (const char*)x; q.G = Gt;
-            q.Cout = Cout_real; q.Cin = Cin_real; q.g_cs = g_cstride; q.x_cs = d->Cin;
-            q.T = d->T; q.H = d->H; q.W = d->W; q.KT = d->KT; q.pt = d->pad_t;
-            q.n_co_tiles = (Cout_real + 63) / 64; q.n_ci_tiles = (Cin_real + 63) / 64;
-            q.f_begin = 0; q.f_end = d->frames;
-            if (d->out_tn > 0 && clips == 1) {
-                DAT_ENFORCE(ctx, d->out_t0 >= 0 && d->out_t0 + d->out_tn <= d->T, "conv3d_wgrad: gradient frames [%d, %d) outside T %d",
-                            d->out_t0, d->out_t0 + d->out_tn, d->T);
-                q.f_begin = d->out_t0; q.f_end = d->out_t0 + d->out_tn;
-            }
-            q.tiles_h = (d->H + 7) / 8; q.tiles_w = (d->W + 7) / 8;
-            q.ablate = ctx->dbg_ablate_wgrad;
-            const long long tiles = (long long)d->KT * q.n_co_tiles * q.n_ci_tiles;
-            const long long nchunks = (long long)(q.f_end - q.f_begin) * q.tiles_h * q.tiles_w;
-            // K split (per-layer sweep of the LDS-DMA kernel, tools/probes/wgrad_bench.py, blocks = tiles x ks): ~384 blocks -- 1.5 per CU --
-            // beat the 640 (1.25 rounds of the 512 slots) the register-staged kernel of rounds 1-3 liked: res3 (12 tiles) ks 53 -> 32 0.181 -> 0.157 ms,
-            // res4 / P3 (48) 13 -> 8 0.192 -> 0.167 / 0.136 -> 0.109, P2 13 -> 8 0.328 -> 0.304; fewer, longer blocks mean fewer atomics and
-            // fewer pipeline fills.  Layers with many tiles (res5: 192) want two blocks per CU again: ks 3 -> 4 0.224 -> 0.205.
-            // Eight-wave blocks (DAT_WGRAD_SUB = 2, the default; round 4): one block per CU, two K ranges per block -- ks counts the RANGES, so it
-            // is even; 2 * floor(256 / tiles) was the best of a sweep for every layer with <= 48 tiles (res3 0.164 -> 0.145 ms, res4 0.166 ->
-            // 0.157, P2 0.306 -> 0.274, P3 0.109 -> 0.104).  Layers with more tiles than half the CUs (res5: 192) take ONE block per tile with
-            // its two ranges -- no K split across blocks, so no contended atomics at all (plain stores outside the deferred-finish mode):
-            // 0.210 -> 0.192 ms against the four-wave blocks' ks = 4 (768 blocks, 113 MB of atomics); two blocks per tile: 0.230.
-            const int sub = ctx->dbg_wgrad_sub >= 2 ? 2 : 1;
-            long long ks = tiles <= 96 ? (384 + tiles - 1) / tiles : (768 + tiles - 1) / tiles;
-            if (sub == 2) ks = tiles <= 128 ? 2 * (256 / tiles) : 2;
-            if (ks > nchunks / 4) ks = nchunks / 4;             // at least 4 patches per block
-            if (ctx->dbg_wgrad_ks > 0) ks = ctx->dbg_wgrad_ks;
-            if (ks > nchunks) ks = nchunks;
-            if (sub == 2) ks &= ~1ll;
-            const bool sub2 = sub == 2 && ks >= 2;
-            if (ks < 1) ks = 1;
-            q.ksplit = (int)ks;
-            q.atomic = ks > (sub2 ? 2 : 1) || acc_mode;
-            const size_t g_elems = (size_t)Cout_real * Cin_real * d->KT * 9;
-            if (q.atomic && !acc_mode && hipMemsetAsync(Gt, 0, g_elems * sizeof(float), st) != hipSuccess)
-                DAT_FAIL(ctx, DAT_ERR_LAUNCH, "conv3d_wgrad: memset failed");
-            q.zeros = (const char*)ctx->zeros;
-            if (sub2) {
-                const size_t lds = 2 * W9D_STAGES * W9D_STAGE;
-                if (dat_ensure_lds(ctx, (const void*)wgrad_dma9_kernel<2>, lds) != DAT_OK) return DAT_ERR_LAUNCH;
-                hipLaunchKernelGGL((wgrad_dma9_kernel<2>), dim3((unsigned)(tiles * ks / 2)), dim3(2 * NT), lds, st, q);
-            } else {
-                const size_t lds = W9D_STAGES * W9D_STAGE;
-                if (dat_ensure_lds(ctx, (const void*)wgrad_dma9_kernel<1>, lds) != DAT_OK) return DAT_ERR_LAUNCH;
-                hipLaunchKernelGGL((wgrad_dma9_kernel<1>), dim3((unsigned)(tiles * ks)), dim3(NT), lds, st, q);
-            }
-            if (!acc_mode)
-                hipLaunchKernelGGL(wgrad_finish_kernel, dim3(grid_for((long long)g_elems, 256)), dim3(256), 0, st, (const float*)Gt, scale, dW,
-                                   Cout_real, Cin_real, d->KT * 9);
-            DAT_CHECK_LAUNCH(ctx, "conv3d_wgrad direct9");
-            return DAT_OK;
-        }
-        if (pw_eligible(ctx, d)) {
-            // pointwise layers (1 x 1 x 1 convs, FC; stride 1 | 2): eight-wave blocks, 64 K accumulators per tile (wgrad_pw_kernel)
-            PwPlan pl;
-            if (int rc = pw_plan(ctx, d, x, g, g_cstride, Cin_real, Cout_real, Gt, &pl)) return rc;
-            const int ncu = dat_conv::ctx_num_cu(ctx);
-            long long ks = pl.tiles >= ncu ? 1 : ncu / pl.tiles;        // one block per CU
-            if (ks > pl.nchunks / 4) ks = pl.nchunks / 4;               // at least 4 chunks per block
-            if (ctx->dbg_wgrad_ks > 0) ks = ctx->dbg_wgrad_ks;
-            if (ks > pl.nchunks) ks = pl.nchunks;
-            if (ks < 1) ks = 1;
-            pl.it.ksplit = (int)ks;
-            pl.it.atomic = ks > 1 || acc_mode;
-            const size_t g_elems = (size_t)Cout_real * Cin_real;
-            if (ks > 1 && !acc_mode && hipMemsetAsync(Gt, 0, g_elems * sizeof(float), st) != hipSuccess)
-                DAT_FAIL(ctx, DAT_ERR_LAUNCH, "conv3d_wgrad: memset failed");
-            if (int rc = pw_launch(ctx, st, &pl, 1)) return rc;
-            if (!acc_mode)
-                hipLaunchKernelGGL(wgrad_finish_kernel, dim3(grid_for((long long)g_elems, 256)), dim3(256), 0, st, (const float*)Gt, scale, dW,
-                                   Cout_real, Cin_real, 1);
-            DAT_CHECK_LAUNCH(ctx, "conv3d_wgrad pointwise");
-            return DAT_OK;
-        }
-        WgradDirectParams wp;
-        memset(&wp, 0, sizeof(wp));
-        wp.g = (const char*)g; wp.x = (const char*)x; wp.G = Gt;
-        wp.Cout = Cout_real; wp.Cin = Cin_real; wp.g_cs = g_cstride; wp.x_cs = d->Cin;
-        wp.T = d->T; wp.H = d->H; wp.W = d->W; wp.Ho = Ho; wp.Wo = Wo; wp.stride = s;
-        column_strip(&wp.Ho, &wp.Wo, &wp.H, &wp.W, &wp.stride);     // (kT x 1 x 1 on a one-column map, see wgrad_direct_eligible: a one-row strip)
-        wp.KT = d->KT; wp.KH = d->KH; wp.KW = d->KW; wp.pt = d->pad_t; wp.ph = d->pad_h; wp.pw = d->pad_w;
-        wp.dil = dl;        // (dilated 3 x 3 layers land here: one block per tap, the tap's input offset scaled)
-        wp.ntaps = d->KT * d->KH * d->KW;
-        wp.n_co_tiles = (Cout_real + 127) / 128; wp.n_ci_tiles = (Cin_real + 127) / 128;
-        wp.how = (unsigned)(Ho * Wo);
-        wp.wo_magic = wp.Wo == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)wp.Wo - 1) / (unsigned)wp.Wo);
-        wp.p_begin = 0; wp.p_end = (unsigned)npos_out;
-        if (d->out_tn > 0 && clips == 1) {   // g is non-zero only in frames [out_t0, out_t0 + out_tn) of the clip
-            DAT_ENFORCE(ctx, d->out_t0 >= 0 && d->out_t0 + d->out_tn <= d->T, "conv3d_wgrad: gradient frames [%d, %d) outside T %d",
-                        d->out_t0, d->out_t0 + d->out_tn, d->T);
-            wp.p_begin = (unsigned)d->out_t0 * wp.how; wp.p_end = (unsigned)(d->out_t0 + d->out_tn) * wp.how;
-        }
-        // (__umulhi(p, ceil(2^32 / n)) == p / n needs p * n < 2^32 or so: checked exactly for the ranges used)
-        const long long tiles = (long long)wp.ntaps * wp.n_co_tiles * wp.n_ci_tiles;
-        const long long nchunks = ((long long)(wp.p_end - wp.p_begin) + 63) / 64;
-        long long ks = 1024 / tiles;                        // ~2 rounds of the 512 resident blocks; every split costs a partial tile
-        if (ks > nchunks / 8) ks = nchunks / 8;             // at least 8 chunks per block
-        if (ks < 1) ks = 1;
-        wp.ksplit = (int)ks;
-        wp.atomic = ks > 1 || acc_mode;
-        const size_t g_elems = (size_t)Cout_real * Cin_real * wp.ntaps;
-        if (ks > 1 && !acc_mode && hipMemsetAsync(Gt, 0, g_elems * sizeof(float), st) != hipSuccess)
-            DAT_FAIL(ctx, DAT_ERR_LAUNCH, "conv3d_wgrad: memset failed");
-        if (dat_ensure_lds(ctx, (const void*)wgrad_direct_kernel, 4 * WD_TILE) != DAT_OK) return DAT_ERR_LAUNCH;
-        hipLaunchKernelGGL(wgrad_direct_kernel, dim3((unsigned)(tiles * ks)), dim3(NT), 4 * WD_TILE, st, wp);
-        if (!acc_mode)
-            hipLaunchKernelGGL(wgrad_finish_kernel, dim3(grid_for((long long)g_elems, 256)), dim3(256), 0, st, (const float*)Gt, scale, dW,
-                               Cout_real, Cin_real, wp.ntaps);
-        DAT_CHECK_LAUNCH(ctx, "conv3d_wgrad direct");
-        return DAT_OK;
-    }
-    char* gT = (char*)workspace;
-    char* xT = gT + (((size_t)Cout_real * Qa * es + 255) & ~(size_t)255);
-    const size_t plane_bytes = (size_t)Cin_real * Qa * es;
-    float* Gt = (float*)(xT + (((size_t)s * s * nc * plane_bytes + 255) & ~(size_t)255));
+    char *gT, *xT;
+    size_t plane_bytes;
+    float* Gt;
+};
 
+static RepackWs repack_ws(const dat_wgrad_job& j, void* workspace) {
+    const dat_conv_desc* d = j.desc;
+    RepackWs w;
+    wgrad_geom(d, &w.Ho, &w.Wo, &w.Tq, &w.Hq, &w.Wq, &w.Qtot, &w.Qa, &w.nc);
+    const size_t es = dat_esize(d->dtype);
+    const int s = d->stride_h;
+    w.gT = (char*)workspace;
+    w.xT = w.gT + (((size_t)j.Cout_real * w.Qa * es + 255) & ~(size_t)255);
+    w.plane_bytes = (size_t)j.Cin_real * w.Qa * es;
+    w.Gt = (float*)(w.xT + (((size_t)s * s * w.nc * w.plane_bytes + 255) & ~(size_t)255));
+    return w;
+}
+
+static int launch_repack(dat_ctx* ctx, hipStream_t st, const WgradPlan& pl, const dat_wgrad_job& j, const RepackWs& w) {
+    const dat_conv_desc* d = j.desc;
+    const int s = d->stride_h, dl = dat_conv::conv_dilation(d), nc = w.nc;
     PackParams pp;
-    pp.clips = clips; pp.Tq = Tq; pp.Hq = Hq; pp.Wq = Wq; pp.Qtot = Qtot; pp.Qa = Qa;
+    pp.clips = d->frames / d->T; pp.Tq = w.Tq; pp.Hq = w.Hq; pp.Wq = w.Wq; pp.Qtot = w.Qtot; pp.Qa = w.Qa;
     auto launch_pack = [&](const PackParams& q) {
-        dim3 grid((unsigned)((Qa + 63) / 64), (unsigned)((q.C + 63) / 64));
-        if (d->dtype == DAT_BF16) hipLaunchKernelGGL(cq_pack_kernel<DAT_BF16>, grid, dim3(256), 0, st, q);
+        dim3 grid((unsigned)((w.Qa + 63) / 64), (unsigned)((q.C + 63) / 64));
+        if (pl.variant == DAT_BF16) hipLaunchKernelGGL(cq_pack_kernel<DAT_BF16>, grid, dim3(256), 0, st, q);
         else hipLaunchKernelGGL(cq_pack_kernel<DAT_F32>, grid, dim3(256), 0, st, q);
     };
     // gT: the output-gradient grid, no shift, zero beyond (T, Ho, Wo)
-    pp.src = (const char*)g; pp.dst = gT; pp.T = d->T; pp.Hs = Ho; pp.Ws = Wo; pp.cs = g_cstride; pp.C = Cout_real;
+    pp.src = (const char*)j.g; pp.dst = w.gT; pp.T = d->T; pp.Hs = w.Ho; pp.Ws = w.Wo; pp.cs = j.g_cstride; pp.C = j.Cout_real;
     pp.st = 1; pp.ot = 0; pp.oy = 0; pp.ox = 0; pp.shift = 0;
     launch_pack(pp);
     // xT planes (stride parity) x copies (element shift)
-    pp.src = (const char*)x; pp.T = d->T; pp.Hs = d->H; pp.Ws = d->W; pp.cs = d->Cin; pp.C = Cin_real; pp.st = s;
+    pp.src = (const char*)j.x; pp.T = d->T; pp.Hs = d->H; pp.Ws = d->W; pp.cs = d->Cin; pp.C = j.Cin_real; pp.st = s;
     pp.ot = d->pad_t;
     for (int py = 0; py < s; ++py)
         for (int px = 0; px < s; ++px)
             for (int c = 0; c < nc; ++c) {
-                pp.dst = xT + ((size_t)((py * s + px) * nc + c)) * plane_bytes;
+                pp.dst = w.xT + ((size_t)((py * s + px) * nc + c)) * w.plane_bytes;
                 pp.oy = py - d->pad_h; pp.ox = px - d->pad_w; pp.shift = c;
                 launch_pack(pp);
             }
@@ -1536,98 +1626,115 @@ static int wgrad_impl(dat_ctx* ctx, dat_stream s_, const dat_conv_desc* d, const
 
     WgradParams wp;
     memset(&wp, 0, sizeof(wp));
-    wp.gT = gT; wp.xT = xT; wp.G = Gt; wp.Cout = Cout_real; wp.Cin = Cin_real;
-    wp.ntaps = d->KT * d->KH * d->KW; wp.Qa = Qa;
-    const int ck = d->dtype == DAT_BF16 ? 64 : 32;
-    wp.K = (Qtot + ck - 1) / ck * ck;
-    wp.k_begin = 0;
-    // d->out_t0 / out_tn (optional): g is non-zero only in frames [out_t0, out_t0 + out_tn) of the clip (a key-frame gradient
-    // embedded in its temporal window): reduce over those frames' positions only
-    if (d->out_tn > 0 && clips == 1) {
-        DAT_ENFORCE(ctx, d->out_t0 >= 0 && d->out_t0 + d->out_tn <= d->T, "conv3d_wgrad: gradient frames [%d, %d) outside T %d",
-                    d->out_t0, d->out_t0 + d->out_tn, d->T);
-        const long long fq = (long long)Hq * Wq;
-        const long long b0 = (long long)d->out_t0 * fq / ck * ck;
-        const long long e0 = ((long long)(d->out_t0 + d->out_tn) * fq + ck - 1) / ck * ck;
-        wp.k_begin = b0;
-        wp.K = (e0 < wp.K ? e0 : wp.K) - b0;
-    }
-    wp.n_co_tiles = (Cout_real + 127) / 128; wp.n_ci_tiles = (Cin_real + 127) / 128;
+    wp.gT = w.gT; wp.xT = w.xT; wp.G = w.Gt; wp.Cout = j.Cout_real; wp.Cin = j.Cin_real;
+    wp.ntaps = pl.taps; wp.Qa = w.Qa;
+    wp.k_begin = pl.r_begin;
+    wp.K = pl.r_end - pl.r_begin;
+    wp.n_co_tiles = pl.n_co_tiles; wp.n_ci_tiles = pl.n_ci_tiles;
     for (int kt = 0; kt < d->KT; ++kt)
         for (int kh = 0; kh < d->KH; ++kh)
             for (int kw = 0; kw < d->KW; ++kw) {
                 const int tap = (kt * d->KH + kh) * d->KW + kw;
-                long long off = ((long long)kt * Hq + kh * dl / s) * Wq + kw * dl / s;
+                long long off = ((long long)kt * w.Hq + kh * dl / s) * w.Wq + kw * dl / s;
                 int copy = 0;
                 if (nc == 2 && (off & 1)) { copy = 1; off -= 1; }
                 wp.tap_off[tap] = off;
-                wp.tap_base[tap] = (long long)(((kh % s) * s + (kw % s)) * nc + copy) * (long long)plane_bytes;
+                wp.tap_base[tap] = (long long)(((kh % s) * s + (kw % s)) * nc + copy) * (long long)w.plane_bytes;
             }
-    const long long tiles = (long long)wp.ntaps * wp.n_co_tiles * wp.n_ci_tiles;
-    const long long ksteps = wp.K / ck;
-    long long ks = 1024 / tiles;                        // ~2 rounds of the 512 resident blocks; every split costs a partial tile
-    if (ks > ksteps / 16) ks = ksteps / 16;             // at least 16 K-steps per block
-    if (ks < 1) ks = 1;
-    wp.ksplit = (int)ks;
-    const size_t g_elems = (size_t)Cout_real * Cin_real * wp.ntaps;
-    if (ks > 1 && hipMemsetAsync(Gt, 0, g_elems * sizeof(float), st) != hipSuccess)
-        DAT_FAIL(ctx, DAT_ERR_LAUNCH, "conv3d_wgrad: memset failed");
-    const unsigned nblocks = (unsigned)(tiles * ks);
-    if (d->dtype == DAT_BF16) hipLaunchKernelGGL(wgrad_gemm_kernel<DAT_BF16>, dim3(nblocks), dim3(NT), 0, st, wp);
-    else hipLaunchKernelGGL(wgrad_gemm_kernel<DAT_F32>, dim3(nblocks), dim3(NT), 0, st, wp);
-    hipLaunchKernelGGL(wgrad_finish_kernel, dim3(grid_for((long long)g_elems, 256)), dim3(256), 0, st, (const float*)Gt, scale, dW,
-                       Cout_real, Cin_real, wp.ntaps);
+    wp.ksplit = pl.ksplit;
+    switch (pl.variant) {
+        case DAT_BF16: hipLaunchKernelGGL(wgrad_gemm_kernel<DAT_BF16>, dim3((unsigned)pl.blocks), dim3(pl.threads), 0, st, wp); break;
+        default: hipLaunchKernelGGL(wgrad_gemm_kernel<DAT_F32>, dim3((unsigned)pl.blocks), dim3(pl.threads), 0, st, wp);
+    }
     DAT_CHECK_LAUNCH(ctx, "conv3d_wgrad gemm");
     return DAT_OK;
 }
 
+// `workspace`: dat_conv3d_wgrad_workspace_bytes() bytes -- the direct families keep only the accumulator there; acc_mode: it IS the
+// caller's accumulator
+static int wgrad_launch(dat_ctx* ctx, hipStream_t st, const WgradPlan& pl, dat_wgrad_job j, const float* scale, void* workspace, float* dW) {
+    RepackWs ws{};
+    if (pl.family == DAT_WGRAD_REPACK) ws = repack_ws(j, workspace);
+    j.Gt = pl.family == DAT_WGRAD_REPACK ? ws.Gt : (float*)workspace;
+    const size_t g_bytes = (size_t)j.Cout_real * j.Cin_real * pl.taps * sizeof(float);
+    if (pl.memset_first && hipMemsetAsync(j.Gt, 0, g_bytes, st) != hipSuccess) DAT_FAIL(ctx, DAT_ERR_LAUNCH, "conv3d_wgrad: memset failed");
+    int rc = DAT_OK;
+    switch (pl.family) {
+        case DAT_WGRAD_NINE_TAP: rc = launch_nine_tap(ctx, st, pl, j); break;
+        case DAT_WGRAD_POINTWISE: {
+            const WgradPwItem it = pw_item(pl, j);
+            rc = pw_launch(ctx, st, &it, 1);
+            break;
+        }
+        case DAT_WGRAD_DIRECT: rc = launch_direct(ctx, st, pl, j); break;
+        default: rc = launch_repack(ctx, st, pl, j, ws);
+    }
+    if (rc != DAT_OK || !pl.finish) return rc;
+    return dat_conv::launch_wgrad_finish(ctx, st, j.Gt, scale, dW, j.Cout_real, j.Cin_real, pl.taps);
+}
+
+static int wgrad_run(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, const void* x, const void* g, int g_cstride, int Cin_real,
+                     int Cout_real, const float* scale, void* workspace, float* dW, int acc_mode) {
+    const char* who = acc_mode ? "conv3d_wgrad_acc" : "conv3d_wgrad";
+    DAT_ENFORCE(ctx, d && x && g && workspace && (dW || acc_mode) && Cin_real > 0 && Cout_real > 0, "%s: null argument", who);
+    if (int rc = wgrad_validate(ctx, d, g_cstride, acc_mode, who)) return rc;
+    const WgradPlan pl = wgrad_plan(ctx, dat_conv::ctx_num_cu(ctx), d, g_cstride, Cin_real, Cout_real, acc_mode);
+    return wgrad_launch(ctx, (hipStream_t)s, pl, dat_wgrad_job{d, x, g, g_cstride, Cin_real, Cout_real, nullptr}, scale, workspace, dW);
+}
+
 int dat_conv3d_wgrad(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, const void* x, const void* g, int g_cstride,
                      int Cin_real, int Cout_real, const float* scale, void* workspace, float* dW) {
-    return wgrad_impl(ctx, s, d, x, g, g_cstride, Cin_real, Cout_real, scale, workspace, dW, 0);
+    return wgrad_run(ctx, s, d, x, g, g_cstride, Cin_real, Cout_real, scale, workspace, dW, 0);
 }
 
 int dat_conv3d_wgrad_acc_supported(dat_ctx* ctx, const dat_conv_desc* d, int g_cstride) {
-    return ctx && d && wgrad_direct_eligible(ctx, d, g_cstride) ? 1 : 0;
+    if (!d) return 0;
+    if (ctx) return wgrad_direct_eligible(ctx, d, g_cstride) ? 1 : 0;
+    dat_ctx env{};                  // ctx == NULL: the knobs as dat_ctx_create reads them, like dat_conv3d_wgrad_plan
+    dat_ctx_read_env(&env);
+    return wgrad_direct_eligible(&env, d, g_cstride) ? 1 : 0;
 }
 
 int dat_conv3d_wgrad_acc(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, const void* x, const void* g, int g_cstride,
                          int Cin_real, int Cout_real, float* Gt) {
-    return wgrad_impl(ctx, s, d, x, g, g_cstride, Cin_real, Cout_real, nullptr, Gt, nullptr, 1);
+    return wgrad_run(ctx, s, d, x, g, g_cstride, Cin_real, Cout_real, nullptr, Gt, nullptr, 1);
 }
 
-// n deferred-finish weight gradients in one call (same result as n dat_conv3d_wgrad_acc calls): the pointwise layers among them share
-// grouped launches of wgrad_pw_kernel -- ~2 blocks per CU over ALL of them, every block about the same number of 32-position chunks --,
-// the others run one by one.
+int dat_conv3d_wgrad_plan(dat_ctx* ctx, const dat_conv_desc* d, int g_cstride, int Cin_real, int Cout_real, int acc_mode, int num_cu,
+                          dat_wgrad_plan* out) {
+    if (!d || !out || num_cu < 0 || (!ctx && num_cu == 0) || Cin_real <= 0 || Cout_real <= 0) return DAT_ERR_ARG;
+    dat_ctx env{};                  // ctx == NULL: nothing but the knobs, as dat_ctx_create reads them
+    if (!ctx) dat_ctx_read_env(&env);
+    dat_ctx* c = ctx ? ctx : &env;
+    if (int rc = wgrad_validate(c, d, g_cstride, acc_mode, "conv3d_wgrad_plan")) return rc;
+    *out = wgrad_plan(c, num_cu ? num_cu : dat_conv::ctx_num_cu(ctx), d, g_cstride, Cin_real, Cout_real, acc_mode);
+    return DAT_OK;
+}
+
+// n deferred-finish weight gradients in one call (same result as n dat_conv3d_wgrad_acc calls): every job is validated and planned like
+// one of those calls; the pointwise layers among them then share grouped launches of wgrad_pw_kernel (pointwise_batch_ksplit), the
+// others run one by one.
 int dat_conv3d_wgrad_acc_batch(dat_ctx* ctx, dat_stream s, const dat_wgrad_job* jobs, int n) {
     DAT_ENFORCE(ctx, jobs || n == 0, "conv3d_wgrad_acc_batch: null argument");
-    std::vector<PwPlan> pls;
+    const int ncu = dat_conv::ctx_num_cu(ctx);
+    std::vector<WgradPlan> plans((size_t)(n > 0 ? n : 0));
+    std::vector<WgradPlan*> pw;
     for (int i = 0; i < n; ++i) {
         const dat_wgrad_job& j = jobs[i];
-        DAT_ENFORCE(ctx, j.desc && j.x && j.g && j.Gt, "conv3d_wgrad_acc_batch: null member in job %d", i);
-        if (wgrad_direct_eligible(ctx, j.desc, j.g_cstride) && pw_eligible(ctx, j.desc)) {
-            PwPlan pl;
-            if (int rc = pw_plan(ctx, j.desc, j.x, j.g, j.g_cstride, j.Cin_real, j.Cout_real, j.Gt, &pl)) return rc;
-            pls.push_back(pl);
-        } else if (int rc = wgrad_impl(ctx, s, j.desc, j.x, j.g, j.g_cstride, j.Cin_real, j.Cout_real, nullptr, j.Gt, nullptr, 1)) {
-            return rc;
-        }
+        DAT_ENFORCE(ctx, j.desc && j.x && j.g && j.Gt && j.Cin_real > 0 && j.Cout_real > 0, "conv3d_wgrad_acc_batch: null member in job %d", i);
+        if (int rc = wgrad_validate(ctx, j.desc, j.g_cstride, 1, "conv3d_wgrad_acc_batch")) return rc;
+        plans[i] = wgrad_plan(ctx, ncu, j.desc, j.g_cstride, j.Cin_real, j.Cout_real, 1);
+        if (plans[i].family == DAT_WGRAD_POINTWISE) pw.push_back(&plans[i]);
     }
-    if (pls.empty()) return DAT_OK;
-    const int ncu = dat_conv::ctx_num_cu(ctx);
-    long long total = 0;
-    for (const PwPlan& pl : pls) total += pl.tiles * pl.nchunks;
-    const long long target = (pls.size() == 1 ? 1 : 2) * (long long)ncu;           // blocks in the grid(s)
-    long long cpb = (total + target - 1) / target;                                  // chunks per block
-    if (cpb < 4) cpb = 4;
-    for (PwPlan& pl : pls) {
-        long long ks = (pl.nchunks + cpb - 1) / cpb;
-        if (ctx->dbg_wgrad_ks > 0) ks = ctx->dbg_wgrad_ks;
-        if (ks > pl.nchunks) ks = pl.nchunks;
-        if (ks < 1) ks = 1;
-        pl.it.ksplit = (int)ks;
-        pl.it.atomic = 1;
-    }
-    return pw_launch(ctx, (hipStream_t)s, pls.data(), (int)pls.size());
+    for (int i = 0; i < n; ++i)
+        if (plans[i].family != DAT_WGRAD_POINTWISE)
+            if (int rc = wgrad_launch(ctx, (hipStream_t)s, plans[i], jobs[i], nullptr, jobs[i].Gt, nullptr)) return rc;
+    if (pw.empty()) return DAT_OK;
+    pointwise_batch_ksplit(ctx, ncu, pw.data(), pw.size());
+    std::vector<WgradPwItem> items;
+    for (int i = 0; i < n; ++i)
+        if (plans[i].family == DAT_WGRAD_POINTWISE) items.push_back(pw_item(plans[i], jobs[i]));
+    return pw_launch(ctx, (hipStream_t)s, items.data(), (int)items.size());
 }
 
 // dW[co][ci][tap] (+)= scale[co] * Gt[tap][co][ci] for a table of layers in ONE launch (blocks of 256 threads x 8 elements; an item owns

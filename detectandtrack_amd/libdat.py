@@ -47,6 +47,21 @@ class ConvPlan(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# dat_wgrad_plan.family
+WGRAD_REPACK, WGRAD_NINE_TAP, WGRAD_POINTWISE, WGRAD_DIRECT = range(4)
+
+
+class WgradPlan(C.Structure):
+    # what dat_conv3d_wgrad_plan says a dense weight-gradient launch does with a layer (dat_wgrad_plan, include/dat_hip.h)
+    _fields_ = [(n, C.c_int) for n in (
+        'family', 'variant', 'ncopies', 'npack', 'strip', 'tile_co', 'tile_ci', 'n_co_tiles', 'n_ci_tiles', 'taps', 'ksplit', 'atomic',
+        'memset_first', 'finish', 'blocks', 'threads', 'lds_bytes')] + \
+               [(n, C.c_longlong) for n in ('tiles', 'r_begin', 'r_end', 'nchunks')]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class PackItem(C.Structure):
     _fields_ = [('w', C.c_void_p), ('packed', C.c_void_p), ('scale', C.c_void_p)] + \
                [(n, C.c_int) for n in ('rows', 'cols', 'ntap', 'cout_pad', 'cin', 'dgrad', 'dtype', 'tile0', 'tiles_x', 'cit')]
@@ -132,6 +147,7 @@ _PROTOS = {
     'dat_conv3d_fwd_sum_mask': (_i, [_p, _p, C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _p]),
     'dat_conv3d_tune_plan': (_i, [_p, _i, _i]),
     'dat_conv3d_plan': (_i, [_p, C.POINTER(ConvDesc), _i, C.POINTER(ConvPlan)]),
+    'dat_conv3d_wgrad_plan': (_i, [_p, C.POINTER(ConvDesc), _i, _i, _i, _i, _i, C.POINTER(WgradPlan)]),
     'dat_conv3d_persistent_share': (_i, [_p, _i]),
     'dat_conv3d_flops': (_d, [C.POINTER(ConvDesc), _i, _i]),
     'dat_conv3d_grouped_packed_weight_bytes': (C.c_size_t, [C.POINTER(ConvDesc), _i]),

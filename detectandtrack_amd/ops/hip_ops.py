@@ -424,6 +424,17 @@ class ConvGrad(object):
             d.dil_h = d.dil_w = self.dilation
         return d
 
+    def plan(self, frames, T, H, W, g_frames=None, acc=False, num_cu=0):
+        """The launch plan the current context gives `weight` (acc: `weight_acc`) at that input shape (dat_conv3d_wgrad_plan: kernel
+        family, variant, tile, K split, atomics, memset / finish launches, grid ...) as a dict; g_frames as for `weight`.  num_cu 0 = the
+        device's CU count.  The grouped weight gradient has its own rule."""
+        assert self.groups == 1, 'dat_conv3d_wgrad_plan describes the dense weight-gradient launches'
+        d, out = self._fwd_desc(frames, T, H, W), L.WgradPlan()
+        if g_frames is not None and frames == T:
+            d.out_t0, d.out_tn = int(g_frames[0]), int(g_frames[1])
+        ctx().call('dat_conv3d_wgrad_plan', C.byref(d), self.g_cstride, self.cin, self.cout, int(acc), int(num_cu), C.byref(out))
+        return out.as_dict()
+
     def weight(self, x, g, T, want_dscale=False, g_frames=None, out=None):
         """x [frames,H,W,x_cstride], g [frames,Ho,Wo,g_cstride] -> (dW fp32 [Cout,Cin,KT,KH,KW] (already x scale),
         dscale fp32 [Cout] | None); out: a contiguous fp32 tensor of the weight's shape to write dW into (gradient arena)"""

@@ -562,6 +562,7 @@ typedef struct dat_wfinish_item {
     int Cout, Cin, ntaps, accumulate;
     long long block0;
 } dat_wfinish_item;
+/* (1: the plan's family is not DAT_WGRAD_REPACK.  ctx == NULL: answered for the knobs in the environment, without a GPU.) */
 int dat_conv3d_wgrad_acc_supported(dat_ctx* ctx, const dat_conv_desc* d, int g_cstride);
 int dat_conv3d_wgrad_acc(dat_ctx* ctx, dat_stream s, const dat_conv_desc* d, const void* x, const void* g, int g_cstride,
                          int Cin_real, int Cout_real, float* Gt);
@@ -578,6 +579,38 @@ typedef struct dat_wgrad_job {
     float* Gt;
 } dat_wgrad_job;
 int dat_conv3d_wgrad_acc_batch(dat_ctx* ctx, dat_stream s, const dat_wgrad_job* jobs, int n);
+/* The launch plan of a dat_conv3d_wgrad (acc_mode 0) / dat_conv3d_wgrad_acc (acc_mode 1) call: which kernel runs a layer, and how.  A pure
+ * function of the context's knobs (DAT_WGRAD_DIRECT / _PW / _SUB / _KS), the CU count and the arguments below -- it makes no HIP call and
+ * needs no GPU.  (dat_conv3d_wgrad_acc_batch plans every job the same way, then re-splits the pointwise layers over their shared grid.) */
+enum { DAT_WGRAD_REPACK = 0,      /* cq_pack_kernel launches + wgrad_gemm_kernel: fp32, and 16-bit layers the direct kernels do not take */
+       DAT_WGRAD_NINE_TAP = 1,    /* wgrad_dma9_kernel: 16-bit 3 x 3 spatial taps, stride 1, pad 1 */
+       DAT_WGRAD_POINTWISE = 2,   /* wgrad_pw_kernel: 16-bit 1 x 1 x 1 and FC */
+       DAT_WGRAD_DIRECT = 3 };    /* wgrad_direct_kernel: every other 16-bit layer, one block per tap */
+typedef struct dat_wgrad_plan {
+    int family;               /* DAT_WGRAD_* above */
+    int variant;              /* nine-tap: K ranges per block, 1 | 2 (wgrad_dma9_kernel<1|2>); pointwise: waves over the co axis, 1 | 2 | 4
+                                 (2: wgrad_pw_kernel<8>, 1 | 4: <10>); re-pack: the element type, DAT_F32 | DAT_BF16; direct: 0 */
+    int ncopies, npack;       /* re-pack: shifted copies of every x plane (1 | 2), and the cq_pack_kernel launches; 0 otherwise */
+    int strip;                /* pointwise, direct: 1 when a one-column output map (Wo == 1 < Ho) is addressed as a one-row strip */
+    int tile_co, tile_ci;     /* output x input channels of a block's tile */
+    int n_co_tiles, n_ci_tiles;
+    int taps;                 /* KT * KH * KW */
+    int ksplit;               /* K ranges, 1 <= ksplit <= max(nchunks, 1); nine-tap variant 2: even, a block takes two */
+    int atomic;               /* partial tiles are added with float atomics (several blocks per tile, or acc_mode) */
+    int memset_first;         /* a memset of the accumulator precedes the launch: atomic && !acc_mode */
+    int finish;               /* a wgrad_finish_kernel launch follows: !acc_mode */
+    int blocks, threads;      /* the grid and the block of the weight-gradient kernel */
+    int lds_bytes;            /* its dynamic LDS */
+    long long tiles;          /* n_co_tiles * n_ci_tiles * (nine-tap: KT; otherwise taps) */
+    long long r_begin, r_end; /* the reduced range [r_begin, r_end), in the family's unit -- nine-tap: frames; pointwise, direct: output
+                                 positions; re-pack: padded positions (k_begin and k_begin + K) */
+    long long nchunks;        /* the range in the units the K split deals out -- nine-tap: 8 x 8 patches; pointwise: chunks of 32 positions;
+                                 direct: chunks of 64; re-pack: K-steps of 64 elements (fp32: 32) */
+} dat_wgrad_plan;
+/* ctx != NULL: the plan that context's next launch takes; num_cu 0 = the device's.  ctx == NULL: the knobs as dat_ctx_create reads them from
+ * the environment, and num_cu > 0 compute units.  Returns what the launch would return for a descriptor it refuses. */
+int dat_conv3d_wgrad_plan(dat_ctx* ctx, const dat_conv_desc* d, int g_cstride, int Cin_real, int Cout_real, int acc_mode, int num_cu,
+                          dat_wgrad_plan* out);
 /* g = (dy [+ dy2]) * (y > 0 if relu) over [npos][cstride] (channels >= C zeroed); dbias[c] += sum_p g (may be NULL).
  * Relu backward on the fused conv's output + the bias / AffineChannelNd-bias reduction
  * (affine_channel_nd_op.cu:74-92). */

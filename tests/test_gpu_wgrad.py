@@ -1,7 +1,10 @@
 """Every weight-gradient kernel of csrc/train_ops.hip and every branch of their launchers, each output element against float64.
 
-dat_conv3d_wgrad / dat_conv3d_wgrad_acc / dat_conv3d_wgrad_acc_batch pick one of four kernels by the layer's geometry (wgrad_impl:
-wgrad_direct_eligible -> 3 x 3 stride-1 pad-1 test -> pw_eligible -> generic direct kernel; everything else re-packs):
+dat_conv3d_wgrad / dat_conv3d_wgrad_acc / dat_conv3d_wgrad_acc_batch pick one of four kernel families by the layer's geometry (wgrad_plan:
+wgrad_direct_eligible -> wgrad_nine_tap -> wgrad_pointwise -> the per-tap direct kernel; everything else re-packs).  Which family,
+instantiation, K split and store mode a (case, variant) lands on is asked of the library (hip_ops.ConvGrad.plan -> dat_conv3d_wgrad_plan),
+printed in the label of every check and asserted by the coverage tests; tests/test_wgrad_plan_cpu.py holds that plan to the independent
+statement of tests/wgrad_plan_cases.py:
 
     wgrad_dma9_kernel<1> / <2>          16-bit 3 x 3 spatial taps, stride 1, pad 1 (KT 1 | 3)
     wgrad_pw_kernel<8> / <10>           16-bit 1 x 1 x 1 and FC, stride 1 | 2
@@ -21,6 +24,7 @@ import pytest
 import torch
 
 from tests import numerics as nm
+from tests import wgrad_plan_cases as wpc
 from tests.test_gpu_train import PW_CASES, _ndhwc
 from tests.wgrad_refs import out_hw, wgrad_ref64, worst_ratio
 
@@ -86,6 +90,10 @@ class _Layer(object):
         self.x, self.gy = x, gy
         self.ref, self.absref, self.K = wgrad_ref64(x, gy, self.scale, k, st, pads, win)
 
+    def plan(self, acc=False):
+        """What the library will do with this layer under the current context's knobs (dat_conv3d_wgrad_plan)."""
+        return _plan(self.ops, self.case, acc, self.dt)
+
     def hold(self, dW, what, times=1):
         r = worst_ratio(dW.cpu(), times * self.ref, times * self.absref, self.K)
         print('wgrad err/bound %.4f  K=%-6d %s %s' % (r, self.K, what, _cid(self.case)))
@@ -112,9 +120,13 @@ class _Layer(object):
         self.hold(dW, what + ' deferred x2', times=2)
 
 
-# ---- the launchers' plans, restated (wgrad_impl in csrc/train_ops.hip), so that a case can SAY which branch it lands on and assert it ----------
-def _cdiv(a, b):
-    return (a + b - 1) // b
+# ---- the launchers' plans, asked of the library, so that a case can SAY which branch it lands on and assert it ------------------------------------
+def _plan(ops, case, acc=False, dt=None):
+    """dat_conv3d_wgrad_plan for a case under the current context's knobs, as a dict (family, variant, ksplit, atomic, r_begin, nchunks ...)."""
+    cin, cout, k, st, N, T, H, W, win = case
+    cg = ops.ConvGrad(torch.zeros((cout, cin) + k), None, (st, st), _pads(k), ops.BF16 if dt is None else dt, ops.round_up(cin, 64),
+                      ops.round_up(cout, 64))
+    return cg.plan(N * T, T, H, W, g_frames=win if (win is not None and N == 1) else None, acc=acc)
 
 
 def _frames(case):
@@ -122,54 +134,15 @@ def _frames(case):
     return win[1] if (win is not None and N == 1) else N * T
 
 
-def _nine_tap_plan(case, sub=2, forced_ks=0, acc=False):
-    """(SUB of the launched wgrad_dma9_kernel, K ranges, atomics) for a 3 x 3 stride-1 layer."""
-    cin, cout, k, st, N, T, H, W, win = case
-    tiles = k[0] * _cdiv(cout, 64) * _cdiv(cin, 64)
-    nchunks = _frames(case) * _cdiv(H, 8) * _cdiv(W, 8)
-    ks = _cdiv(384, tiles) if tiles <= 96 else _cdiv(768, tiles)
-    if sub == 2:
-        ks = 2 * (256 // tiles) if tiles <= 128 else 2
-    ks = min(ks, nchunks // 4)
-    if forced_ks > 0:
-        ks = forced_ks
-    ks = min(ks, nchunks)
-    if sub == 2:
-        ks &= ~1
-    sub2 = sub == 2 and ks >= 2
-    ks = max(ks, 1)
-    return (2 if sub2 else 1), ks, bool(ks > (2 if sub2 else 1) or acc)
-
-
-def _direct_ksplit(case):
-    """K ranges of wgrad_direct_kernel: min(1024 / tiles, chunks of 64 positions / 8); > 1 means memset + atomics and split > 0 blocks."""
-    cin, cout, k, st, N, T, H, W, win = case
-    Ho, Wo = out_hw(H, W, k, st, _pads(k))
-    tiles = int(np.prod(k)) * _cdiv(cout, 128) * _cdiv(cin, 128)
-    return max(1, min(1024 // tiles, _cdiv(_frames(case) * Ho * Wo, 64) // 8))
-
-
-def _gemm_plan(case, ck):
-    """(k_begin, the window's first padded position, K ranges) of wgrad_gemm_kernel over the re-packed position grid (ck 64 | 32 in fp32)."""
-    cin, cout, k, st, N, T, H, W, win = case
-    Ho, Wo = out_hw(H, W, k, st, _pads(k))
-    Hq, Wq = Ho + (k[1] - 1) // st, Wo + (k[2] - 1) // st
-    Wq += Wq & 1
-    K = _cdiv(N * (T + k[0] - 1) * Hq * Wq, ck) * ck
-    k_begin = first = 0
-    if win is not None and N == 1:
-        first = win[0] * Hq * Wq
-        k_begin = first // ck * ck
-        K = min(_cdiv((win[0] + win[1]) * Hq * Wq, ck) * ck, K) - k_begin
-    tiles = int(np.prod(k)) * _cdiv(cout, 128) * _cdiv(cin, 128)
-    return k_begin, first, max(1, min(1024 // tiles, (K // ck) // 16))
+def _ranges(p):
+    return '%d K range%s' % (p['ksplit'], '' if p['ksplit'] == 1 else 's')
 
 
 # ---- wgrad_dma9_kernel<2> / <1> ---------------------------------------------------------------------------------------------------------------
 NINE_TAP_CASES = [
     # cin, cout, (kt,kh,kw), stride, N, T, H, W, window -- all 16-bit, 3 x 3 spatial taps, stride 1, pad 1: wgrad_dma9_kernel.  Which
     # instantiation, how many K ranges and whether they meet in atomics follows from the chunk count (frames x 8 x 8 patches) and the forced
-    # split: _nine_tap_plan computes it per (case, variant), the label of every check prints it, the coverage test below asserts it.
+    # split: the library's plan says it per (case, variant), the label of every check prints it, the coverage test below asserts it.
     (64, 64, (3, 3, 3), 1, 1, 3, 8, 8, None),           # dma9, 3 chunks (one exact patch per frame): <1> by default, <2> with plain stores when forced
     (64, 64, (1, 3, 3), 1, 1, 2, 9, 17, None),          # dma9, 12 chunks, KT 1, partial patches on both edges: <2> plain stores by default, atomics at ks 4
     (130, 70, (3, 3, 3), 1, 1, 2, 7, 7, None),          # dma9, 2 chunks, channel strides 192 / 128 (masked tile columns), a map smaller than a patch
@@ -186,41 +159,50 @@ NINE_TAP_VARIANTS = [
 ]
 
 
-def _nine_tap_label(case, sub, forced, acc=False):
-    inst, ks, atomic = _nine_tap_plan(case, sub, forced, acc)
-    return 'dma9<%d> %d K range%s, %s (SUB=%d KS=%d)' % (inst, ks, '' if ks == 1 else 's', 'atomics' if atomic else 'plain stores', sub, forced)
+def _nine_tap_env(sub, forced):
+    return dict(({'DAT_WGRAD_SUB': '1'} if sub == 1 else {}), **({'DAT_WGRAD_KS': str(forced)} if forced else {}))
 
 
-def test_the_nine_tap_cases_reach_both_instantiations_with_plain_stores_atomics_and_clamps():
-    """From the launcher's arithmetic: the (case, variant) pairs of the test below run wgrad_dma9_kernel<2> and <1>, each with plain
+def _nine_tap_label(lay, sub, forced, acc=False):
+    """(asked under the context the launch will use)"""
+    p = lay.plan(acc)
+    assert p['family'] == wpc.NINE_TAP, p
+    return 'dma9<%d> %s, %s (SUB=%d KS=%d)' % (p['variant'], _ranges(p), 'atomics' if p['atomic'] else 'plain stores', sub, forced)
+
+
+def test_the_nine_tap_cases_reach_both_instantiations_with_plain_stores_atomics_and_clamps(ops, monkeypatch):
+    """From the library's plan: the (case, variant) pairs of the test below run wgrad_dma9_kernel<2> and <1>, each with plain
     stores and with atomics, and the clamps of a forced split (to the chunk count, to an even count, from two ranges down to <1>)."""
-    seen, clamps = set(), set()
-    for case in NINE_TAP_CASES:
-        nchunks = _frames(case) * _cdiv(case[6], 8) * _cdiv(case[7], 8)
-        for sub, forced in NINE_TAP_VARIANTS:
-            inst, ks, atomic = _nine_tap_plan(case, sub, forced)
-            seen.add((inst, atomic))
-            if forced > nchunks:
-                clamps.add('chunk count')
-            if sub == 2 and forced and min(forced, nchunks) & 1:
-                clamps.add('even' if inst == 2 else 'below two ranges')
+    seen, clamps, plans = set(), set(), {}
+    for sub, forced in NINE_TAP_VARIANTS:
+        with _env(ops, monkeypatch, _nine_tap_env(sub, forced)):
+            for case in NINE_TAP_CASES:
+                p = _plan(ops, case)
+                nchunks = _frames(case) * wpc.cdiv(case[6], 8) * wpc.cdiv(case[7], 8)
+                assert (p['family'], p['nchunks']) == (wpc.NINE_TAP, nchunks), p
+                inst, ks, atomic = plans[(case, sub, forced)] = (p['variant'], p['ksplit'], bool(p['atomic']))
+                assert p['memset_first'] == atomic and p['blocks'] == p['tiles'] * ks // inst, p
+                seen.add((inst, atomic))
+                if forced > nchunks:
+                    clamps.add('chunk count')
+                if sub == 2 and forced and min(forced, nchunks) & 1:
+                    clamps.add('even' if inst == 2 else 'below two ranges')
     assert seen == {(2, False), (2, True), (1, False), (1, True)}, seen
     assert clamps == {'chunk count', 'even', 'below two ranges'}, clamps
-    assert _nine_tap_plan(NINE_TAP_CASES[0], 2, 5) == (2, 2, False)         # (3 chunks: a forced 5 is clamped to 3, then to 2: plain stores)
-    assert _nine_tap_plan(NINE_TAP_CASES[1], 2, 5) == (2, 4, True)
+    assert plans[(NINE_TAP_CASES[0], 2, 5)] == (2, 2, False)         # (3 chunks: a forced 5 is clamped to 3, then to 2: plain stores)
+    assert plans[(NINE_TAP_CASES[1], 2, 5)] == (2, 4, True)
 
 
 @pytest.mark.parametrize('case', NINE_TAP_CASES, ids=_cid)
 def test_wgrad_dma9_kernel_sub2_and_sub1_every_split(ops, monkeypatch, case):
     lay = _Layer(ops, case)
     for sub, forced in NINE_TAP_VARIANTS:
-        env = dict(({'DAT_WGRAD_SUB': '1'} if sub == 1 else {}), **({'DAT_WGRAD_KS': str(forced)} if forced else {}))
-        with _env(ops, monkeypatch, env):
-            lay.immediate(_nine_tap_label(case, sub, forced))
-    lay.deferred(_nine_tap_label(case, 2, 0, acc=True) + ' acc mode')
+        with _env(ops, monkeypatch, _nine_tap_env(sub, forced)):
+            lay.immediate(_nine_tap_label(lay, sub, forced))
+    lay.deferred(_nine_tap_label(lay, 2, 0, acc=True) + ' acc mode')
     with _env(ops, monkeypatch, {'DAT_WGRAD_SUB': '1'}):
-        lay.deferred(_nine_tap_label(case, 1, 0, acc=True) + ' acc mode')
-    _Layer(ops, case, with_scale=False).immediate(_nine_tap_label(case, 2, 0) + ' no scale')
+        lay.deferred(_nine_tap_label(lay, 1, 0, acc=True) + ' acc mode')
+    _Layer(ops, case, with_scale=False).immediate(_nine_tap_label(lay, 2, 0) + ' no scale')
 
 
 # ---- wgrad_pw_kernel<8> / <10> -----------------------------------------------------------------------------------------------------------------
@@ -229,7 +211,7 @@ def _pw(c):
     return (cin, cout, (1, 1, 1), st, N, T, H, W, win)
 
 
-# (the ten PW_CASES: their own comments in tests/test_gpu_train.py name the tile shape pw_plan picks -- 256 x 256 is wgrad_pw_kernel<8>,
+# (the ten PW_CASES: their own comments in tests/test_gpu_train.py name the tile shape wgrad_plan picks -- 256 x 256 is wgrad_pw_kernel<8>,
 #  128 x 512 and 512 x 128 are <10>; the default K split is one block per CU, at least 4 chunks of 32 positions per block)
 POINTWISE_CASES = [_pw(c) for c in PW_CASES] + [
     (256, 128, (1, 1, 1), 2, 1, 2, 6, 2, None),         # pw<8> (256 x 256), stride 2, Wo == 1 < Ho: column_strip relabels the column as a strip
@@ -258,7 +240,10 @@ def test_wgrad_pw_kernel_8_and_10_panels_every_tile_and_split(ops, monkeypatch, 
     assert lay.cg.pointwise
     for what, env in POINTWISE_VARIANTS:
         with _env(ops, monkeypatch, env):
-            lay.immediate(what)
+            p = lay.plan()
+            assert p['family'] == wpc.POINTWISE and p['variant'] == int(env.get('DAT_WGRAD_PW', 10 * p['variant'])) // 10, (what, p)
+            lay.immediate('%s: pw<%d> %d x %d, %s, %s' % (what, 8 if p['variant'] == 2 else 10, p['tile_co'], p['tile_ci'], _ranges(p),
+                                                        'atomics' if p['atomic'] else 'plain stores'))
     lay.deferred('pw acc mode')
     _Layer(ops, case, with_scale=False).immediate('pw no scale')
 
@@ -333,17 +318,23 @@ DIRECT_SPLIT_CASES = [
 DIRECT_CASES += DIRECT_SPLIT_CASES
 
 
-def test_the_direct_kernel_cases_include_several_k_ranges():
-    """From the launcher's arithmetic: DIRECT_SPLIT_CASES run wgrad_direct_kernel with ksplit > 1, the other cases with one range."""
-    assert [_direct_ksplit(c) for c in DIRECT_SPLIT_CASES] == [2, 4, 2, 2, 2]
-    assert all(_direct_ksplit(c) == 1 for c in DIRECT_CASES if c not in DIRECT_SPLIT_CASES)
+def _direct_ksplit(ops, case):
+    p = _plan(ops, case)
+    assert p['family'] == wpc.DIRECT and p['atomic'] == p['memset_first'] == (p['ksplit'] > 1) and p['blocks'] == p['tiles'] * p['ksplit'], p
+    return p['ksplit']
+
+
+def test_the_direct_kernel_cases_include_several_k_ranges(ops):
+    """From the library's plan: DIRECT_SPLIT_CASES run wgrad_direct_kernel with ksplit > 1, the other cases with one range."""
+    assert [_direct_ksplit(ops, c) for c in DIRECT_SPLIT_CASES] == [2, 4, 2, 2, 2]
+    assert all(_direct_ksplit(ops, c) == 1 for c in DIRECT_CASES if c not in DIRECT_SPLIT_CASES)
 
 
 @pytest.mark.parametrize('case', DIRECT_CASES, ids=_cid)
 def test_wgrad_direct_kernel_temporal_and_stride2_layers(ops, case):
     lay = _Layer(ops, case)
     assert not lay.cg.pointwise
-    ks = _direct_ksplit(case)
+    ks = _direct_ksplit(ops, case)
     assert (ks > 1) == (case in DIRECT_SPLIT_CASES)
     lay.immediate('direct, %d K range%s, %s' % (ks, '' if ks == 1 else 's', 'memset + atomics' if ks > 1 else 'plain stores'))
     lay.deferred('direct acc mode, %d K range%s' % (ks, '' if ks == 1 else 's'))
@@ -357,6 +348,7 @@ def test_wgrad_direct_kernel_on_the_nine_tap_shapes(ops, monkeypatch, case):
     lay = _Layer(ops, case)
     one_column = case[7] == 1 and case[6] > 1
     with _env(ops, monkeypatch, {'DAT_WGRAD_DIRECT': '2'}):
+        assert lay.plan()['family'] == (wpc.REPACK if one_column else wpc.DIRECT)
         lay.immediate('gemm<BF16> (3 x 3 taps, one column)' if one_column else 'direct, nine-tap shape')
         lay.deferred('direct acc mode, nine-tap shape', expect_supported=not one_column)
 
@@ -366,6 +358,9 @@ def test_wgrad_direct_kernel_on_the_pointwise_shapes(ops, monkeypatch, case):
     """DAT_WGRAD_PW=0: pointwise layers on wgrad_direct_kernel (one tap), the 6 x 2 / 7 x 1 / 9 x 1 one-column maps relabelled as strips."""
     lay = _Layer(ops, case)
     with _env(ops, monkeypatch, {'DAT_WGRAD_PW': '0'}):
+        p = lay.plan()
+        Ho, Wo = out_hw(case[6], case[7], case[2], case[3], _pads(case[2]))
+        assert p['family'] == wpc.DIRECT and p['strip'] == (Wo == 1 and Ho > 1), p
         lay.immediate('direct, pointwise shape')
         lay.deferred('direct acc mode, pointwise shape')
 
@@ -385,8 +380,9 @@ def test_cq_pack_and_wgrad_gemm_kernel_f32_on_every_geometry(ops, case):
     """fp32 training: every layer re-packs (stride-parity planes, one copy) and runs wgrad_gemm_kernel<F32>; the label carries k_begin
     (windows) and the K ranges (several from 1024 padded positions on: DIRECT_SPLIT_CASES)."""
     lay = _Layer(ops, case, dt=ops.F32)
-    k_begin, _, ks = _gemm_plan(case, 32)
-    lay.immediate('gemm<F32> k_begin %d, %d K range%s' % (k_begin, ks, '' if ks == 1 else 's'))
+    p = lay.plan()
+    assert (p['family'], p['variant']) == (wpc.REPACK, ops.F32), p
+    lay.immediate('gemm<F32> k_begin %d, %s' % (p['r_begin'], _ranges(p)))
     lay.deferred('', expect_supported=False)
 
 
@@ -400,19 +396,30 @@ REPACK_16BIT_CASES = [
 ]
 
 
-def test_the_16_bit_repack_cases_reach_an_off_boundary_k_begin_and_several_k_ranges():
-    """From the launcher's arithmetic (wgrad_geom, wgrad_impl): the windows of the stride-2 and the stride-1 case start off a 64-element
+def _gemm_plan(ops, case):
+    """(k_begin, the window's first padded position, K ranges) of wgrad_gemm_kernel<BF16> over the re-packed position grid: k_begin and
+    the ranges from the library's plan, the first position from the geometry (window start x padded frame)."""
+    p = _plan(ops, case)
+    assert (p['family'], p['variant']) == (wpc.REPACK, ops.BF16) and p['memset_first'] == (p['ksplit'] > 1), p
+    d = wpc.from_case(case)['d']
+    Hq, Wq = wpc.repack_geometry(d)[:2]
+    return p['r_begin'], d['out_t0'] * Hq * Wq, p['ksplit']
+
+
+def test_the_16_bit_repack_cases_reach_an_off_boundary_k_begin_and_several_k_ranges(ops, monkeypatch):
+    """From the library's plan (wgrad_geom, wgrad_plan): the windows of the stride-2 and the stride-1 case start off a 64-element
     boundary behind a non-zero k_begin -- a launcher that ignored k_begin, or did not round it down, would miss positions -- and the
     largest case splits K."""
-    plans = [_gemm_plan(c, 64) for c in REPACK_16BIT_CASES]
+    with _env(ops, monkeypatch, {'DAT_WGRAD_DIRECT': '0'}):
+        plans = [_gemm_plan(ops, c) for c in REPACK_16BIT_CASES]
     assert plans == [(64, 96, 1), (384, 440, 1), (0, 0, 1), (0, 0, 2)], plans
 
 
 @pytest.mark.parametrize('case', REPACK_16BIT_CASES, ids=_cid)
 def test_cq_pack_and_wgrad_gemm_kernel_bf16_under_direct_0(ops, monkeypatch, case):
     lay = _Layer(ops, case)
-    k_begin, _, ks = _gemm_plan(case, 64)
     with _env(ops, monkeypatch, {'DAT_WGRAD_DIRECT': '0'}):
+        k_begin, _, ks = _gemm_plan(ops, case)
         lay.immediate('gemm<BF16> k_begin %d, %d K range%s' % (k_begin, ks, '' if ks == 1 else 's'))
         lay.deferred('', expect_supported=False)
 
