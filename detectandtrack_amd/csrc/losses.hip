@@ -47,8 +47,23 @@ struct RpnLossParams {
                         //    (a*4 + c) of tube slot t.  0: one frame per clip with 4*T*A delta channels
     float cls_mult;     // scale / norm
     float bbox_beta, bbox_mult;   // scale / N
-    float* loss;        // [2]: cls, bbox (accumulated with atomics)
+    float* partial;     // [blocks][2]: every block's cls / bbox sums (loss_partial_reduce_kernel adds them up)
 };
+
+// The loss VALUE of a launch.  Every block stores the sum(s) over its positions as one row of `partial` ([blocks][n], in the context's
+// scratch, like the bias partials of relu_bias_bwd) and this one-block launch adds the rows up in block order and adds the scaled sums
+// to loss[0 .. n).  (One float atomicAdd per block made the value depend on the order in which the blocks retired: its last bits
+// differed between two runs on the same input.  The gradients never went through the atomics.)
+__global__ __launch_bounds__(256) void loss_partial_reduce_kernel(const float* __restrict__ partial, int blocks, int n, float mult0,
+                                                                  float mult1, float* __restrict__ loss) {
+    __shared__ float red[256];
+    for (int j = 0; j < n; ++j) {
+        float v = 0.f;
+        for (int i = threadIdx.x; i < blocks; i += blockDim.x) v += partial[(size_t)i * n + j];
+        v = block_sum(v, red);
+        if (threadIdx.x == 0) loss[j] += v * (j == 0 ? mult0 : mult1);
+    }
+}
 
 __global__ __launch_bounds__(256) void rpn_loss_kernel(const RpnLossParams p) {
     __shared__ float red[256];
@@ -97,14 +112,14 @@ __global__ __launch_bounds__(256) void rpn_loss_kernel(const RpnLossParams p) {
     }
     const float sc = block_sum(lc, red), sb = block_sum(lb, red);
     if (threadIdx.x == 0) {
-        atomicAdd(p.loss + 0, sc * p.cls_mult);
-        atomicAdd(p.loss + 1, sb * p.bbox_mult);
+        p.partial[2 * (size_t)blockIdx.x + 0] = sc;
+        p.partial[2 * (size_t)blockIdx.x + 1] = sb;
     }
 }
 
 __global__ __launch_bounds__(256) void smooth_l1_rows_kernel(const void* pred, int dtype, int ld, const float* tgt, const float* w_in,
                                                              const float* w_out, int R, int D, float beta, float mult, void* dpred,
-                                                             float* loss) {
+                                                             float* partial) {
     __shared__ float red[256];
     float l = 0.f;
     const long long total = (long long)R * ld;
@@ -123,13 +138,13 @@ __global__ __launch_bounds__(256) void smooth_l1_rows_kernel(const void* pred, i
         stf(dpred, dtype, i, grad);
     }
     const float s = block_sum(l, red);
-    if (threadIdx.x == 0) atomicAdd(loss, s * mult);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 // one block per row; D up to a few thousand (56*56 spatial softmax)
 __global__ __launch_bounds__(256) void softmax_ce_rows_kernel(const void* logits, int dtype, int ld, const int* labels,
                                                               const float* weights, int R, int D, float mult, void* dlogits,
-                                                              int dl_dtype, int dl_ld, float* loss, int* correct) {
+                                                              int dl_dtype, int dl_ld, float* partial, int* correct) {
     __shared__ float red[256];
     __shared__ int redi[256];
     const int r = blockIdx.x, tid = threadIdx.x;
@@ -168,8 +183,8 @@ __global__ __launch_bounds__(256) void softmax_ce_rows_kernel(const void* logits
     }
     if (tid == 0) {
         const float pl = expf(ldf(logits, dtype, base + label) - m) / s;
-        atomicAdd(loss, -w * logf(fmaxf(pl, 1e-20f)) * mult);
-        if (correct && argmax == label) atomicAdd(correct, 1);
+        partial[r] = -w * logf(fmaxf(pl, 1e-20f));
+        if (correct && argmax == label) atomicAdd(correct, 1);      // (an integer count: the same in any order)
     }
 }
 
@@ -190,11 +205,16 @@ int dat_rpn_loss(dat_ctx* ctx, dat_stream s, int dtype, const void* head, void* 
     p.dtype = dtype; p.N = N; p.H = H; p.W = W; p.cs = cstride; p.A = A; p.logit_off = logit_off; p.delta_off = delta_off;
     p.T = T; p.per_frame = per_frame;
     p.Hw = Hw; p.Ww = Ww; p.cls_mult = cls_scale_over_norm; p.bbox_beta = bbox_beta; p.bbox_mult = bbox_scale_over_n;
-    p.loss = loss2;
     const long long npos = (long long)N * (per_frame ? T : 1) * H * W;
+    if (npos == 0) return DAT_OK;
     long long blocks = (npos + 255) / 256;
     if (blocks > 2048) blocks = 2048;
+    const int rc = dat_ensure_ws(ctx, (size_t)blocks * 2 * sizeof(float));
+    if (rc != DAT_OK) return rc;
+    p.partial = (float*)ctx->ws;
     hipLaunchKernelGGL(rpn_loss_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)s, p);
+    hipLaunchKernelGGL(loss_partial_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)p.partial, (int)blocks, 2,
+                       cls_scale_over_norm, bbox_scale_over_n, loss2);
     DAT_CHECK_LAUNCH(ctx, "rpn_loss");
     return DAT_OK;
 }
@@ -205,8 +225,13 @@ int dat_smooth_l1_rows(dat_ctx* ctx, dat_stream s, int dtype, const void* pred, 
     if (R == 0) return DAT_OK;
     long long blocks = ((long long)R * ld + 255) / 256;
     if (blocks > 2048) blocks = 2048;
+    const int rc = dat_ensure_ws(ctx, (size_t)blocks * sizeof(float));
+    if (rc != DAT_OK) return rc;
+    float* partial = (float*)ctx->ws;
     hipLaunchKernelGGL(smooth_l1_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)s, pred, dtype, ld, targets, inside,
-                       outside, R, D, beta, scale_over_n, dpred, loss);
+                       outside, R, D, beta, scale_over_n, dpred, partial);
+    hipLaunchKernelGGL(loss_partial_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)partial, (int)blocks, 1,
+                       scale_over_n, 0.f, loss);
     DAT_CHECK_LAUNCH(ctx, "smooth_l1_rows");
     return DAT_OK;
 }
@@ -215,8 +240,13 @@ int dat_softmax_ce_rows(dat_ctx* ctx, dat_stream s, int dtype, const void* logit
                         int R, int D, float scale_over_norm, int dl_dtype, void* dlogits, int dl_ld, float* loss, int* correct) {
     DAT_ENFORCE(ctx, logits && labels && dlogits && loss && ld >= D && dl_ld >= D, "softmax_ce_rows: bad argument");
     if (R == 0) return DAT_OK;
+    const int rc = dat_ensure_ws(ctx, (size_t)R * sizeof(float));
+    if (rc != DAT_OK) return rc;
+    float* partial = (float*)ctx->ws;      // one entry per row (= per block)
     hipLaunchKernelGGL(softmax_ce_rows_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)s, logits, dtype, ld, labels, weights, R, D,
-                       scale_over_norm, dlogits, dl_dtype, dl_ld, loss, correct);
+                       scale_over_norm, dlogits, dl_dtype, dl_ld, partial, correct);
+    hipLaunchKernelGGL(loss_partial_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)partial, R, 1, scale_over_norm,
+                       0.f, loss);
     DAT_CHECK_LAUNCH(ctx, "softmax_ce_rows");
     return DAT_OK;
 }

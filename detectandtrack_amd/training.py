@@ -989,7 +989,6 @@ class Trainer(object):
         mode = getattr(ws, 'dtype', None) or cfg.HIP.DTYPE
         assert mode in ('bf16', 'fp32'), "cfg.HIP.DTYPE %r is an inference mode (train in 'bf16' or 'fp32')" % (mode,)
         _mode(ws)       # (the 16-bit mode must match the loaded build)
-        self.trainable = list(model.TrainableParams())
         self.biases = set(model.biases)
         self.iter = 0
         # Flat order = the order in which the backward pass COMPLETES the gradients (heads first, res3 last; weights, then biases):
@@ -999,6 +998,11 @@ class Trainer(object):
         planner._plan_rpn_siblings()
         self.ready_index = param_ready_index(model.net, planner._fused)
         n_ops = len(model.net.ops)
+        # What the reference updates (detector.py:57-65 `p in self.param_to_grad`, model_builder.py:966): a parameter that no
+        # differentiated op uses -- conv1 / res2 and their BN / GN pairs below the StopGradient marker -- has no gradient there, so it
+        # gets no update op: no momentum, no weight decay.  It stays out of the flat buffers (it used to sit in them with a zero
+        # gradient, and the weight-decay term of the update shrank the frozen trunk by lr * WEIGHT_DECAY every iteration).
+        self.trainable = [n for n in model.TrainableParams() if self.ready_index.get(n, -1) != n_ops]
         rank_of = {n: i for i, n in enumerate(self.trainable)}
         by_done = sorted(self.trainable, key=lambda n: (-self.ready_index.get(n, -1), rank_of[n]))   # unreferenced parameters last
         order = [n for n in by_done if n not in self.biases] + [n for n in by_done if n in self.biases]

@@ -630,7 +630,9 @@ int dat_roi_align_bwd(dat_ctx* ctx, dat_stream s, int dtype, float* const* dfeat
 /* backward of dat_kps_finalize: dout fp32 [R, Tr*K, M, M] -> dsub [R*Tr, S, S, cs] (channels >= 4K zero) */
 int dat_kps_finalize_bwd(dat_ctx* ctx, dat_stream s, int dtype, const float* dout, int R, int Tr, int S, int cs, int K, int up,
                          void* dsub);
-/* ---- losses: value + gradient w.r.t. the prediction in one pass (model_builder.py:481-494, 612-636, 873-889; FPN.py:282-321) */
+/* ---- losses: value + gradient w.r.t. the prediction in one pass (model_builder.py:481-494, 612-636, 873-889; FPN.py:282-321).
+ * The loss VALUE is summed per block into the context's scratch and added up in block order by a second, one-block launch:
+ * the same input gives the same bits on every run.  The loss words are read and written by that launch only (no atomics). */
 /* RPN losses of one level on the fused head tensor [N, H, W, cstride] (logits at logit_off + a, deltas at delta_off + a*4 + c):
  * SigmoidCrossEntropyLoss on the logits (labels int32 (N, A, Hw, Ww), -1 = ignore) and SmoothL1Loss on the deltas (targets /
  * inside / outside weights fp32 (N, 4A, Hw, Ww)); the wide label arrays are narrowed to H x W by indexing (SpatialNarrowAs).

@@ -533,7 +533,8 @@ def test_gradient_completion_order_of_the_training_graph():
     idx = param_ready_index(m.net, ex._fused)
     train = list(m.TrainableParams())
     assert all(n in idx for n in train), [n for n in train if n not in idx]
-    # conv1 / res2 sit below StopGradient: listed as trainable (they take part in the update with a zero gradient), final at once
+    # conv1 / res2 sit below StopGradient: the model lists them as trainable, they are final at once (and the Trainer, which reads
+    # this index, keeps them out of its update: tests/test_gpu_trainer_state.py)
     frozen = [n for n in train if n.startswith(('conv1', 'res2'))]
     assert frozen and all(idx[n] == len(m.net.ops) for n in frozen)
     uses = {}
