@@ -309,12 +309,15 @@ def _build_defaults():
     # (lib/utils/keypoints.py:221-263); the reference's wiring sits behind a raise and hard-codes the threshold 0.3, here it is a key.
     # For tubes the reference defines nothing: without TUBE_NMS_OKS they raise its NotImplementedError('Handle tubes'), with it the
     # overlap of two tubes is the float64 mean of their T per-frame OKS values, each with the kept tube's box of that frame as the area
-    # NONLOCAL (opt-in, inference only): a comma-separated list of body blocks of res3 / res4 ('res3_1,res4_1') that are
+    # NONLOCAL (opt-in; training: opt-in with TRAIN_NONLOCAL): a comma-separated list of body blocks of res3 / res4 ('res3_1,res4_1') that are
     # followed by a spacetime non-local block (Wang et al., CVPR 2018, embedded Gaussian): theta / phi / g 1x1x1 convs to C / 2 channels, every
     # position of the clip attends to every (pooled) position of the clip in one fused launch that never writes the scores (csrc/nonlocal.hip),
     # then a 1x1x1 conv + affine (scale initialised to zero) + the block's input, no ReLU.  Behind the last block of a stage the output keeps
-    # the stage's name, so FPN and the heads read it.  Empty: every graph is what it is without the key.  Not combinable with training,
+    # the stage's name, so FPN and the heads read it.  Empty: every graph is what it is without the key.  Not combinable with
     # HIP.KEYFRAME_DCE or HIP.FRAME_TRUNK_CACHE.
+    # TRAIN_NONLOCAL (opt-in until measured at full size, like TRAIN_GROUPED_CONV): training graphs with HIP.NONLOCAL build -- the forward stores
+    # the row statistic, the backward recomputes P (csrc/nonlocal_bwd.hip), and under the affine default the block's closing `_out_bn` affine is
+    # recorded unfused (`AffineTrain`) so that its zero-initialised scale trains.  Test-mode graphs do not change with the switch.
     # NONLOCAL_MAXPOOL: phi and g go through MaxPool [1, 2, 2] / stride [1, 2, 2] / pad 0 first (a quarter of the keys).
     # NONLOCAL_SCALE: the scores are scaled by (C / 2)^-1/2 before the softmax; off, by 1
     c.HIP = AttrDict({'DTYPE': 'bf16', 'KEYFRAME_DCE': False, 'DEVICE_KPS_DECODE': True, 'FRAME_TRUNK_CACHE': 0,
@@ -325,7 +328,7 @@ def _build_defaults():
                       'TRAIN_GROUPED_CONV': False, 'USE_GN': False, 'GN_NUM_GROUPS': 32, 'GN_EPSILON': 1e-5, 'GN_KPS_HEAD': False,
                       'TUBE_SOFT_NMS': False, 'TRACK_CNN_WEIGHTS': '',
                       'TUBE_NMS_OKS': False, 'NMS_OKS_THRESH': 0.3,
-                      'NONLOCAL': '', 'NONLOCAL_MAXPOOL': True, 'NONLOCAL_SCALE': True})
+                      'NONLOCAL': '', 'NONLOCAL_MAXPOOL': True, 'NONLOCAL_SCALE': True, 'TRAIN_NONLOCAL': False})
     return c
 
 

@@ -19,6 +19,8 @@
 // reproducible and does not depend on the number of clips in the launch.
 #include "dat_common.h"
 
+#include <type_traits>
+
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
@@ -33,6 +35,10 @@ struct NlParams {
     long long Lq, Lk;
     int ldq, ldk, ldv, ldy;
     float c;   // scale * log2(e)
+};
+// the training forward also stores the row statistic lse_i = m_i + log2(l_i) (in the units of c * score) that the backward recomputes P from
+struct NlParamsLse : NlParams {
+    float* lse;
 };
 
 template <int DT, int D, int DV>
@@ -52,8 +58,8 @@ struct NlCfg {
 // row of a 32 x 32 MFMA result held in accumulator register `reg` of lane half `h`
 __device__ __forceinline__ int nl_crow(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
-template <int DT, int D, int DV>
-__global__ __launch_bounds__(256) void nonlocal_attention_kernel(NlParams p) {
+template <int DT, int D, int DV, bool LSE>
+__global__ __launch_bounds__(256) void nonlocal_attention_kernel(typename std::conditional<LSE, NlParamsLse, NlParams>::type p) {
     typedef NlCfg<DT, D, DV> Cfg;
     typedef typename ElemOf<DT>::type T;
     extern __shared__ __align__(16) unsigned char nl_smem[];
@@ -265,6 +271,8 @@ __global__ __launch_bounds__(256) void nonlocal_attention_kernel(NlParams p) {
 
     if (!qvalid) return;
     const float l = l_run + __shfl_xor(l_run, 32);   // the partner lane holds the same (valid) query row
+    if constexpr (LSE)
+        if (h == 0 && blockIdx.z == 0) p.lse[clip * p.Lq + qrow] = m_run + __log2f(l);
     T* yp = (T*)p.y + (size_t)(clip * p.Lq + qrow) * p.ldy + dv0;
 #pragma unroll
     for (int n = 0; n < DV / 32; ++n)
@@ -279,23 +287,20 @@ __global__ __launch_bounds__(256) void nonlocal_attention_kernel(NlParams p) {
         }
 }
 
-template <int DT, int D, int DV>
-int nl_launch(dat_ctx* ctx, hipStream_t s, const dat_nonlocal_desc* d, const NlParams& p) {
+template <int DT, int D, int DV, bool LSE>
+int nl_launch(dat_ctx* ctx, hipStream_t s, const dat_nonlocal_desc* d, const typename std::conditional<LSE, NlParamsLse, NlParams>::type& p) {
     typedef NlCfg<DT, D, DV> Cfg;
-    const void* kern = (const void*)nonlocal_attention_kernel<DT, D, DV>;
+    const void* kern = (const void*)nonlocal_attention_kernel<DT, D, DV, LSE>;
     const int rc = dat_ensure_lds(ctx, kern, Cfg::LDS_BYTES);
     if (rc != DAT_OK) return rc;
     const dim3 grid((unsigned)((d->Lq + NL_ROWS - 1) / NL_ROWS), (unsigned)d->clips, (unsigned)(D / DV));
-    hipLaunchKernelGGL((nonlocal_attention_kernel<DT, D, DV>), grid, dim3(256), Cfg::LDS_BYTES, s, p);
+    hipLaunchKernelGGL((nonlocal_attention_kernel<DT, D, DV, LSE>), grid, dim3(256), Cfg::LDS_BYTES, s, p);
     DAT_CHECK_LAUNCH(ctx, "nonlocal_attention");
     return DAT_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int dat_nonlocal_attention(dat_ctx* ctx, dat_stream s, const dat_nonlocal_desc* d, const void* q, const void* k, const void* v, void* y) {
+// argument checks shared by the two forward entry points; fills the launch parameters
+int nl_check(dat_ctx* ctx, const dat_nonlocal_desc* d, const void* q, const void* k, const void* v, void* y, NlParams& p) {
     DAT_ENFORCE(ctx, ctx && d, "nonlocal_attention: null context or descriptor");
     if (d->dtype != DAT_F32 && d->dtype != DAT_BF16)
         DAT_FAIL(ctx, DAT_ERR_UNSUPPORTED, "nonlocal_attention: dtype %d (DAT_F32 | DAT_BF16)", d->dtype);
@@ -314,26 +319,52 @@ int dat_nonlocal_attention(dat_ctx* ctx, dat_stream s, const dat_nonlocal_desc* 
     DAT_ENFORCE(ctx, q && k && v && y, "nonlocal_attention: null pointer (q %p, k %p, v %p, y %p)", q, k, v, y);
     DAT_ENFORCE(ctx, (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)y) & 15) == 0,
                 "nonlocal_attention: q, k, v and y must be 16-byte aligned");
-    NlParams p;
     p.q = q; p.k = k; p.v = v; p.y = y;
     p.Lq = d->Lq; p.Lk = d->Lk;
     p.ldq = d->ldq; p.ldk = d->ldk; p.ldv = d->ldv; p.ldy = d->ldy;
     p.c = d->scale * 1.44269504088896340736f;
-    hipStream_t st = (hipStream_t)s;
+    return DAT_OK;
+}
+
+template <bool LSE>
+int nl_dispatch(dat_ctx* ctx, hipStream_t st, const dat_nonlocal_desc* d, const typename std::conditional<LSE, NlParamsLse, NlParams>::type& p) {
     if (d->dtype == DAT_BF16) {
         switch (d->D) {
-            case 64: return nl_launch<DAT_BF16, 64, 64>(ctx, st, d, p);
-            case 128: return nl_launch<DAT_BF16, 128, 128>(ctx, st, d, p);
-            case 256: return nl_launch<DAT_BF16, 256, 256>(ctx, st, d, p);
-            default: return nl_launch<DAT_BF16, 512, 256>(ctx, st, d, p);   // two value slices, scores recomputed per slice
+            case 64: return nl_launch<DAT_BF16, 64, 64, LSE>(ctx, st, d, p);
+            case 128: return nl_launch<DAT_BF16, 128, 128, LSE>(ctx, st, d, p);
+            case 256: return nl_launch<DAT_BF16, 256, 256, LSE>(ctx, st, d, p);
+            default: return nl_launch<DAT_BF16, 512, 256, LSE>(ctx, st, d, p);   // two value slices, scores recomputed per slice
         }
     }
     switch (d->D) {
-        case 64: return nl_launch<DAT_F32, 64, 64>(ctx, st, d, p);
-        case 128: return nl_launch<DAT_F32, 128, 128>(ctx, st, d, p);
-        case 256: return nl_launch<DAT_F32, 256, 128>(ctx, st, d, p);
-        default: return nl_launch<DAT_F32, 512, 64>(ctx, st, d, p);
+        case 64: return nl_launch<DAT_F32, 64, 64, LSE>(ctx, st, d, p);
+        case 128: return nl_launch<DAT_F32, 128, 128, LSE>(ctx, st, d, p);
+        case 256: return nl_launch<DAT_F32, 256, 128, LSE>(ctx, st, d, p);
+        default: return nl_launch<DAT_F32, 512, 64, LSE>(ctx, st, d, p);
     }
+}
+
+}  // namespace
+
+extern "C" {
+
+int dat_nonlocal_attention(dat_ctx* ctx, dat_stream s, const dat_nonlocal_desc* d, const void* q, const void* k, const void* v, void* y) {
+    NlParams p;
+    const int rc = nl_check(ctx, d, q, k, v, y, p);
+    if (rc != DAT_OK) return rc;
+    return nl_dispatch<false>(ctx, (hipStream_t)s, d, p);
+}
+
+// The same kernel, also storing lse[clip * Lq + i] = m_i + log2(l_i) (fp32, in the units of scale * log2(e) * score): what the backward
+// (nonlocal_bwd.hip) recomputes P from.  y is bit-identical to dat_nonlocal_attention.
+int dat_nonlocal_attention_lse(dat_ctx* ctx, dat_stream s, const dat_nonlocal_desc* d, const void* q, const void* k, const void* v, void* y,
+                               float* lse) {
+    NlParamsLse p;
+    const int rc = nl_check(ctx, d, q, k, v, y, p);
+    if (rc != DAT_OK) return rc;
+    DAT_ENFORCE(ctx, lse && ((uintptr_t)lse & 3) == 0, "nonlocal_attention_lse: lse is null or misaligned (%p)", (void*)lse);
+    p.lse = lse;
+    return nl_dispatch<true>(ctx, (hipStream_t)s, d, p);
 }
 
 }  // extern "C"

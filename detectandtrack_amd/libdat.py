@@ -110,6 +110,12 @@ class NonLocalDesc(C.Structure):
                 ('ldk', C.c_int), ('ldv', C.c_int), ('ldy', C.c_int), ('scale', C.c_float)]
 
 
+class NonLocalBwdDesc(C.Structure):
+    _fields_ = [('dtype', C.c_int), ('clips', C.c_int), ('Lq', C.c_longlong), ('Lk', C.c_longlong), ('D', C.c_int), ('ldq', C.c_int),
+                ('ldk', C.c_int), ('ldv', C.c_int), ('ldy', C.c_int), ('lddy', C.c_int), ('lddq', C.c_int), ('lddk', C.c_int),
+                ('lddv', C.c_int), ('scale', C.c_float)]
+
+
 if not os.path.exists(LIB_PATH):
     raise ImportError('libdat_hip.so not built at %s — run __graft_entry__.build()' % LIB_PATH)
 _lib = C.CDLL(LIB_PATH)
@@ -236,6 +242,9 @@ _PROTOS = {
     'dat_oks_nms_host': (_i, [C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _d, C.POINTER(_i), C.POINTER(_i), C.POINTER(_d), C.POINTER(_d)]),
     'dat_oks_nms': (_i, [_p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p]),
     'dat_nonlocal_attention': (_i, [_p, _p, C.POINTER(NonLocalDesc), _p, _p, _p, _p]),
+    'dat_nonlocal_attention_lse': (_i, [_p, _p, C.POINTER(NonLocalDesc), _p, _p, _p, _p, _p]),
+    'dat_nonlocal_attention_bwd': (_i, [_p, _p, C.POINTER(NonLocalBwdDesc), _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'dat_maxpool_hw_bwd': (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i]),
 }
 EXPORTS = sorted(_PROTOS)
 for _name, (_res, _args) in _PROTOS.items():

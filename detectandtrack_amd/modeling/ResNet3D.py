@@ -7,7 +7,7 @@ kT = 1 in conv1/res2, never a temporal stride (reference ResNet3D.py:258-284; SU
 (ResNet-(2+1)D, Tran et al., CVPR 2018; no reference code) factorise every kT x 3 x 3 conv of res3..res5 into a 1 x 3 x 3 conv,
 affine, ReLU and a kT x 1 x 1 conv, affine; blob names of block outputs, stage outputs and FPN taps stay those of the I3D body.
 Blocks of res3 / res4 named in HIP.NONLOCAL are followed by a spacetime non-local block (add_nonlocal_block; Wang et al., CVPR 2018; no
-reference code; inference only); stage output names stay what FPN and the heads look up.
+reference code; training opt-in with HIP.TRAIN_NONLOCAL); stage output names stay what FPN and the heads look up.
 """
 from detectandtrack_amd.core.config import cfg
 from detectandtrack_amd.modeling.common import ConvStageInfo
@@ -154,7 +154,7 @@ def nonlocal_blocks_of_stage(prefix, n, dim):
 
 
 def add_nonlocal_block(model, blob_in, dim, nl, blob_out):
-    """Spacetime non-local block, embedded-Gaussian form (Wang et al., CVPR 2018; inference only): theta / phi / g
+    """Spacetime non-local block, embedded-Gaussian form (Wang et al., CVPR 2018; training opt-in): theta / phi / g
     1x1x1 convs to D = dim / 2 channels, phi and g max-pooled 2 x 2 in space (HIP.NONLOCAL_MAXPOOL), y = softmax(scale theta phi^T) g over
     every position of the CLIP in one fused launch, then `<nl>_out` (D -> dim, no bias) + `<nl>_out_bn` + blob_in with no ReLU -- one conv
     launch with the residual in its epilogue.  `_out_bn_s` starts at zero: a checkpoint without the block's blobs gives the base network."""
@@ -168,7 +168,10 @@ def add_nonlocal_block(model, blob_in, dim, nl, blob_out):
         g = model.MaxPool(g, nl + '_g_pool', kernels=[1, 2, 2], pads=zero, strides=[1, 2, 2])
     y = model.NonLocalAttention([theta, phi, g], nl + '_y', dim=D, scale=D ** -0.5 if cfg.HIP.NONLOCAL_SCALE else 1.)
     z = model.ConvNd(y, nl + '_out', D, dim, one, strides=one, pads=zero, no_bias=1)
-    z = model.AffineChannelNd(z, nl + '_out_bn', dim_out=dim, scale_init=('ConstantFill', {'value': 0.}))
+    # a training graph (HIP.TRAIN_NONLOCAL) keeps the affine unfused so that its zero-initialised scale receives a gradient; under
+    # MODEL.USE_BN / HIP.USE_GN the closing op is a trainable SpatialBN / GroupNorm already
+    z = model.AffineChannelNd(z, nl + '_out_bn', dim_out=dim, scale_init=('ConstantFill', {'value': 0.}),
+                              **({'trainable': True} if (model.train and cfg.HIP.get('TRAIN_NONLOCAL', False)) else {}))
     return model.net.Sum([z, blob_in], blob_out)
 
 

@@ -107,7 +107,8 @@ class Net(object):
         return self.producer(str(blob)) is not None
 
 
-_NORM_OPS = ('SpatialBN', 'GroupNorm')      # normalisation ops behind an unfused conv: Sum (same shape) and Relu fold into them
+# normalisation ops behind an unfused conv: Sum (same shape) and Relu fold into them ('AffineTrain': the trainable affine of a non-local block)
+_NORM_OPS = ('SpatialBN', 'GroupNorm', 'AffineTrain')
 
 
 def gn_groups(channels, max_groups):
@@ -210,9 +211,11 @@ class DetectionModelHelper(object):
             return self.ConvNd(blob_in, blob_out, dim_in, dim_out, kernel, weight=weight, bias=bias, **kwargs)
         return self.Conv(blob_in, blob_out, dim_in, dim_out, kernel, weight=weight, bias=bias, **kwargs)
 
-    def AffineChannelNd(self, blob_in, blob_out, dim_out, share_with=None, inplace=False, scale_init=None):
+    def AffineChannelNd(self, blob_in, blob_out, dim_out, share_with=None, inplace=False, scale_init=None, trainable=False):
         """detector.py:89-108.  Folded into the producing conv's epilogue when possible.  scale_init: init spec of `_s` in place of the
-        constant 1 (the zero-initialised last scale of a non-local block)."""
+        constant 1 (the zero-initialised last scale of a non-local block).  trainable (training graphs of a non-local block under
+        HIP.TRAIN_NONLOCAL): the affine is recorded as an `AffineTrain` op behind the unfused conv, and `_s` / `_b` receive gradients --
+        the reference's AffineChannel has none, so nothing else asks for it."""
         if cfg.HIP.USE_GN and cfg.MODEL.USE_BN:
             raise ValueError('HIP.USE_GN and MODEL.USE_BN both replace every AffineChannel[Nd]: set one of them')
         if cfg.MODEL.USE_BN:
@@ -223,6 +226,9 @@ class DetectionModelHelper(object):
         prefix = str(blob_out) if share_with is None else share_with
         s = self._param(prefix + '_s', [dim_out], scale_init or ('ConstantFill', {'value': 1.}), 'w')
         b = self._param(prefix + '_b', [dim_out], ('ConstantFill', {'value': 0.}), 'b')
+        if trainable:
+            assert share_with is None and not inplace, 'a trainable affine keeps its input for the backward and owns its parameters'
+            return self.net.add(Op('AffineTrain', [blob_in], [str(blob_out)], scale=s, bias=b, relu=False, residual=None))
         self.param_specs[s]['affine'] = self.param_specs[b]['affine'] = True
         return self._record_affine(blob_in, blob_in if inplace else str(blob_out), s, b)
 
@@ -314,7 +320,8 @@ class DetectionModelHelper(object):
 
     def NonLocalAttention(self, blobs_in, blob_out, dim, scale):
         """y = softmax(scale * theta phi^T) g over all positions of a clip (blobs_in = [theta, phi, g], `dim` channels each): one fused
-        launch that never writes the scores (csrc/nonlocal.hip).  Inference only."""
+        launch that never writes the scores (csrc/nonlocal.hip).  A training executor runs the form that also
+        stores the row statistic and differentiates it with csrc/nonlocal_bwd.hip (HIP.TRAIN_NONLOCAL)."""
         assert len(blobs_in) == 3, blobs_in
         return self.net.add(Op('NonLocalAttention', [str(b) for b in blobs_in], [str(blob_out)], dim=int(dim), scale=float(scale)))
 

@@ -49,9 +49,10 @@ def create(model_name, train=False, init_params=None):
         raise NotImplementedError('training a grouped (ResNeXt, RESNETS.NUM_GROUPS = %d) body needs the grouped data-gradient and '
                                   'weight-gradient kernels, which are opt-in until they have been measured at full size: set '
                                   'cfg.HIP.TRAIN_GROUPED_CONV = True' % cfg.RESNETS.NUM_GROUPS)
-    if train and cfg.HIP.get('NONLOCAL', ''):
+    if train and cfg.HIP.get('NONLOCAL', '') and not cfg.HIP.get('TRAIN_NONLOCAL', False):
         raise NotImplementedError('training with non-local blocks (HIP.NONLOCAL = %r) needs the backward of the fused attention and of its '
-                                  '2 x 2 max-pool, which do not exist yet: the blocks are inference only' % (cfg.HIP.NONLOCAL,))
+                                  '2 x 2 max-pool, which are opt-in until they have been measured at full size: set '
+                                  'cfg.HIP.TRAIN_NONLOCAL = True' % (cfg.HIP.NONLOCAL,))
     return get_func(model_name)(init_model(model_name, train, init_params))
 
 

@@ -1413,6 +1413,65 @@ def nonlocal_attention(q, k, v, dtype, clips, D, scale, out=None):
     return out
 
 
+def nonlocal_attention_lse(q, k, v, dtype, clips, D, scale, out=None):
+    """dat_nonlocal_attention_lse: nonlocal_attention (bit-identical y) that also returns the fp32 row statistic lse [clips * Lq] =
+    m_i + log2(l_i) in the units of scale * log2(e) * score -- what nonlocal_attention_bwd recomputes P from.  -> (y, lse)."""
+    clips, D = int(clips), int(D)
+    for t in (q, k, v):
+        assert t.dim() == 2 and t.stride(1) == 1 and t.shape[1] >= D and t.dtype == tdtype(dtype), (tuple(t.shape), t.stride(), t.dtype, D)
+    assert clips >= 1 and q.shape[0] % clips == 0 and k.shape[0] % clips == 0 and k.shape[0] == v.shape[0], (q.shape, k.shape, v.shape, clips)
+    if out is None:
+        out = torch.empty((q.shape[0], D), dtype=q.dtype, device=q.device)
+    assert out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == q.shape[0] and out.shape[1] >= D and out.dtype == q.dtype
+    lse = torch.empty(q.shape[0], dtype=torch.float32, device=q.device)
+    d = L.NonLocalDesc()
+    d.dtype, d.clips, d.D, d.scale = dtype, clips, D, float(scale)
+    d.Lq, d.Lk = int(q.shape[0]) // clips, int(k.shape[0]) // clips
+    d.ldq, d.ldk, d.ldv, d.ldy = int(q.stride(0)), int(k.stride(0)), int(v.stride(0)), int(out.stride(0))
+    ctx().call('dat_nonlocal_attention_lse', _stream(), C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse))
+    return out, lse
+
+
+def nonlocal_attention_bwd(q, k, v, y, dy, lse, dtype, clips, D, scale, dq=None, dk=None, dv=None):
+    """dat_nonlocal_attention_bwd: -> (dq [clips * Lq, D], dk, dv [clips * Lk, D]) of y = softmax(scale q k^T) v
+    for the upstream gradient dy, recomputing P from q, k and the forward's lse.  Operands and outputs may be channel-range / row-range
+    views (unit channel stride, any row stride); given outputs get their first D channels filled and nothing else touched.  With one
+    clip, q / y / dy / lse may be the rows of a frame window: dq then covers that window, dk and dv all keys."""
+    clips, D = int(clips), int(D)
+    for t in (q, k, v, y, dy):
+        assert t.dim() == 2 and t.stride(1) == 1 and t.shape[1] >= D and t.dtype == tdtype(dtype), (tuple(t.shape), t.stride(), t.dtype, D)
+    assert clips >= 1 and q.shape[0] % clips == 0 and k.shape[0] % clips == 0 and k.shape[0] == v.shape[0], (q.shape, k.shape, v.shape, clips)
+    assert y.shape[0] == q.shape[0] and dy.shape[0] == q.shape[0], (q.shape, y.shape, dy.shape)
+    assert lse.dtype == torch.float32 and lse.dim() == 1 and lse.shape[0] == q.shape[0] and lse.is_contiguous(), (lse.shape, lse.dtype)
+    outs = []
+    for o, like in ((dq, q), (dk, k), (dv, v)):
+        if o is None:
+            o = torch.empty((like.shape[0], D), dtype=q.dtype, device=q.device)
+        assert o.dim() == 2 and o.stride(1) == 1 and o.shape[0] == like.shape[0] and o.shape[1] >= D and o.dtype == q.dtype
+        outs.append(o)
+    dq, dk, dv = outs
+    delta = torch.empty(q.shape[0], dtype=torch.float32, device=q.device)
+    d = L.NonLocalBwdDesc()
+    d.dtype, d.clips, d.D, d.scale = dtype, clips, D, float(scale)
+    d.Lq, d.Lk = int(q.shape[0]) // clips, int(k.shape[0]) // clips
+    d.ldq, d.ldk, d.ldv, d.ldy = int(q.stride(0)), int(k.stride(0)), int(v.stride(0)), int(y.stride(0))
+    d.lddy, d.lddq, d.lddk, d.lddv = int(dy.stride(0)), int(dq.stride(0)), int(dk.stride(0)), int(dv.stride(0))
+    ctx().call('dat_nonlocal_attention_bwd', _stream(), C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(y), _ptr(dy), _ptr(lse), _ptr(delta),
+               _ptr(dq), _ptr(dk), _ptr(dv))
+    return dq, dk, dv
+
+
+def maxpool_hw_bwd(x, dy, dtype, k, stride, pad):
+    """dat_maxpool_hw_bwd: the gradient of maxpool_hw for non-overlapping windows (k <= stride).  x [f, h, w, c] the pool's input, dy
+    [f, ho, wo, c]; -> dx like x, written whole (the first maximum in scan order takes the window's gradient, everything else is 0)."""
+    f, h, w, c = x.shape
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    assert tuple(dy.shape) == (f, ho, wo, c) and x.is_contiguous() and dy.is_contiguous() and dy.dtype == x.dtype, (x.shape, dy.shape)
+    dx = torch.empty_like(x)
+    ctx().call('dat_maxpool_hw_bwd', _stream(), dtype, _ptr(x), _ptr(dy), _ptr(dx), f, h, w, c, k, stride, pad)
+    return dx
+
+
 OKS_NMS_MAX_ROWS = 1024      # DAT_OKS_NMS_MAX_ROWS: an image's score keys, visiting order and alive flags stay in LDS
 
 

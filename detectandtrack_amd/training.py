@@ -804,16 +804,78 @@ class TrainExecutor(Executor):
         self._add_grad(op.inputs[0], g)
 
     def bwd_MaxPool(self, i, op):
-        """Only the P6 'sub-sampling' pool (kernel 1, stride 2; FPN3D.py:155-164) sits above the frozen trunk."""
+        """Above the frozen trunk sit the P6 'sub-sampling' pool (kernel 1, stride 2; FPN3D.py:155-164) and the 2 x 2 / stride 2 pools of
+        the non-local blocks' phi and g branches (dat_maxpool_hw_bwd: non-overlapping windows).  Pools are per frame: a frame window of
+        the gradient stays that window."""
         a = op.args
         x = self.ws.blobs[op.inputs[0]]
         dy, lo = self._take_grad(op.outputs[0], x.dt)
         if dy is None:
             return
-        assert a['k'] == 1 and a['stride'] == 2 and a['pad'] == 0, 'max-pool backward above the frozen trunk: P6 only'
-        g = torch.zeros((dy.shape[0],) + tuple(x.t.shape[1:]), dtype=x.t.dtype, device=x.t.device)
-        g[:, ::2, ::2] = dy
-        self._add_grad(op.inputs[0], g, lo)
+        if a['k'] == 1 and a['stride'] == 2 and a['pad'] == 0:
+            g = torch.zeros((dy.shape[0],) + tuple(x.t.shape[1:]), dtype=x.t.dtype, device=x.t.device)
+            g[:, ::2, ::2] = dy
+            self._add_grad(op.inputs[0], g, lo)
+            return
+        assert a['k'] <= a['stride'], 'max-pool backward above the frozen trunk: non-overlapping windows only (kernel %d, stride %d)' % (
+            a['k'], a['stride'])
+        n = dy.shape[0]
+        assert (lo == 0 and n == x.t.shape[0]) or x.N == 1, 'frame-window gradients assume one clip per forward'
+        self._add_grad(op.inputs[0], ops.maxpool_hw_bwd(x.t[lo:lo + n], dy if dy.is_contiguous() else dy.contiguous(), x.dt, a['k'],
+                                                        a['stride'], a['pad']), lo)
+
+    def bwd_NonLocalAttention(self, i, op):
+        """dq, dk, dv of the fused attention (ops.nonlocal_attention_bwd: P recomputed from the stored row statistic).  With one clip a
+        frame window of dy is a contiguous row range of q, y, lse and dy: dq covers that window, dk and dv every frame (all keys of the
+        clip hear from the window's queries)."""
+        ws, a = self.ws, op.args
+        y = ws.blobs[op.outputs[0]]
+        dy, lo = self._take_grad(op.outputs[0], y.dt)
+        if dy is None:
+            return
+        q, k, v = (ws.blobs[n] for n in op.inputs)
+        n, D = dy.shape[0], a['dim']
+        assert (lo == 0 and n == y.t.shape[0]) or q.N == 1, 'frame-window gradients assume one clip per forward (TRAIN.IMS_PER_BATCH 1)'
+        assert y.lse is not None, 'the forward of %r did not keep its row statistic (not a training executor)' % (op.outputs[0],)
+        assert all(t.shape[3] == D for t in (q.t, k.t, v.t, y.t, dy)), (D, [tuple(t.shape) for t in (q.t, k.t, v.t, y.t, dy)])
+        per = q.t.shape[1] * q.t.shape[2]
+        rows = lambda t: t.reshape(-1, D)
+        dq, dk, dv = ops.nonlocal_attention_bwd(rows(q.t[lo:lo + n]), rows(k.t), rows(v.t), rows(y.t[lo:lo + n]),
+                                                rows(dy if dy.is_contiguous() else dy.contiguous()), y.lse[lo * per:(lo + n) * per], q.dt,
+                                                q.N, D, a['scale'])
+        for name, x, g, l in ((op.inputs[0], q, dq, lo), (op.inputs[1], k, dk, 0), (op.inputs[2], v, dv, 0)):
+            if name not in self.no_grad:
+                self._add_grad(name, g.view((-1,) + tuple(x.t.shape[1:])), l)
+
+    def bwd_AffineTrain(self, i, op):
+        """The trainable closing affine of a non-local block, y = z * s + b (+ residual): g = dy (also the residual's gradient),
+        db = sum g and ds = sum g * z through the SpatialBN reduction with mean 0 and rstd 1 -- straight into the arena views -- and
+        dz = s * g through its normalise pass with b' = 0.  Per position: a frame window stays that window."""
+        ws, a = self.ws, op.args
+        out = op.outputs[0]
+        y = ws.blobs[out]
+        dy, lo = self._take_grad(out, y.dt)
+        assert not self._last_masked, 'a ReLU-masked gradient reached an AffineTrain (the mask fusions of bwd_Conv are for Conv producers)'
+        if dy is None:
+            return
+        z, s_tab = y.bn
+        assert (lo == 0 and dy.shape[0] == z.shape[0]) or y.N == 1, 'frame-window gradients assume one clip per forward'
+        cs = z.shape[3]
+        dev = {}
+        for key in ('bias', 'scale'):
+            name = a[key]
+            if self._trainable(name):       # the kernel ACCUMULATES: straight into the (zeroed) arena view when there is one
+                dev[key] = self.arena[name] if (self.arena is not None and name in self.arena) else \
+                    torch.zeros(y.C, dtype=torch.float32, device=ws.device)
+        zero, one = torch.zeros(cs, dtype=torch.float32, device=ws.device), torch.ones(cs, dtype=torch.float32, device=ws.device)
+        g, _ = ops.bn_bwd_reduce(dy if dy.is_contiguous() else dy.contiguous(), y.t, z, y.dt, y.C, zero, one, frame_lo=lo,
+                                 relu=bool(a['relu']), dbeta=dev.get('bias'), dgamma=dev.get('scale'))
+        for key, t in dev.items():
+            self._pgrad(a[key], t)
+        if a['residual']:
+            self._add_grad(a['residual'], g, lo)
+        if op.inputs[0] not in self.no_grad:
+            self._add_grad(op.inputs[0], ops.bn_apply(g, y.dt, y.C, s_tab, zero), lo)
 
     # ---- update ---------------------------------------------------------------------------------------------------------------
     def loss_values(self):
@@ -840,7 +902,7 @@ def no_grad_blobs(net):
     return ng
 
 
-_PARAM_KEYS = {'SpatialBN': ('scale', 'bias'), 'GroupNorm': ('scale', 'bias')}     # op type -> the args that name its trainable parameters (default: w, b)
+_PARAM_KEYS = {'SpatialBN': ('scale', 'bias'), 'GroupNorm': ('scale', 'bias'), 'AffineTrain': ('scale', 'bias')}     # op type -> the args that name its trainable parameters (default: w, b)
 
 
 def param_ready_index(net, fused=None):

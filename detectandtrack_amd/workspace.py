@@ -22,7 +22,7 @@ logger = logging.getLogger(__name__)
 class Blob(object):
     """A device blob.  kind: 'fmap' [N*T,H,W,Cs] | 'rows' [1,1,R,Cs] (FC activations) | 'mat' fp32 tensor |
     'rois' fp32 [cap, cols] + device count."""
-    __slots__ = ('t', 'kind', 'N', 'T', 'C', 'dt', 'five_d', 'count', 'sigmoid_of', 'host', 'keyframe', 't2c', 'split', 'tsel', 'bn', 'roi')
+    __slots__ = ('t', 'kind', 'N', 'T', 'C', 'dt', 'five_d', 'count', 'sigmoid_of', 'host', 'keyframe', 't2c', 'split', 'tsel', 'bn', 'roi', 'lse')
 
     def __init__(self, t, kind, N=1, T=1, C=0, dt=0, five_d=False, count=None):
         self.t, self.kind, self.N, self.T, self.C, self.dt = t, kind, N, T, C, dt
@@ -38,7 +38,9 @@ class Blob(object):
         self.t2c = False        # time moved into channels (detector.py:480-491): still stored as T frames of C channels
         self.keyframe = None    # set when only this frame of a T-frame blob was computed (cfg.HIP.KEYFRAME_DCE)
         self.bn = None          # output of a training-mode SpatialBN: (its input tensor z, fp32 [4, cs] = mean, rstd, a, b') for the backward;
-                                # of a GroupNorm: (z, fp32 [4, clips, cs]); of a GroupNorm over a per-RoI blob: (z, (mean, rstd) fp32 [R, groups])
+                                # of a GroupNorm: (z, fp32 [4, clips, cs]); of a GroupNorm over a per-RoI blob: (z, (mean, rstd) fp32 [R, groups]);
+                                # of an AffineTrain: (z, the scale table fp32 [cs])
+        self.lse = None         # output of a training-mode NonLocalAttention: the fp32 row statistic [N * T * H * W] of its softmax
 
 
 class Workspace(object):
@@ -214,6 +216,15 @@ def _unscoped(name):
 
 def _count(b):
     return int(b.count.item()) if isinstance(b.count, torch.Tensor) else int(b.count)
+
+
+def _pad_table(t, cs):
+    """A per-channel fp32 table [C] as the normalisation kernels read it: [cs] with zeros in the padding channels (itself when C == cs)."""
+    if t.numel() == cs:
+        return t
+    out = torch.zeros(cs, dtype=torch.float32, device=t.device)
+    out[:t.numel()] = t
+    return out
 
 
 def _valid_rows(b, arr):
@@ -742,8 +753,27 @@ class Executor(object):
             assert x.C == a['dim'] and x.N == q.N and x.T == q.T and x.dt == q.dt and x.t.shape[0] == x.N * x.T, (op, x.C, x.N, x.T)
         assert k.t.shape[:3] == v.t.shape[:3], (op, tuple(k.t.shape), tuple(v.t.shape))
         rows = lambda x: x.t.view(-1, x.t.shape[3])
-        y = ops.nonlocal_attention(rows(q), rows(k), rows(v), q.dt, q.N, a['dim'], a['scale'])
-        ws.blobs[op.outputs[0]] = Blob(y.view(tuple(q.t.shape[:3]) + (a['dim'],)), 'fmap', q.N, q.T, a['dim'], q.dt, q.five_d)
+        lse = None
+        if self.training:       # the same kernel (bit-identical y), which also stores the row statistic the backward recomputes P from
+            y, lse = ops.nonlocal_attention_lse(rows(q), rows(k), rows(v), q.dt, q.N, a['dim'], a['scale'])
+        else:
+            y = ops.nonlocal_attention(rows(q), rows(k), rows(v), q.dt, q.N, a['dim'], a['scale'])
+        b = Blob(y.view(tuple(q.t.shape[:3]) + (a['dim'],)), 'fmap', q.N, q.T, a['dim'], q.dt, q.five_d)
+        b.lse = lse
+        ws.blobs[op.outputs[0]] = b
+
+    def op_AffineTrain(self, i, op):
+        """The trainable closing affine of a non-local block (training graphs under HIP.TRAIN_NONLOCAL): y = z * s + b (+ residual) through
+        the SpatialBN normalise pass with a = s, b' = b.  The output keeps z for the backward."""
+        ws, a = self.ws, op.args
+        x = ws.blobs[op.inputs[0]]
+        assert x.kind == 'fmap' and x.keyframe is None and not x.t2c and x.count is None, (op, x.kind)
+        res = ws.blobs[a['residual']].t if a['residual'] else None
+        s, sh = _pad_table(ws.dev_param(a['scale']), x.t.shape[3]), _pad_table(ws.dev_param(a['bias']), x.t.shape[3])
+        y = ops.bn_apply(x.t, x.dt, x.C, s, sh, relu=a['relu'], residual=res)
+        b = Blob(y, 'fmap', x.N, x.T, x.C, x.dt, x.five_d)
+        b.bn = (x.t, s)
+        ws.blobs[op.outputs[0]] = b
 
     def op_MaxPool(self, i, op):
         x = self.ws.blobs[op.inputs[0]]

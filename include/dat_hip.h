@@ -838,6 +838,37 @@ typedef struct {
     float scale;
 } dat_nonlocal_desc;
 int dat_nonlocal_attention(dat_ctx* ctx, dat_stream s, const dat_nonlocal_desc* d, const void* q, const void* k, const void* v, void* y);
+/* The training forward: the same kernel (y is bit-identical), which also stores the row statistic lse[clip * Lq + i] = m_i + log2(l_i)
+ * (fp32, in the units of scale * log2(e) * score; m_i the row maximum, l_i the denominator) for clips * Lq rows. */
+int dat_nonlocal_attention_lse(dat_ctx* ctx, dat_stream s, const dat_nonlocal_desc* d, const void* q, const void* k, const void* v, void* y,
+                               float* lse);
+
+/* Backward of the fused attention (HIP.TRAIN_NONLOCAL).  With p_ij = exp2(c s_ij - lse_i), c = scale * log2(e),
+ * delta_i = sum_d dy_id y_id, dP_ij = sum_d dy_id v_jd and dS_ij = p_ij (dP_ij - delta_i):
+ *   dv_jd = sum_i p_ij dy_id,   dq_id = scale sum_j dS_ij k_jd,   dk_jd = scale sum_i dS_ij q_id.
+ * P is recomputed from q, k and lse (the scores are never written).  Three launches (delta; dq, query-stationary; dk and dv,
+ * key-stationary): nothing is summed across workgroups, so there are no atomics, no workspace beyond `delta`, no host synchronisation; the
+ * result is bitwise reproducible and does not depend on `clips`.  Every output is written whole (rows [0, Lq) / [0, Lk) of every clip,
+ * channels [0, D)); padding channels are not touched.  With one clip a frame window of the queries is the same call on offset q / y / dy /
+ * lse / dq pointers with Lq = the window's rows. */
+typedef struct {
+    int dtype;               /* DAT_F32 | DAT_BF16 (the build's 16-bit format) */
+    int clips;
+    long long Lq, Lk;        /* query / key rows per clip, >= 1 */
+    int D;                   /* channels: 64 | 128 | 256 | 512 */
+    int ldq, ldk, ldv, ldy;  /* row strides in elements of q, k, v, y: >= D, multiples of 8; pointers 16-byte aligned */
+    int lddy, lddq, lddk, lddv;  /* row strides of dy, dq, dk, dv: the same rules */
+    float scale;
+} dat_nonlocal_bwd_desc;
+/* lse: what dat_nonlocal_attention_lse stored; delta: clips * Lq floats the call fills (sum_d dy y in fp32) and then reads. */
+int dat_nonlocal_attention_bwd(dat_ctx* ctx, dat_stream s, const dat_nonlocal_bwd_desc* d, const void* q, const void* k, const void* v,
+                               const void* y, const void* dy, const float* lse, float* delta, void* dq, void* dk, void* dv);
+
+/* Backward of dat_maxpool_hw for NON-OVERLAPPING windows (1 <= k <= stride, 0 <= pad < k): dx [frames, H, W, C] is written whole -- the
+ * window's gradient at the FIRST maximum in (h, w) scan order (torch's max_pool2d on the host), zero everywhere else, rows and columns
+ * outside any window included.  No atomics: every input element belongs to at most one window.  C: a multiple of 8. */
+int dat_maxpool_hw_bwd(dat_ctx* ctx, dat_stream s, int dtype, const void* x, const void* dy, void* dx, int frames, int H, int W, int C, int k,
+                       int stride, int pad);
 
 #ifdef __cplusplus
 }
