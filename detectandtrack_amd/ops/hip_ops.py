@@ -424,14 +424,32 @@ class ConvGrad(object):
             d.dil_h = d.dil_w = self.dilation
         return d
 
+    def _wgrad_desc(self, frames, T, H, W, g_frames):
+        """The forward descriptor with the gradient's frame window: g is zero outside frames [t0, t0 + n) of the (single) clip."""
+        d = self._fwd_desc(frames, T, H, W)
+        if g_frames is not None and frames == T:
+            d.out_t0, d.out_tn = int(g_frames[0]), int(g_frames[1])
+        return d
+
+    def _acc_supported(self, d):
+        return bool(L.lib().dat_conv3d_wgrad_acc_supported(ctx().h, C.byref(d), self.g_cstride))
+
+    def takes_acc(self, frames, T, H, W, g_frames=None):
+        """Does `weight_acc` take this layer at that input shape (dat_conv3d_wgrad_acc_supported: answered on the host, nothing is
+        launched)?  Grouped layers always do."""
+        return self.groups > 1 or self._acc_supported(self._wgrad_desc(frames, T, H, W, g_frames))
+
+    def repack(self):
+        """after an in-place update of the forward master: refresh the packed data-gradient weights (if they were built)"""
+        if self._data_layer is not None:
+            self._data_layer.repack()
+
     def plan(self, frames, T, H, W, g_frames=None, acc=False, num_cu=0):
         """The launch plan the current context gives `weight` (acc: `weight_acc`) at that input shape (dat_conv3d_wgrad_plan: kernel
         family, variant, tile, K split, atomics, memset / finish launches, grid ...) as a dict; g_frames as for `weight`.  num_cu 0 = the
         device's CU count.  The grouped weight gradient has its own rule."""
         assert self.groups == 1, 'dat_conv3d_wgrad_plan describes the dense weight-gradient launches'
-        d, out = self._fwd_desc(frames, T, H, W), L.WgradPlan()
-        if g_frames is not None and frames == T:
-            d.out_t0, d.out_tn = int(g_frames[0]), int(g_frames[1])
+        d, out = self._wgrad_desc(frames, T, H, W, g_frames), L.WgradPlan()
         ctx().call('dat_conv3d_wgrad_plan', C.byref(d), self.g_cstride, self.cin, self.cout, int(acc), int(num_cu), C.byref(out))
         return out.as_dict()
 
@@ -439,9 +457,7 @@ class ConvGrad(object):
         """x [frames,H,W,x_cstride], g [frames,Ho,Wo,g_cstride] -> (dW fp32 [Cout,Cin,KT,KH,KW] (already x scale),
         dscale fp32 [Cout] | None); out: a contiguous fp32 tensor of the weight's shape to write dW into (gradient arena)"""
         frames, H, W, _ = x.shape
-        d = self._fwd_desc(frames, T, H, W)
-        if g_frames is not None and frames == T:      # g is zero outside frames [t0, t0 + n) of the (single) clip
-            d.out_t0, d.out_tn = int(g_frames[0]), int(g_frames[1])
+        d = self._wgrad_desc(frames, T, H, W, g_frames)
         if self.groups > 1:
             nbytes = L.lib().dat_conv3d_grouped_wgrad_workspace_bytes(C.byref(d), self.groups)
         else:
@@ -469,15 +485,13 @@ class ConvGrad(object):
         WeightFinishBatch turns all accumulators into gradients with one launch.  Returns False -- nothing launched -- when the layer
         does not take the direct kernels (the caller then uses `weight`)."""
         frames, H, W, _ = x.shape
-        d = self._fwd_desc(frames, T, H, W)
-        if g_frames is not None and frames == T:
-            d.out_t0, d.out_tn = int(g_frames[0]), int(g_frames[1])
+        d = self._wgrad_desc(frames, T, H, W, g_frames)
         if self.groups > 1:       # Gt[tap][C][C / groups]: the elements outside the diagonal blocks do not exist
             assert gt.dtype == torch.float32 and gt.is_contiguous() and gt.numel() == self.w.numel()
             assert x.is_contiguous() and g.is_contiguous()
             ctx().call('dat_conv3d_grouped_wgrad_acc', _stream(), C.byref(d), self.groups, _ptr(x), _ptr(g), self.g_cstride, _ptr(gt))
             return True
-        if not L.lib().dat_conv3d_wgrad_acc_supported(ctx().h, C.byref(d), self.g_cstride):
+        if not self._acc_supported(d):
             return False
         assert gt.dtype == torch.float32 and gt.is_contiguous() and gt.numel() == self.w.numel()
         ctx().call('dat_conv3d_wgrad_acc', _stream(), C.byref(d), _ptr(x), _ptr(g), self.g_cstride, self.cin, self.cout, _ptr(gt))
@@ -489,10 +503,8 @@ class ConvGrad(object):
         if self.groups > 1:         # grouped layers are never queued into the pointwise batch
             return None
         frames, H, W, _ = x.shape
-        d = self._fwd_desc(frames, T, H, W)
-        if g_frames is not None and frames == T:
-            d.out_t0, d.out_tn = int(g_frames[0]), int(g_frames[1])
-        if not L.lib().dat_conv3d_wgrad_acc_supported(ctx().h, C.byref(d), self.g_cstride):
+        d = self._wgrad_desc(frames, T, H, W, g_frames)
+        if not self._acc_supported(d):
             return None
         assert gt.dtype == torch.float32 and gt.is_contiguous() and gt.numel() == self.w.numel()
         assert x.is_contiguous() and g.is_contiguous()
@@ -714,15 +726,6 @@ class WeightFinishBatch(object):
 
     def run(self):
         ctx().call('dat_wgrad_finish_batch', _stream(), _ptr(self.table), self.n, C.c_longlong(self.total))
-
-
-def _convgrad_repack(self):
-    """after an in-place update of the forward master: refresh the packed data-gradient weights (if they were built)"""
-    if self._data_layer is not None:
-        self._data_layer.repack()
-
-
-ConvGrad.repack = _convgrad_repack
 
 
 def relu_bias_bwd(dy, y, dtype, C_real, relu=True, dy2=None, dbias=None):

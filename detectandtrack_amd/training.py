@@ -22,6 +22,7 @@ import torch
 
 from detectandtrack_amd.core.config import cfg
 from detectandtrack_amd.ops import hip_ops as ops
+from detectandtrack_amd.train_plan import ConvBwdFacts, GradLedger, check_one_clip, plan_conv_bwd, sealed_error
 from detectandtrack_amd.utils import lr_policy
 from detectandtrack_amd.workspace import Executor, _count
 
@@ -34,7 +35,7 @@ class TrainExecutor(Executor):
 
     def __init__(self, ws, net, arena=None, gt_arena=None):
         super(TrainExecutor, self).__init__(ws, net)
-        self.grads = {}          # blob name -> list of gradient tensors (blob layout; activation dtype or fp32)
+        self.ledger = GradLedger()   # the gradient contributions that wait for each blob (blob layout; activation dtype or fp32)
         self.param_grads = {}    # param name -> fp32 CUDA tensor (reference blob layout)
         # Trainer's gradient arena: param name -> a zeroed fp32 view of ONE flat buffer (the all-reduce and the SGD update run on
         # the flat buffer; weight-gradient kernels write into the views directly).  None: gradients are separate tensors.
@@ -50,8 +51,6 @@ class TrainExecutor(Executor):
         self._sealed = set()     # parameters whose gradient bucket is already on its way to the other ranks (Trainer, overlap)
         self.accumulate_all = False   # the arena already holds gradients of an earlier clip (Trainer.step(zero_grad=False)): add, never overwrite
         self._iter_cache = {}           # per backward pass: objects several ops build from the same weights (see backward)
-        self._last_masked = False       # set by _take_grad: the gradient just taken already carries its producer's ReLU mask
-        self._ncontrib = {}             # blob name -> gradient contributions received so far (entries of self.grads may be sums of several)
         self._trainable_set = None
         self._readers = {}
         for o in net.ops:
@@ -60,7 +59,6 @@ class TrainExecutor(Executor):
                 self._readers[b] = self._readers.get(b, 0) + 1
         self.losses = {}         # loss blob name -> fp32 CUDA scalar tensor
         self.metrics = {}
-        self._cg = {}
         # blobs at or below the StopGradient marker (frozen trunk): no gradient is computed for them or their producers
         self.no_grad = no_grad_blobs(net)
 
@@ -115,7 +113,7 @@ class TrainExecutor(Executor):
         loss2 = self._loss_buf(op.outputs)
         dhead = ops.rpn_loss(head.t, head.dt, A, 0, A, labels.t, tgt.t, w_in.t, w_out.t, cls_mult, a['beta'],
                              a['bbox_scale'] / n_batch, loss2, T=T, per_frame=per_frame)
-        self._add_grad(head_name, dhead)
+        self.ledger.add(head_name, dhead)
 
     def op_SoftmaxLoss(self, i, op):
         ws, a = self.ws, op.args
@@ -126,7 +124,7 @@ class TrainExecutor(Executor):
         correct = self._scalar_pool(1).view(torch.int32)
         d = ops.softmax_ce_rows(x.t, x.dt, x.C, labels.t, None, a['scale'] / max(R, 1), loss, correct)
         self.metrics[op.outputs[2]] = (correct, R)
-        self._add_grad(op.inputs[0], d)
+        self.ledger.add(op.inputs[0], d)
 
     def op_SmoothL1Loss(self, i, op):
         ws, a = self.ws, op.args
@@ -139,7 +137,7 @@ class TrainExecutor(Executor):
         else:
             R = x.t.shape[2]
             d = ops.smooth_l1_rows(x.t, x.dt, x.C, tgt.t, w_in.t, w_out.t, a['beta'], a['scale'] / max(R, 1), loss)
-        self._add_grad(op.inputs[0], d)
+        self.ledger.add(op.inputs[0], d)
 
     def op_KeypointLoss(self, i, op):
         ws, a = self.ws, op.args
@@ -155,7 +153,7 @@ class TrainExecutor(Executor):
         logits = x.t.view(R * K, M * M)
         mult = a['scale'] / norm if norm > 0 else 0.0
         d = ops.softmax_ce_rows(logits, ops.F32, M * M, loc.t.view(-1), wts.t.view(-1), mult, loss)
-        self._add_grad(op.inputs[0], d.view(R, K, M, M))
+        self.ledger.add(op.inputs[0], d.view(R, K, M, M))
 
     def op_CollectAndDistributeFpnRpnProposals(self, i, op):
         if not op.args.get('train'):
@@ -203,55 +201,11 @@ class TrainExecutor(Executor):
                 ws.FeedBlob(name, np.ascontiguousarray(blobs[name]))
 
     # ---- gradient bookkeeping ---------------------------------------------------------------------------------------------
-    # A gradient of a T-frame feature map may cover only a WINDOW of frames [lo, lo + n) (everything else is exactly zero):
-    # with BODY_HEAD_LINK 'slice-center' the heads read one frame, so the FPN post-hoc convs (60 % of the forward FLOPs)
-    # receive a 1-frame gradient and hand a 3-frame gradient down; each kT = 3 conv widens the window by its temporal reach.
-    def _add_grad(self, name, t, lo=0, masked=False):
-        """masked: the ReLU backward of `name`'s producer is already applied to `t` (fused into the data-gradient conv that made it).
-        The flag travels WITH the entry (tensor, first frame, masked) -- not in a side table keyed by id(tensor)."""
-        self.grads.setdefault(name, []).append((t, lo, bool(masked)))
-        self._ncontrib[name] = self._ncontrib.get(name, 0) + 1
-
-    def _take_grad(self, name, dtype):
-        """-> (dy, lo) with dy in the activation dtype covering frames [lo, lo + dy.shape[0]), or (None, 0).  `self._last_masked`
-        says whether the returned gradient already carries the ReLU mask of `name`'s producer (a single, masked contribution)."""
-        lst = self.grads.pop(name, None)
-        self._ncontrib.pop(name, None)
-        self._last_masked = False
-        if not lst:
-            return None, 0
-        tdt = ops.tdtype(dtype)
-        self._last_masked = len(lst) == 1 and lst[0][2]
-        assert not any(m for _, _, m in lst) or len(lst) == 1, 'a masked gradient must be the only contribution to %r' % name
-        lo = min(l for _, l, _ in lst)
-        hi = max(l + t.shape[0] for t, l, _ in lst)
-        if len(lst) == 1:
-            t, l, _ = lst[0]
-            return (t if t.dtype == tdt else t.to(tdt)), l
-        # the sum starts as ONE out-of-place add of two full-window contributions (no clone + add pair).  (Adding the fp32 accumulators of
-        # the RoIAlign backward without the .to() pass -- a mixed-dtype in-place add -- measured slower: ATen's casting kernel is not vectorised.)
-        full = [e for e in lst if e[0].shape[0] == hi - lo and not getattr(e[0], '_roi_acc', False)]
-        first = next((e for e in full if e[0].dtype == tdt), None)
-        acc = None
-        if first is not None:
-            second = next((e for e in full if e is not first and e[0].shape == first[0].shape), None)
-            if second is not None:
-                acc = torch.add(first[0], second[0]) if second[0].dtype == tdt else torch.add(first[0], second[0]).to(tdt)
-                lst = [e for e in lst if e is not first and e is not second]
-            else:
-                acc = first[0].clone()
-                lst = [e for e in lst if e is not first]
-        if acc is None:
-            acc = torch.zeros((hi - lo,) + tuple(lst[0][0].shape[1:]), dtype=tdt, device=lst[0][0].device)
-        for t, l, _ in lst:
-            acc[l - lo:l - lo + t.shape[0]] += t if t.dtype == tdt else t.to(tdt)
-        return acc, lo
-
+    # (contributions to blob gradients wait in self.ledger; parameter gradients go to the arena views or self.param_grads)
     def _pgrad(self, name, t):
         """Add a parameter-gradient contribution `t` (a fresh tensor the caller does not reuse)."""
         if name in self._sealed:
-            raise RuntimeError('gradient contribution to %r after its bucket was handed to the all-reduce (static completion index '
-                               'of the parameter is wrong)' % name)
+            raise sealed_error(name)
         if self.arena is not None and name in self.arena:
             view = self.arena[name]
             if t.data_ptr() != view.data_ptr():      # not produced in place (see _pgrad_out)
@@ -270,6 +224,17 @@ class TrainExecutor(Executor):
         if self.arena is None or name not in self.arena or name in self.param_grads or self.accumulate_all:
             return None
         return self.arena[name]
+
+    def _pgrad_acc(self, name, n):
+        """Where a kernel that ACCUMULATES (a bias or scale reduction) adds the gradient of `name`: straight into the (zeroed) arena view
+        when there is one -- no fill, no add -- else into fresh zeros [n].  The caller hands the result to _pgrad."""
+        if self.arena is not None and name in self.arena:
+            return self.arena[name]
+        return torch.zeros(n, dtype=torch.float32, device=self.ws.device)
+
+    def _norm_pgrads(self, a, C):
+        """{'bias' | 'scale': accumulation target} of the trainable parameters of a norm op."""
+        return {key: self._pgrad_acc(a[key], C) for key in ('bias', 'scale') if self._trainable(a[key])}
 
     def _conv_grad(self, i, build):
         """ConvGrad of op i, cached across iterations in the workspace (the Trainer re-packs it after every update)."""
@@ -302,8 +267,7 @@ class TrainExecutor(Executor):
             if on_op_done is not None:
                 on_op_done(i)
         self._finish_deferred()
-        self.grads.clear()
-        self._ncontrib.clear()
+        self.ledger.clear()
 
     def _flush_pw(self):
         """Run the queued pointwise weight gradients (one grouped launch per tile class) and drop the references that kept their operands alive."""
@@ -337,123 +301,83 @@ class TrainExecutor(Executor):
         self._sealed.update(names)
 
     def bwd_Conv(self, i, op):
-        ws, a = self.ws, op.args
+        """Take the gradient, gather the facts, plan (train_plan.plan_conv_bwd decides everything), launch."""
         if i in self._fused:
             return self._bwd_rpn_head(i)
-        out = op.outputs[0]
-        y = ws.blobs[out]
-        dy, lo = self._take_grad(out, y.dt)
+        ws, a = self.ws, op.args
+        y, xin = ws.blobs[op.outputs[0]], ws.blobs[op.inputs[0]]
+        dy, lo, masked = self.ledger.take(op.outputs[0], y.dt)
         if dy is None:
             return
-        xin = ws.blobs[op.inputs[0]]
-        assert not xin.t2c and y.keyframe is None, 'training with time->channel heads / key-frame DCE is not supported'
-        n = dy.shape[0]
-        full = (lo == 0 and n == y.t.shape[0])
-        assert full or xin.N == 1, 'frame-window gradients assume one clip per forward (TRAIN.IMS_PER_BATCH 1)'
-        cout = a['dim_out']
-        train_b = a['b'] if (a['b'] and self._trainable(a['b'])) else None
-        dbias = None
-        if train_b:     # the kernel ACCUMULATES the bias reduction: straight into the (zeroed) arena view when there is one
-            dbias = self.arena[train_b] if (self.arena is not None and train_b in self.arena) else \
-                torch.zeros(cout, dtype=torch.float32, device=ws.device)
-        # (the mask may already be in dy: the data-gradient conv of this blob's only reader applied it in its epilogue)
-        need_relu = bool(a['relu']) and not self._last_masked
-        if need_relu or dbias is not None:
-            g = ops.relu_bias_bwd(dy, y.t[lo:lo + n], y.dt, cout, relu=need_relu, dbias=dbias)
-        else:
-            g = dy          # no ReLU to mask by, no trainable bias to reduce into (the shortcut convs: AffineChannelNd has no gradient)
-            # g ALIASES dy here (it may also be queued as the residual's gradient below): everything downstream reads whole channel
-            # strides, so the padding channels [cout, stride) must be zero -- they are when dy came out of a conv epilogue or
-            # relu_bias_bwd of a layer with cout == stride; make it so otherwise instead of trusting the producer
-            if cout != dy.shape[3]:
-                dy[..., cout:].zero_()
-        if train_b:
-            self._pgrad(train_b, dbias)
-        if a['residual']:
-            if a['res_mode'] == 2:
-                self._add_grad(a['residual'], ops.upsample2x_bwd(g, y.dt), lo)
-            else:
-                self._add_grad(a['residual'], g, lo)
-        # frames of the input this gradient window reaches through the temporal taps
-        pt = a['pads'][0]
-        T = xin.T if xin.N == 1 else xin.t.shape[0]
-        ilo, ihi = (max(0, lo - pt), min(T, lo + n + pt)) if xin.N == 1 else (0, xin.t.shape[0])
-        x_win = xin.t[ilo:ihi]
-        if (ilo, ihi) != (lo, lo + n):
-            g_emb = torch.zeros((ihi - ilo,) + tuple(g.shape[1:]), dtype=g.dtype, device=g.device)
-            g_emb[lo - ilo:lo - ilo + n] = g
-        else:
-            g_emb = g
-        Tw = (ihi - ilo) if xin.N == 1 else xin.T
+
         def build():
             w5 = self._master(a['w'])
             w5 = w5 if w5.dim() == 5 else w5.unsqueeze(2)
             scale = ws.affine_pair(a)[0]        # (a test-mode SpatialBN: the folded scale)
-            return ops.ConvGrad(w5, scale, a['strides'], a['pads'], y.dt, xin.t.shape[3], g.shape[3], groups=a.get('group', 1),
+            return ops.ConvGrad(w5, scale, a['strides'], a['pads'], y.dt, xin.t.shape[3], dy.shape[3], groups=a.get('group', 1),
                                 dilation=a.get('dilation', 1))
         cg = self._conv_grad(i, build)
-        if self._trainable(a['w']):
-            gfr = (lo - ilo, n) if xin.N == 1 else None
-            gt = self.gt_arena.get(a['w']) if (self.gt_arena is not None and a['w'] in self.arena) else None
-            if a['w'] in self._sealed:
-                self._pgrad(a['w'], None)       # raises: the bucket of this weight is already being exchanged
-            job = None
-            if gt is not None and cg.pointwise and self._pw_batch > 0:
-                # pointwise layers: queued, and run as ONE grouped launch per gradient bucket / per `WGRAD_PW_BATCH` layers (a layer launched
-                # alone is split over all CUs and adds 64 MB of partial tiles with float atomics; a shared grid a tenth of that)
-                job = cg.weight_acc_job(x_win if x_win.is_contiguous() else x_win.contiguous(), g_emb, Tw, gt, g_frames=gfr)
-            if job is not None:
-                self._pw_pending.append((a['w'], job))
-                self._deferred[a['w']] = cg.scale
-                if len(self._pw_pending) >= self._pw_batch:
-                    self._flush_pw()
-            elif gt is not None and cg.weight_acc(x_win, g_emb, Tw, gt, g_frames=gfr):
-                self._deferred[a['w']] = cg.scale
-            else:
-                dW, _ = cg.weight(x_win, g_emb, Tw, g_frames=gfr, out=self._pgrad_out(a['w']))
-                self._pgrad(a['w'], dW)
-        if op.inputs[0] not in self.no_grad:
-            f, H, W, _ = xin.t.shape
-            # a gradient of the same frame window that already waits for this input (the block's shortcut): the data-gradient conv
-            # adds into it in its epilogue instead of producing a second tensor for an ATen add
-            into = None
-            pend = self.grads.get(op.inputs[0])
-            if pend and len(pend) == 1:
-                t0, l0, m0 = pend[0]
-                assert not m0, 'a ReLU-masked gradient is the ONLY contribution of its blob (one reader): nothing may be added into it'
-                if l0 == ilo and t0.shape[0] == ihi - ilo and t0.dtype == ops.tdtype(y.dt) and tuple(t0.shape[1:3]) == (H, W) and \
-                        t0.is_contiguous() and not getattr(t0, '_roi_acc', False) and t0.shape[3] == ops.round_up(cg.cin, 64):
-                    into = t0
-            # ReLU backward of the input blob fused into this launch's epilogue: x = relu(...) is read by this conv only, its
-            # gradient has this one contribution, and its producer is a conv this executor differentiates
-            mask = None
-            prod = self.net.producer(op.inputs[0])
-            if (into is None and cfg.HIP.get('FUSE_RELU_BWD', True) and prod is not None and prod.type == 'Conv' and
-                    isinstance(prod.args, dict) and prod.args.get('relu') and self._readers.get(op.inputs[0], 0) == 1 and
-                    not pend and xin.keyframe is None and not xin.t2c and xin.t.shape[3] == ops.round_up(cg.cin, 64)):
-                mask = x_win if x_win.is_contiguous() else None
-            # a queued pointwise weight gradient may still have to READ the tensor the sum would be written into (the block output's gradient
-            # is both branch2c's `g` and the shortcut contribution of the block input): then the sum goes to a new tensor
-            # (byte-range overlap with BOTH operands of every queued job -- an offset view or the x operand would have slipped past
-            #  an equality test of the g operand's start pointer)
-            held = into is not None and any(_bytes_overlap(into, j[1]) or _bytes_overlap(into, j[2]) for _, j in self._pw_pending)
-            # ... and when this conv is the LAST of the blob's readers to contribute (a residual block's output: read by the next block's
-            # first conv and by its shortcut), the same epilogue applies the ReLU backward of the blob's producer to the finished sum
-            # (dat_conv3d_fwd_sum_mask, round 6): that producer's elementwise mask pass (three passes over the block output) goes
-            # (grouped layers have no sum + mask instantiation; a `branch2b` input has one reader, so the case does not arise for them)
-            if (into is not None and cg.groups == 1 and cfg.HIP.get('FUSE_RELU_BWD', True) and cfg.HIP.get('FUSE_RELU_SUM_BWD', True) and _SUM_FUSE_ENV and prod is not None and
-                    prod.type == 'Conv' and isinstance(prod.args, dict) and prod.args.get('relu') and
-                    self._readers.get(op.inputs[0], 0) == 2 and self._ncontrib.get(op.inputs[0], 0) == 1 and
-                    xin.keyframe is None and not xin.t2c and x_win.is_contiguous() and tuple(x_win.shape) == tuple(into.shape) and
-                    x_win.dtype == into.dtype):
-                mask = x_win
-            dx = cg.data(g_emb, Tw, H, W, accumulate_into=into, g_frames=(lo - ilo, n) if xin.N == 1 else None, mask=mask, inplace=not held)
-            if into is None:
-                self._add_grad(op.inputs[0], dx, ilo, masked=mask is not None)
-            else:
-                self._ncontrib[op.inputs[0]] = self._ncontrib.get(op.inputs[0], 0) + 1
-                if held or mask is not None:
-                    self.grads[op.inputs[0]] = [(dx, ilo, mask is not None)]
+        self._launch_conv_bwd(op, cg, plan_conv_bwd(self._conv_bwd_facts(op, cg, y, xin, dy, lo, masked)), y, xin, dy, lo)
+
+    def _conv_bwd_facts(self, op, cg, y, xin, dy, lo, masked):
+        a, src = op.args, op.inputs[0]
+        arena, gt_arena = self.arena or {}, self.gt_arena or {}
+        prod = self.net.producer(src)
+        return ConvBwdFacts(
+            args=a, train_w=self._trainable(a['w']), train_b=self._trainable(a['b']), w_in_arena=a['w'] in arena,
+            b_in_arena=a['b'] in arena, w_in_gt_arena=a['w'] in gt_arena, w_sealed=a['w'] in self._sealed, pw_batch=self._pw_batch,
+            dy=dy, lo=lo, masked=masked, y_frames=y.t.shape[0], y_dt=y.dt, y_keyframe=y.keyframe, src=src, x=xin.t, x_N=xin.N,
+            x_T=xin.T, x_t2c=xin.t2c, x_keyframe=xin.keyframe, waiting=self.ledger.waiting(src),
+            ncontrib=self.ledger.contributions(src), readers=self._readers.get(src, 0),
+            producer=None if prod is None else (prod.type, isinstance(prod.args, dict) and prod.args.get('relu')),
+            in_no_grad=src in self.no_grad, fuse_relu=cfg.HIP.get('FUSE_RELU_BWD', True),
+            fuse_relu_sum=cfg.HIP.get('FUSE_RELU_SUM_BWD', True), sum_env=_SUM_FUSE_ENV, pointwise=cg.pointwise, groups=cg.groups,
+            cin=cg.cin, acc_direct=cg.takes_acc, queued=[(j[1], j[2]) for _, j in self._pw_pending])
+
+    def _launch_conv_bwd(self, op, cg, p, y, xin, dy, lo):
+        a, src = op.args, op.inputs[0]
+        n, cout = dy.shape[0], a['dim_out']
+        dbias = self._pgrad_acc(a['b'], cout) if p.bias is not None else None
+        if p.relu_pass or dbias is not None:
+            g = ops.relu_bias_bwd(dy, y.t[lo:lo + n], y.dt, cout, relu=p.relu_pass, dbias=dbias)
+        else:
+            g = dy
+            if p.zero_pad:
+                dy[..., cout:].zero_()
+        if dbias is not None:
+            self._pgrad(a['b'], dbias)
+        if p.residual is not None:
+            self.ledger.add(a['residual'], ops.upsample2x_bwd(g, y.dt) if p.residual == 'upsample' else g, lo)
+        x_win = xin.t[p.ilo:p.ihi]
+        g_emb = g
+        if p.embed:
+            g_emb = torch.zeros((p.ihi - p.ilo,) + tuple(g.shape[1:]), dtype=g.dtype, device=g.device)
+            g_emb[lo - p.ilo:lo - p.ilo + n] = g
+        if p.wgrad == 'queue':
+            job = cg.weight_acc_job(x_win if x_win.is_contiguous() else x_win.contiguous(), g_emb, p.Tw, self.gt_arena[a['w']],
+                                    g_frames=p.g_frames)
+            assert job is not None, 'planned a queued weight gradient for a layer the direct kernels do not take'
+            self._pw_pending.append((a['w'], job))
+            self._deferred[a['w']] = cg.scale
+            if len(self._pw_pending) >= self._pw_batch:
+                self._flush_pw()
+        elif p.wgrad == 'acc':
+            took = cg.weight_acc(x_win, g_emb, p.Tw, self.gt_arena[a['w']], g_frames=p.g_frames)
+            assert took, 'planned an accumulating weight gradient for a layer the direct kernels do not take'
+            self._deferred[a['w']] = cg.scale
+        elif p.wgrad == 'immediate':
+            dW, _ = cg.weight(x_win, g_emb, p.Tw, g_frames=p.g_frames, out=self._pgrad_out(a['w']))
+            self._pgrad(a['w'], dW)
+        if p.dgrad == 'none':
+            return
+        _, H, W, _ = xin.t.shape
+        summed, masks = p.dgrad in ('sum', 'sum_mask'), p.dgrad in ('mask', 'sum_mask')
+        into = self.ledger.waiting(src)[0].t if summed else None
+        dx = cg.data(g_emb, p.Tw, H, W, accumulate_into=into, g_frames=p.g_frames, mask=x_win if masks else None, inplace=p.inplace)
+        if summed:
+            self.ledger.summed_into(src, dx, masks)
+        else:
+            self.ledger.add(src, dx, p.ilo, masked=masks)
 
     def bwd_SpatialBN(self, i, op):
         """g = dy masked by the fused ReLU (also the residual's gradient), db = sum g, ds = sum g * xhat, and
@@ -462,27 +386,21 @@ class TrainExecutor(Executor):
         ws, a = self.ws, op.args
         out = op.outputs[0]
         y = ws.blobs[out]
-        dy, lo = self._take_grad(out, y.dt)
-        assert not self._last_masked, 'a ReLU-masked gradient reached a SpatialBN (the mask fusions of bwd_Conv are for Conv producers)'
-        self._last_masked = False
+        dy, lo, masked = self.ledger.take(out, y.dt)
+        assert not masked, 'a ReLU-masked gradient reached a SpatialBN (the mask fusions of bwd_Conv are for Conv producers)'
         if dy is None:
             return
         z, st = y.bn
-        assert lo == 0 and dy.shape[0] == z.shape[0] or y.N == 1, 'frame-window gradients assume one clip per forward'
-        dev = {}
-        for key in ('bias', 'scale'):
-            name = a[key]
-            if self._trainable(name):       # the kernel ACCUMULATES: straight into the (zeroed) arena view when there is one
-                dev[key] = self.arena[name] if (self.arena is not None and name in self.arena) else \
-                    torch.zeros(y.C, dtype=torch.float32, device=ws.device)
+        check_one_clip((lo == 0 and dy.shape[0] == z.shape[0]) or y.N == 1)
+        dev = self._norm_pgrads(a, y.C)
         g, sums = ops.bn_bwd_reduce(dy if dy.is_contiguous() else dy.contiguous(), y.t, z, y.dt, y.C, st[0], st[1], frame_lo=lo,
                                     relu=bool(a['relu']), dbeta=dev.get('bias'), dgamma=dev.get('scale'))
         for key, t in dev.items():
             self._pgrad(a[key], t)
         if a['residual']:
-            self._add_grad(a['residual'], g, lo)
+            self.ledger.add(a['residual'], g, lo)
         if op.inputs[0] not in self.no_grad:
-            self._add_grad(op.inputs[0], ops.bn_bwd_apply(g, z, y.dt, y.C, st[0], st[1], st[2], sums, frame_lo=lo), 0)
+            self.ledger.add(op.inputs[0], ops.bn_bwd_apply(g, z, y.dt, y.C, st[0], st[1], st[2], sums, frame_lo=lo), 0)
 
     def bwd_GroupNorm(self, i, op):
         """g = dy masked by the fused ReLU (also the residual's gradient), dbias = sum g, dscale = sum g * xhat, and
@@ -491,19 +409,13 @@ class TrainExecutor(Executor):
         ws, a = self.ws, op.args
         out = op.outputs[0]
         y = ws.blobs[out]
-        dy, lo = self._take_grad(out, y.dt)
-        assert not self._last_masked, 'a ReLU-masked gradient reached a GroupNorm (the mask fusions of bwd_Conv are for Conv producers)'
-        self._last_masked = False
+        dy, lo, masked = self.ledger.take(out, y.dt)
+        assert not masked, 'a ReLU-masked gradient reached a GroupNorm (the mask fusions of bwd_Conv are for Conv producers)'
         if dy is None:
             return
         z, st = y.bn
-        assert lo == 0 and dy.shape[0] == z.shape[0] or (y.N == 1 and not y.roi), 'frame-window gradients assume one clip per forward'
-        dev = {}
-        for key in ('bias', 'scale'):
-            name = a[key]
-            if self._trainable(name):       # the kernel ACCUMULATES: straight into the (zeroed) arena view when there is one
-                dev[key] = self.arena[name] if (self.arena is not None and name in self.arena) else \
-                    torch.zeros(y.C, dtype=torch.float32, device=ws.device)
+        check_one_clip((lo == 0 and dy.shape[0] == z.shape[0]) or (y.N == 1 and not y.roi))
+        dev = self._norm_pgrads(a, y.C)
         if y.roi:       # per-RoI blob: the fused backward (a per-RoI gradient always covers the RoI's frames)
             need_dz = op.inputs[0] not in self.no_grad
             g, dz, _ = ops.gn_roi_bwd(dy if dy.is_contiguous() else dy.contiguous(), y.t, z, y.dt, y.C, a['groups'], st[0], st[1],
@@ -512,9 +424,9 @@ class TrainExecutor(Executor):
             for key, t in dev.items():
                 self._pgrad(a[key], t)
             if a['residual']:
-                self._add_grad(a['residual'], g, 0)
+                self.ledger.add(a['residual'], g, 0)
             if need_dz:
-                self._add_grad(op.inputs[0], dz, 0)
+                self.ledger.add(op.inputs[0], dz, 0)
             return
         g, _, coef = ops.gn_bwd_reduce(dy if dy.is_contiguous() else dy.contiguous(), y.t, z, y.dt, y.C, a['groups'], st[0], st[1],
                                        self._master(a['scale']), clips=y.N, frame_lo=lo, relu=bool(a['relu']), dbeta=dev.get('bias'),
@@ -522,16 +434,16 @@ class TrainExecutor(Executor):
         for key, t in dev.items():
             self._pgrad(a[key], t)
         if a['residual']:
-            self._add_grad(a['residual'], g, lo)
+            self.ledger.add(a['residual'], g, lo)
         if op.inputs[0] not in self.no_grad:
-            self._add_grad(op.inputs[0], ops.gn_bwd_apply(g, z, y.dt, y.C, st[0], st[2], coef, clips=y.N, frame_lo=lo), 0)
+            self.ledger.add(op.inputs[0], ops.gn_bwd_apply(g, z, y.dt, y.C, st[0], st[2], coef, clips=y.N, frame_lo=lo), 0)
 
     def _bwd_rpn_head(self, i):
         ws = self.ws
         lo, do, gi = self._fused[i]
         name = lo.outputs[0] + '+' + do.outputs[0]
         y = ws.blobs[name]
-        dy, _lo = self._take_grad(name, y.dt)
+        dy, _lo, _ = self.ledger.take(name, y.dt)
         if dy is None:
             return
         xin = ws.blobs[lo.inputs[0]]
@@ -544,7 +456,7 @@ class TrainExecutor(Executor):
         if xin.t2c:
             # heads over time-moved-to-channels (FPN tube RPN, channel index t*C + c): one 1x1 weight slice per input frame;
             # the head has ONE output frame per clip, every input frame gets its own data gradient
-            assert xin.N == 1, 'tube RPN training assumes one clip per forward (TRAIN.IMS_PER_BATCH 1)'
+            check_one_clip(xin.N == 1, what='tube RPN training assumes', hint=True)
             T, C = xin.T, xin.C
             f, H, W, cs = xin.t.shape
             wT = w.view(A + D, T, C)
@@ -555,43 +467,37 @@ class TrainExecutor(Executor):
                 dWs.append(dW_t.reshape(A + D, C))
                 dxs.append(cg.data(g, 1, H, W))
             dW = torch.stack(dWs, dim=1).reshape(A + D, T * C)
-            self._pgrad(lo.args['w'], dW[:A])
-            self._pgrad(do.args['w'], dW[A:])
-            self._pgrad(lo.args['b'], dbias[:A])
-            self._pgrad(do.args['b'], dbias[A:])
-            self._add_grad(lo.inputs[0], torch.cat(dxs, dim=0))
-            return
-        # (the levels above the first share the parameters: one ConvGrad -- one pack of the data-gradient weights -- per iteration)
-        ck = ('rpnhead', lo.args['w'], do.args['w'], int(xin.t.shape[3]), int(g.shape[3]))
-        cg = self._iter_cache.get(ck)
-        if cg is None:
-            cg = self._iter_cache[ck] = ops.ConvGrad(w.view(A + D, -1, 1, 1, 1), None, (1, 1), (0, 0, 0), y.dt, xin.t.shape[3], g.shape[3])
-        dW, _ = cg.weight(xin.t, g, xin.T)
+            dx = lambda: torch.cat(dxs, dim=0)
+        else:
+            # (the levels above the first share the parameters: one ConvGrad -- one pack of the data-gradient weights -- per iteration)
+            ck = ('rpnhead', lo.args['w'], do.args['w'], int(xin.t.shape[3]), int(g.shape[3]))
+            cg = self._iter_cache.get(ck)
+            if cg is None:
+                cg = self._iter_cache[ck] = ops.ConvGrad(w.view(A + D, -1, 1, 1, 1), None, (1, 1), (0, 0, 0), y.dt, xin.t.shape[3], g.shape[3])
+            dW, _ = cg.weight(xin.t, g, xin.T)
+            dx = lambda: cg.data(g, xin.T, xin.t.shape[1], xin.t.shape[2])
         self._pgrad(lo.args['w'], dW[:A])
         self._pgrad(do.args['w'], dW[A:])
         self._pgrad(lo.args['b'], dbias[:A])
         self._pgrad(do.args['b'], dbias[A:])
-        f, H, W, _ = xin.t.shape
-        self._add_grad(lo.inputs[0], cg.data(g, xin.T, H, W))
+        self.ledger.add(lo.inputs[0], dx())         # (made after the parameter gradients were added, in both forms)
 
     def bwd_TimeToChannel(self, i, op):
         # a re-interpretation of the same [T, H, W, C] tensor: the gradient passes through unchanged
         x = self.ws.blobs[op.inputs[0]]
-        dy, lo = self._take_grad(op.outputs[0], x.dt)
+        dy, lo, _ = self.ledger.take(op.outputs[0], x.dt)
         if dy is not None:
-            self._add_grad(op.inputs[0], dy, lo)
+            self.ledger.add(op.inputs[0], dy, lo)
 
     def bwd_FC(self, i, op):
         ws, a = self.ws, op.args
         out = op.outputs[0]
         y = ws.blobs[out]
-        dy, _lo = self._take_grad(out, y.dt)
+        dy, _lo, _ = self.ledger.take(out, y.dt)
         if dy is None:
             return
         x = ws.blobs[op.inputs[0]]
-        # (the kernel ACCUMULATES the bias reduction: straight into the zeroed arena view when there is one -- no fill, no add)
-        dbias = self.arena[a['b']] if (self.arena is not None and a['b'] in self.arena) else \
-            torch.zeros(a['dim_out'], dtype=torch.float32, device=ws.device)
+        dbias = self._pgrad_acc(a['b'], a['dim_out'])
         g = ops.relu_bias_bwd(dy, y.t, y.dt, a['dim_out'], relu=a['relu'], dbias=dbias)
         self._pgrad(a['b'], dbias)
         w = self._master(a['w'])
@@ -625,13 +531,13 @@ class TrainExecutor(Executor):
             dx = cg.data(g, 1, 1, xin.shape[2])
             if x.kind == 'fmap':
                 dx = dx[..., :cin_real].reshape(x.t.shape)
-            self._add_grad(op.inputs[0], dx)
+            self.ledger.add(op.inputs[0], dx)
 
     def bwd_ConvTranspose(self, i, op):
         ws, a = self.ws, op.args
         out = op.outputs[0]
         y = ws.blobs[out]
-        dy, _lo = self._take_grad(out, y.dt)
+        dy, _lo, _ = self.ledger.take(out, y.dt)
         if dy is None:
             return
         x = ws.blobs[op.inputs[0]]
@@ -647,7 +553,7 @@ class TrainExecutor(Executor):
         dW3, _ = cg.weight(x.t, g, 1)                  # [4K, Cin, 1, 3, 3]
         self._pgrad(a['w'], self._deconv_filter_grad(dW3, K, Cin))
         f, H, W, _ = x.t.shape
-        self._add_grad(op.inputs[0], cg.data(g, 1, H, W))
+        self.ledger.add(op.inputs[0], cg.data(g, 1, H, W))
 
     def _deconv_filter_grad(self, dW3, K, Cin):
         """Gradient of the sub-pixel conv weight [4K, Cin, 1, 3, 3] -> gradient of the ConvTranspose filter [Cin, K, 4, 4]: the transpose of
@@ -699,29 +605,29 @@ class TrainExecutor(Executor):
             k = TK // T
             self._pgrad(a['w'], torch.cat([dWs[t][:, t * k:(t + 1) * k] for t in range(T)], dim=0).contiguous())
         if dxs:
-            self._add_grad(op.inputs[0], torch.stack(dxs, dim=1).reshape(f, H, W, dxs[0].shape[3]))
+            self.ledger.add(op.inputs[0], torch.stack(dxs, dim=1).reshape(f, H, W, dxs[0].shape[3]))
 
     def bwd_BilinearInterpolation(self, i, op):
         ws = self.ws
-        d, _lo = self._take_grad(op.outputs[0], ops.F32)
+        d, _lo, _ = self.ledger.take(op.outputs[0], ops.F32)
         if d is None:
             return
         x = ws.blobs[op.inputs[0]]
         f, S, _, cs = x.t.shape
         K, up = op.args['dim'], op.args['up_scale']
-        self._add_grad(op.inputs[0], ops.kps_finalize_bwd(d.contiguous(), x.dt, x.N, x.T, S, cs, K, up))
+        self.ledger.add(op.inputs[0], ops.kps_finalize_bwd(d.contiguous(), x.dt, x.N, x.T, S, cs, K, up))
 
     def bwd_TubeDeltasToRows(self, i, op):
         """rows [R, K*T*4] -> head output [R*T, 1, 1, cs] with channels (k, xywh) per frame (model_builder.py:446-473)"""
         x = self.ws.blobs[op.inputs[0]]
-        d, _lo = self._take_grad(op.outputs[0], ops.F32)
+        d, _lo, _ = self.ledger.take(op.outputs[0], ops.F32)
         if d is None:
             return
         R, T, cs = x.N, x.T, x.t.shape[3]
         K4 = x.C
         g = torch.zeros((R, T, cs), dtype=torch.float32, device=d.device)
         g[:, :, :K4] = d.view(R, K4 // 4, T, 4).permute(0, 2, 1, 3).reshape(R, T, K4)
-        self._add_grad(op.inputs[0], g.view(R * T, 1, 1, cs))
+        self.ledger.add(op.inputs[0], g.view(R * T, 1, 1, cs))
 
     def bwd_TimeMean(self, i, op):
         """scores averaged over the T frames of each RoI: every frame receives d / T"""
@@ -729,35 +635,34 @@ class TrainExecutor(Executor):
         y = self.ws.blobs[op.outputs[0]]
         if y.kind != 'rows':
             return          # the RPN's TimeMean is folded into the proposal / loss kernels
-        d, _lo = self._take_grad(op.outputs[0], ops.F32)
+        d, _lo, _ = self.ledger.take(op.outputs[0], ops.F32)
         if d is None:
             return
         R, T, cs = x.N, x.T, x.t.shape[3]
         g = torch.zeros((R, T, cs), dtype=torch.float32, device=d.device)
         g[:, :, :x.C] = (d.view(R, 1, -1)[:, :, :x.C] / float(T))
-        self._add_grad(op.inputs[0], g.view(R * T, 1, 1, cs))
+        self.ledger.add(op.inputs[0], g.view(R * T, 1, 1, cs))
 
     def bwd_SpatialMean(self, i, op):
         x = self.ws.blobs[op.inputs[0]]
-        d, _lo = self._take_grad(op.outputs[0], x.dt)
+        d, _lo, _ = self.ledger.take(op.outputs[0], x.dt)
         if d is None:
             return
         f, h, w, cs = x.t.shape
-        self._add_grad(op.inputs[0], (d.view(f, 1, 1, cs).float() / float(h * w)).to(d.dtype).expand(f, h, w, cs).contiguous())
+        self.ledger.add(op.inputs[0], (d.view(f, 1, 1, cs).float() / float(h * w)).to(d.dtype).expand(f, h, w, cs).contiguous())
 
     def bwd_TimePoolAvg(self, i, op):
         """BODY_HEAD_LINK 'avg' (detector.py:559-569): every frame receives d / T"""
         x = self.ws.blobs[op.inputs[0]]
-        d, _lo = self._take_grad(op.outputs[0], x.dt)
+        d, _lo, _ = self.ledger.take(op.outputs[0], x.dt)
         if d is None:
             return
         f, h, w, cs = x.t.shape
         g = (d.view(x.N, 1, h, w, cs).float() / float(x.T)).to(d.dtype).expand(x.N, x.T, h, w, cs).reshape(f, h, w, cs)
-        self._add_grad(op.inputs[0], g.contiguous())
+        self.ledger.add(op.inputs[0], g.contiguous())
 
     def bwd_TimeToBatch(self, i, op):
-        if op.outputs[0] in self.grads:
-            self.grads.setdefault(op.inputs[0], []).extend(self.grads.pop(op.outputs[0]))
+        self.ledger.move(op.outputs[0], op.inputs[0])
 
     bwd_Alias = bwd_TimeToBatch
     bwd_BatchToTime = bwd_TimeToBatch       # (views of the keypoint maps in the order they were written: the gradient passes through as it is)
@@ -765,7 +670,7 @@ class TrainExecutor(Executor):
     def bwd_RoIFeatureTransform(self, i, op):
         ws, a = self.ws, op.args
         y = ws.blobs[op.outputs[0]]
-        dy, _lo = self._take_grad(op.outputs[0], y.dt)
+        dy, _lo, _ = self.ledger.take(op.outputs[0], y.dt)
         if dy is None:
             return
         names = op.inputs[:a['n_feat']]
@@ -774,34 +679,24 @@ class TrainExecutor(Executor):
         rt = rois.t.view(-1, rois.t.shape[-1]).float().contiguous()
         R = _count(rois) if rois.count is not None else rt.shape[0]
         Tr = (rt.shape[1] - 1) // 4
-        accs = []
-        for n, f in zip(names, feats):
-            acc = None
-            for t, _l, _m in self.grads.get(n, []):
-                if t.dtype == torch.float32 and getattr(t, '_roi_acc', False):
-                    acc = t
-            if acc is None:
-                acc = torch.zeros(f.t.shape, dtype=torch.float32, device=ws.device)
-                acc._roi_acc = True
-                self._add_grad(n, acc)
-            accs.append(acc)
+        accs = [self.ledger.roi_accumulator(n, f.t.shape, ws.device) for n, f in zip(names, feats)]
         ops.roi_align_bwd(accs, a['scales'], y.dt, rt[:R], dy, T=feats[0].T, Tr=Tr, t0=0, pooled=a['resolution'],
                           sampling=a['sampling_ratio'], k_min=cfg.FPN.ROI_MIN_LEVEL,
                           canon_scale=float(cfg.FPN.ROI_CANONICAL_SCALE), canon_level=cfg.FPN.ROI_CANONICAL_LEVEL)
 
     def bwd_SliceKeyFrame(self, i, op):
         x = self.ws.blobs[op.inputs[0]]
-        dy, _lo = self._take_grad(op.outputs[0], x.dt)
+        dy, _lo, _ = self.ledger.take(op.outputs[0], x.dt)
         if dy is None:
             return
         k = op.args['keyframe']
         if x.N == 1:
-            self._add_grad(op.inputs[0], dy, k)          # a one-frame window: no zero-filled T-frame tensor
+            self.ledger.add(op.inputs[0], dy, k)          # a one-frame window: no zero-filled T-frame tensor
             return
         g = torch.zeros_like(x.t)
         f, h, w, c = x.t.shape
         g.view(x.N, x.T, h, w, c)[:, k] = dy.view(x.N, h, w, c)
-        self._add_grad(op.inputs[0], g)
+        self.ledger.add(op.inputs[0], g)
 
     def bwd_MaxPool(self, i, op):
         """Above the frozen trunk sit the P6 'sub-sampling' pool (kernel 1, stride 2; FPN3D.py:155-164) and the 2 x 2 / stride 2 pools of
@@ -809,19 +704,19 @@ class TrainExecutor(Executor):
         the gradient stays that window."""
         a = op.args
         x = self.ws.blobs[op.inputs[0]]
-        dy, lo = self._take_grad(op.outputs[0], x.dt)
+        dy, lo, _ = self.ledger.take(op.outputs[0], x.dt)
         if dy is None:
             return
         if a['k'] == 1 and a['stride'] == 2 and a['pad'] == 0:
             g = torch.zeros((dy.shape[0],) + tuple(x.t.shape[1:]), dtype=x.t.dtype, device=x.t.device)
             g[:, ::2, ::2] = dy
-            self._add_grad(op.inputs[0], g, lo)
+            self.ledger.add(op.inputs[0], g, lo)
             return
         assert a['k'] <= a['stride'], 'max-pool backward above the frozen trunk: non-overlapping windows only (kernel %d, stride %d)' % (
             a['k'], a['stride'])
         n = dy.shape[0]
-        assert (lo == 0 and n == x.t.shape[0]) or x.N == 1, 'frame-window gradients assume one clip per forward'
-        self._add_grad(op.inputs[0], ops.maxpool_hw_bwd(x.t[lo:lo + n], dy if dy.is_contiguous() else dy.contiguous(), x.dt, a['k'],
+        check_one_clip((lo == 0 and n == x.t.shape[0]) or x.N == 1)
+        self.ledger.add(op.inputs[0], ops.maxpool_hw_bwd(x.t[lo:lo + n], dy if dy.is_contiguous() else dy.contiguous(), x.dt, a['k'],
                                                         a['stride'], a['pad']), lo)
 
     def bwd_NonLocalAttention(self, i, op):
@@ -830,12 +725,12 @@ class TrainExecutor(Executor):
         clip hear from the window's queries)."""
         ws, a = self.ws, op.args
         y = ws.blobs[op.outputs[0]]
-        dy, lo = self._take_grad(op.outputs[0], y.dt)
+        dy, lo, _ = self.ledger.take(op.outputs[0], y.dt)
         if dy is None:
             return
         q, k, v = (ws.blobs[n] for n in op.inputs)
         n, D = dy.shape[0], a['dim']
-        assert (lo == 0 and n == y.t.shape[0]) or q.N == 1, 'frame-window gradients assume one clip per forward (TRAIN.IMS_PER_BATCH 1)'
+        check_one_clip((lo == 0 and n == y.t.shape[0]) or q.N == 1, hint=True)
         assert y.lse is not None, 'the forward of %r did not keep its row statistic (not a training executor)' % (op.outputs[0],)
         assert all(t.shape[3] == D for t in (q.t, k.t, v.t, y.t, dy)), (D, [tuple(t.shape) for t in (q.t, k.t, v.t, y.t, dy)])
         per = q.t.shape[1] * q.t.shape[2]
@@ -845,7 +740,7 @@ class TrainExecutor(Executor):
                                                 q.N, D, a['scale'])
         for name, x, g, l in ((op.inputs[0], q, dq, lo), (op.inputs[1], k, dk, 0), (op.inputs[2], v, dv, 0)):
             if name not in self.no_grad:
-                self._add_grad(name, g.view((-1,) + tuple(x.t.shape[1:])), l)
+                self.ledger.add(name, g.view((-1,) + tuple(x.t.shape[1:])), l)
 
     def bwd_AffineTrain(self, i, op):
         """The trainable closing affine of a non-local block, y = z * s + b (+ residual): g = dy (also the residual's gradient),
@@ -854,28 +749,23 @@ class TrainExecutor(Executor):
         ws, a = self.ws, op.args
         out = op.outputs[0]
         y = ws.blobs[out]
-        dy, lo = self._take_grad(out, y.dt)
-        assert not self._last_masked, 'a ReLU-masked gradient reached an AffineTrain (the mask fusions of bwd_Conv are for Conv producers)'
+        dy, lo, masked = self.ledger.take(out, y.dt)
+        assert not masked, 'a ReLU-masked gradient reached an AffineTrain (the mask fusions of bwd_Conv are for Conv producers)'
         if dy is None:
             return
         z, s_tab = y.bn
-        assert (lo == 0 and dy.shape[0] == z.shape[0]) or y.N == 1, 'frame-window gradients assume one clip per forward'
+        check_one_clip((lo == 0 and dy.shape[0] == z.shape[0]) or y.N == 1)
         cs = z.shape[3]
-        dev = {}
-        for key in ('bias', 'scale'):
-            name = a[key]
-            if self._trainable(name):       # the kernel ACCUMULATES: straight into the (zeroed) arena view when there is one
-                dev[key] = self.arena[name] if (self.arena is not None and name in self.arena) else \
-                    torch.zeros(y.C, dtype=torch.float32, device=ws.device)
+        dev = self._norm_pgrads(a, y.C)
         zero, one = torch.zeros(cs, dtype=torch.float32, device=ws.device), torch.ones(cs, dtype=torch.float32, device=ws.device)
         g, _ = ops.bn_bwd_reduce(dy if dy.is_contiguous() else dy.contiguous(), y.t, z, y.dt, y.C, zero, one, frame_lo=lo,
                                  relu=bool(a['relu']), dbeta=dev.get('bias'), dgamma=dev.get('scale'))
         for key, t in dev.items():
             self._pgrad(a[key], t)
         if a['residual']:
-            self._add_grad(a['residual'], g, lo)
+            self.ledger.add(a['residual'], g, lo)
         if op.inputs[0] not in self.no_grad:
-            self._add_grad(op.inputs[0], ops.bn_apply(g, y.dt, y.C, s_tab, zero), lo)
+            self.ledger.add(op.inputs[0], ops.bn_apply(g, y.dt, y.C, s_tab, zero), lo)
 
     # ---- update ---------------------------------------------------------------------------------------------------------------
     def loss_values(self):
@@ -883,12 +773,6 @@ class TrainExecutor(Executor):
 
 
 _SUM_FUSE_ENV = os.environ.get('DAT_FUSE_RELU_SUM_BWD', '1') != '0'       # experiment switch for same-box A/B runs (cfg.HIP.FUSE_RELU_SUM_BWD is the setting)
-
-
-def _bytes_overlap(a, b):
-    """Do the memory extents of two (dense) tensors intersect?"""
-    a0, b0 = a.data_ptr(), b.data_ptr()
-    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
 
 
 def no_grad_blobs(net):
@@ -1239,13 +1123,3 @@ class Trainer(object):
         for n, m in (blobs or {}).items():
             if n in self.momentum:
                 self.momentum[n].copy_(torch.from_numpy(np.ascontiguousarray(m, dtype=np.float32)).to(self.flat_v.device).view_as(self.momentum[n]))
-
-    def _all_reduce(self):
-        """Serial bucketed sum all-reduce over slices of the flat gradient buffer (losses are already divided by NUM_GPUS,
-        model_builder.py:932-942): the exchange without overlap, BUCKET_BYTES per collective."""
-        per = max(1, self.BUCKET_BYTES // 4)
-        n = self.flat_g.numel()
-        x = GradExchange(self.flat_g, [(off, min(off + per, n)) for off in range(0, n, per)], self.dist, overlap=False,
-                         direct=(ops.BucketAllReduce(self.dist.get_rank(), self.dist.get_world_size())
-                                 if cfg.HIP.get('RCCL_DIRECT', False) and self.flat_g.is_cuda else None))
-        x.finish()

@@ -427,20 +427,19 @@ def _allreduce_worker(rank, world, port, q):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group('gloo', rank=rank, world_size=world)
-    from detectandtrack_amd.training import Trainer
-    t = Trainer.__new__(Trainer)
-    t.dist = dist
-    t.BUCKET_BYTES = 4096          # force several buckets
+    from detectandtrack_amd.training import GradExchange
+    per = 4096 // 4                # force several buckets
     g = torch.Generator().manual_seed(100 + rank)
     # the Trainer's flat gradient buffer with per-parameter views into it (training.py): reduced in bucket-sized slices, in place
     sizes = (7, 300, 1500, 64, 2000, 5)
-    t.flat_g = torch.randn(sum(sizes), generator=g)
+    flat_g = torch.randn(sum(sizes), generator=g)
     tensors, off = [], 0
     for n in sizes:
-        tensors.append(t.flat_g[off:off + n])
+        tensors.append(flat_g[off:off + n])
         off += n
     local = [x.clone() for x in tensors]
-    t._all_reduce()
+    n = flat_g.numel()
+    GradExchange(flat_g, [(off, min(off + per, n)) for off in range(0, n, per)], dist, overlap=False).finish()
     q.put((rank, [x.numpy() for x in local], [x.numpy() for x in tensors]))
     dist.destroy_process_group()
 
@@ -1001,33 +1000,36 @@ def test_clips_given_as_image_files_are_decoded_to_bgr_frames(tmp_path):
 
 
 def test_gradient_contributions_of_a_blob_are_summed_over_their_frame_windows():
-    """TrainExecutor._take_grad (training.py): contributions (tensor, first frame, masked) of one blob -- full-window tensors, shorter
+    """GradLedger.take (train_plan.py): contributions (tensor, first frame, masked) of one blob -- full-window tensors, shorter
     windows, another dtype (the fp32 RoIAlign accumulators) -- come back as ONE tensor over the union of the windows; a single
     contribution is passed through untouched and keeps its `masked` flag; the inputs are not modified."""
-    import types
     import torch
-    from detectandtrack_amd import training
+    from detectandtrack_amd.train_plan import GradLedger
     from detectandtrack_amd.ops import hip_ops as ops
     g = torch.Generator().manual_seed(0)
     rnd = lambda *s: torch.randn(*s, generator=g)
-    for dt, tdt in ((ops.F32, torch.float32), (ops.BF16, torch.bfloat16)):
-        ex = types.SimpleNamespace(grads={}, _last_masked=False, _ncontrib={})
-        take = lambda name: training.TrainExecutor._take_grad(ex, name, dt)
-        assert take('none') == (None, 0)
+    for dt in (ops.F32, ops.BF16):
+        tdt = ops.tdtype(dt)        # (the 16-bit format is the loaded build's)
+        led = GradLedger()
+        take = lambda name: led.take(name, dt)
+        assert take('none') == (None, 0, False)
         # one contribution: the tensor itself, the mask flag survives
         t = rnd(3, 2, 2, 4).to(tdt)
-        ex.grads['a'] = [(t, 1, True)]
-        out, lo = take('a')
-        assert out is t and lo == 1 and ex._last_masked and 'a' not in ex.grads
+        led.add('a', t, 1, masked=True)
+        out, lo, masked = take('a')
+        assert out is t and lo == 1 and masked and not led.waiting('a')
         # two full windows + a one-frame window + an fp32 accumulator marked as the RoIAlign backward's
         a, b = rnd(3, 2, 2, 4).to(tdt), rnd(3, 2, 2, 4).to(tdt)
         c = rnd(1, 2, 2, 4).to(tdt)
-        r = rnd(3, 2, 2, 4)
-        r._roi_acc = True
+        r = led.roi_accumulator('b', (3, 2, 2, 4), 'cpu')       # (waits for frames [0, 3) like every RoIAlign accumulator)
+        assert led.roi_accumulator('b', (3, 2, 2, 4), 'cpu') is r and led.contributions('b') == 1
+        r.copy_(rnd(3, 2, 2, 4))
         keep = [x.clone() for x in (a, b, c, r)]
-        ex.grads['b'] = [(r, 2, False), (a, 2, False), (c, 3, False), (b, 2, False)]
-        out, lo = take('b')
-        assert lo == 2 and out.dtype == tdt and tuple(out.shape) == (3, 2, 2, 4) and not ex._last_masked
+        led.add('b', a, 0)
+        led.add('b', c, 1)
+        led.add('b', b, 0)
+        out, lo, masked = take('b')
+        assert lo == 0 and out.dtype == tdt and tuple(out.shape) == (3, 2, 2, 4) and not masked
         ref = a.float() + b.float() + r
         ref[1:2] += c.float()
         tol = 1e-6 if tdt == torch.float32 else 0.05
@@ -1035,8 +1037,9 @@ def test_gradient_contributions_of_a_blob_are_summed_over_their_frame_windows():
         for x, k in zip((a, b, c, r), keep):
             assert torch.equal(x, k)
         # windows that only overlap: the union is allocated
-        ex.grads['c'] = [(c, 0, False), (rnd(2, 2, 2, 4).to(tdt), 1, False)]
-        out, lo = take('c')
+        led.add('c', c, 0)
+        led.add('c', rnd(2, 2, 2, 4).to(tdt), 1)
+        out, lo, _ = take('c')
         assert lo == 0 and tuple(out.shape) == (3, 2, 2, 4)
         assert (out[0:1].float() - c.float()).abs().max() < tol
 
